@@ -86,6 +86,43 @@ def mixed_scene_flops(tokens):
     return total
 
 
+DUMP_SAMPLE = 1 << 19          # elements kept per dumped array (--dump-outputs)
+DUMP_BUDGET = 64 * 1024 * 1024  # bytes written by --dump-outputs in all
+
+
+def _output_arrays(obj, name):
+    """(name, tensor) for every tensor in a run_scenes / run_scene result; lists and tuples are numbered, plain ints dropped."""
+    if isinstance(obj, torch.Tensor):
+        yield name, obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from _output_arrays(v, f"{name}_{k}" if name else str(k))
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            yield from _output_arrays(v, f"{name}_{i:02d}")
+
+
+def dump_outputs(out, out_dir):
+    """Write every output array of one step as out_dir/<name>.npy.  An array of more than DUMP_SAMPLE elements is reduced to
+    the elements at DUMP_SAMPLE flat indices drawn (sorted, with replacement) from a generator seeded by its name and shape, so two runs with the
+    same arguments sample the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in _output_arrays(out, ""):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(f"{name}{tuple(t.shape)}".encode()))
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        a = flat.to(dt).cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_BUDGET, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget at {name}"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -110,7 +147,13 @@ def main():
                     "this command has per-symbol averages that equal the line's (scripts/gpu_profile_r04.sh)")
     ap.add_argument("--stream-frames", type=int, default=200)
     ap.add_argument("--cpu-timeout", type=float, default=420.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, or float64 for integer "
+                         "outputs): every array a caller of run_scenes / run_scene receives, each reduced to a fixed, seeded sample of at most "
+                         f"{DUMP_SAMPLE} elements of its flattened form (rank 0 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.step_only:
         args.no_single = args.no_configs = args.no_alt = args.no_cpu_baseline = True
 
@@ -161,22 +204,27 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
-    def timed(fn, nsteps):
+    def timed(fn, nsteps, keep_last=False):
         sync()
         t0 = time.perf_counter()
+        out = None
         for _ in range(nsteps):
-            fn()
+            out = None   # the previous step's result is released before the next step runs, as when it is discarded
+            out = fn()
         sync()
         dt = time.perf_counter() - t0
         if world > 1:
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt
+        return (dt, out) if keep_last else dt
 
     for _ in range(max(args.warmup, 1)):
         step()
-    dt = timed(step, args.steps)
+    dt, last_out = timed(step, args.steps, keep_last=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out, args.dump_outputs)
+    del last_out
     views_per_step = Sn * V * world
     value = views_per_step * args.steps / dt
 

@@ -50,3 +50,127 @@ def rel_inf_view(a_sub, ref_sub, vmax):
 
 
 from must3r_amd.synthetic import make_cam_pointmaps as cam_scene  # noqa: E402,F401
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The reference's side of tests/test_oracle_vs_reference.py.  Where the reference tree exists (conftest.HAS_REFERENCE) every
+# value is computed live, as it always was; with M3R_RECORD_REFERENCE=1 it is also kept, in call order, and the whole set is
+# written to tests/golden/reference_values.pt.xz (torch.save, xz-compressed).  Elsewhere the tests read those values back, so
+# the restatements are checked against the reference's own outputs without its source.  To keep the file small, a value
+# recorded with ``sample=True`` keeps each floating-point tensor of more than SAMPLE_MIN elements as every SAMPLE_STRIDE-th
+# element of its flattened form (17 is coprime to the 7 pointmap channels and to the 128 / 256 feature widths, so every channel
+# of every pixel or token row is reached), and the tests compare ``ref.px(ours)``, the same sample of their own tensor.  Values
+# a test only compares for equality are recorded as ``digest(value)``.
+# ----------------------------------------------------------------------------------------------------------------------
+REFERENCE_VALUES = os.path.join(GOLDEN, "reference_values.pt.xz")
+RECORD_REFERENCE = os.environ.get("M3R_RECORD_REFERENCE") == "1"
+SAMPLE_STRIDE = 17
+SAMPLE_MIN = 1024
+_recorded = None
+
+
+def _stored(v):
+    """a copy of v that later in-place updates of the live objects cannot change"""
+    if torch.is_tensor(v):
+        return v.detach().clone()
+    if isinstance(v, np.ndarray):
+        return v.copy()
+    if isinstance(v, dict):
+        return {k: _stored(u) for k, u in v.items()}
+    if isinstance(v, (list, tuple)):
+        return type(v)(_stored(u) for u in v)
+    return v
+
+
+def _sample(v):
+    if torch.is_tensor(v) and v.is_floating_point() and v.numel() > SAMPLE_MIN:
+        return v.detach().reshape(-1)[::SAMPLE_STRIDE]
+    if isinstance(v, dict):
+        return {k: _sample(u) for k, u in v.items()}
+    if isinstance(v, (list, tuple)):
+        return type(v)(_sample(u) for u in v)
+    return v
+
+
+def digest(v):
+    """v with every tensor / array replaced by (kind, shape, dtype, sha256 of its bytes): equal digests = bit-equal values"""
+    import hashlib
+    if isinstance(v, dict):
+        return {k: digest(u) for k, u in v.items()}
+    if isinstance(v, (list, tuple)):
+        return type(v)(digest(u) for u in v)
+    if torch.is_tensor(v):
+        t = v.detach().contiguous()
+        return ("tensor", tuple(t.shape), str(t.dtype), hashlib.sha256(t.reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest())
+    if isinstance(v, np.ndarray):
+        a = np.ascontiguousarray(v)
+        return ("ndarray", a.shape, str(a.dtype), hashlib.sha256(a.tobytes()).hexdigest())
+    return v
+
+
+def _load_reference_values():
+    import io
+    import lzma
+    with open(REFERENCE_VALUES, "rb") as f:
+        return torch.load(io.BytesIO(lzma.decompress(f.read())), weights_only=False)
+
+
+def reference_values():
+    global _recorded
+    if _recorded is None:
+        _recorded = {} if RECORD_REFERENCE else _load_reference_values()
+    return _recorded
+
+
+def save_reference_values():
+    if RECORD_REFERENCE and _recorded:
+        import io
+        import lzma
+        vals = _load_reference_values() if os.path.exists(REFERENCE_VALUES) else {}
+        vals.update(_recorded)
+        buf = io.BytesIO()
+        torch.save(dict(sorted(vals.items())), buf)
+        with open(REFERENCE_VALUES, "wb") as f:
+            f.write(lzma.compress(buf.getvalue(), preset=9 | lzma.PRESET_EXTREME))
+
+
+class Reference:
+    """``ref(lambda: <reference expression>)`` is the expression's value: computed live where the reference tree exists (and
+    recorded with M3R_RECORD_REFERENCE=1), read back in call order elsewhere.  ``ref.live(lambda: ...)`` builds a reference
+    object only the live runs use (None otherwise)."""
+
+    def __init__(self, key):
+        from conftest import HAS_REFERENCE
+        self.is_live = HAS_REFERENCE
+        self.i = 0
+        if RECORD_REFERENCE:
+            self.vals = reference_values()[key] = []
+        elif not self.is_live:
+            vals = reference_values()
+            assert key in vals, f"{key}: not in {os.path.relpath(REFERENCE_VALUES)}; record it with M3R_RECORD_REFERENCE=1"
+            self.vals = vals[key]
+
+    def live(self, fn):
+        return fn() if self.is_live else None
+
+    def px(self, t):
+        """our side of a comparison with a value recorded with ``sample=True``"""
+        return t if self.is_live else _sample(t)
+
+    def __call__(self, fn, sample=False):
+        if self.is_live:
+            try:
+                v = fn()
+            except Exception as e:
+                if RECORD_REFERENCE:
+                    self.vals.append({"__raised__": type(e).__name__})
+                raise
+            if RECORD_REFERENCE:
+                self.vals.append(_stored(_sample(v) if sample else v))
+            return v
+        v = self.vals[self.i]
+        self.i += 1
+        if isinstance(v, dict) and "__raised__" in v:
+            import builtins
+            raise getattr(builtins, v["__raised__"])(f"{v['__raised__']} raised by the reference (recorded)")
+        return v
