@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 8
+#define MUST3R_HIP_ABI_VERSION 9
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -231,6 +231,55 @@ int must3r_hip_weighted_spoc(const float* feat, const float* attn, int n_images,
  * out[i] in [0, 2*divider^2). */
 int must3r_hip_nn_query(const float* db_xyz, int64_t n_db, const float* q_xyz, int64_t n_q, float* out_dist, void* stream);
 int must3r_hip_quadrant_ids(const float* pts_xyz, int64_t n, const float* cam_center_host3, int divider, int32_t* out, void* stream);
+
+/* ---- ABI 9: image ingestion -- the reference's three image loaders in front of the forwards ----
+ * must3r/demo/inference.py:63-76 load_images: ImgNorm (ToTensor, Normalize(0.5, 0.5)), then get_resize_function
+ *   (must3r/tools/image.py:55-97): torchvision CenterCrop + Resize on the fp32 tensor (torchvision >= 0.17: antialiased bilinear)
+ *   -> MUST3R_RESAMPLE_AA_BILINEAR = F.interpolate(x[None], size, mode="bilinear", align_corners=False, antialias=True): a triangle
+ *   filter of support max(in/out, 1), weights normalised per output pixel, width pass first, fp32 intermediate.
+ * must3r/slam/model.py:99-120 preproc_frame (and dust3r's load_images behind must3r/retrieval/model.py:12,49): dust3r _resize_pil_image
+ *   (PIL LANCZOS when shrinking, BICUBIC otherwise) on the uint8 frame, an integer crop, then ImgNorm
+ *   -> MUST3R_RESAMPLE_PIL_LANCZOS / _BICUBIC: bit-exact with Pillow's Image.resize on RGB uint8: coefficients in double, fixed point
+ *   with 22 fractional bits, int32 sums from 1 << 21, clip8 after each pass, horizontal pass over the rows the vertical pass reads.
+ * get_resize_function(..., is_mask=True) -> MUST3R_RESAMPLE_NEAREST_EXACT = F.interpolate(mode="nearest-exact").
+ * An axis whose size does not change is copied exactly (the replaced libraries skip that pass). */
+enum { MUST3R_RESAMPLE_AA_BILINEAR = 0, MUST3R_RESAMPLE_PIL_LANCZOS = 1, MUST3R_RESAMPLE_PIL_BICUBIC = 2, MUST3R_RESAMPLE_NEAREST_EXACT = 3 };
+/* source layouts: interleaved uint8 rows (RGB from PIL / a decoder; each byte u enters as the fp32 value (u / 255 - 0.5) / 0.5 of a
+ * 256-entry table built on the host), or fp32 planes used as they are (AA_BILINEAR / NEAREST_EXACT only) */
+enum { MUST3R_IMG_U8_HWC = 0, MUST3R_IMG_F32_CHW = 1 };
+
+/* Host only (no GPU needed), the coefficients one axis of a call uses: in_size source pixels -> out_size.  *ksize = taps per output
+ * (the stride of `weights`); with bounds and weights NULL only *ksize is written.  bounds int32 [out_size][2] = (first source pixel,
+ * taps); weights [out_size][ksize]: int32 fixed point (<< 22) for the PIL modes, fp32 otherwise; unused taps are 0. */
+int must3r_hip_resample_coeffs(int mode, int in_size, int out_size, int* ksize, int32_t* bounds, void* weights);
+
+/* One image of a resample call.  The source region [crop_y, +crop_h) x [crop_x, +crop_w) is resampled to resize_h x resize_w, and
+ * the window [out_y, +out_h) x [out_x, +out_w) of that is written as fp32 planes [channels][out_h][out_w] at out + out_offset.
+ * load_images: crop = torchvision's centre crop, resize = the bucket, window = all of it.  preproc_frame: crop = the whole frame,
+ * resize = _resize_pil_image's size, window = preproc_frame's crop box. */
+typedef struct must3r_hip_image_desc {
+    const void* src;          /* DEVICE pointer to pixel (0, 0) of the source (not of the crop) */
+    int32_t src_format;       /* MUST3R_IMG_* */
+    int32_t channels;         /* 1 ... 4 (3 for RGB) */
+    int32_t H, W;             /* source size */
+    int64_t row_stride;       /* between source rows: bytes (U8_HWC, >= W * channels) or elements (F32_CHW, >= W) */
+    int64_t plane_stride;     /* F32_CHW: elements between channel planes */
+    int32_t crop_y, crop_x, crop_h, crop_w;
+    int32_t resize_h, resize_w;
+    int32_t out_y, out_x, out_h, out_w;
+    int64_t out_offset;       /* elements */
+} must3r_hip_image_desc;
+
+/* device bytes of scratch a must3r_hip_resample call with these descriptors needs (0 on invalid descriptors): the host-built tables
+ * (normalisation table, per-image descriptors, coefficients) and the intermediate of the two passes */
+size_t must3r_hip_image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n_images);
+/* Resamples n_images images (any mix of sizes) with one upload of the tables and ONE launch per pass.  `out` fp32 on the device;
+ * `scratch` >= must3r_hip_image_scratch_bytes device bytes, 256-byte aligned; `stream` belongs to the current device.  The descriptor array
+ * is read on the host during the call; the tables travel through pinned host slots of the calling thread (a ring of 4, grown on demand,
+ * reused once their copy has completed), so the call does not wait for earlier work on the stream; coefficients of recently seen
+ * (in, out) sizes are cached per thread.  The sources, `out` and `scratch` must stay valid until the work queued on `stream` has run. */
+int must3r_hip_resample(int mode, const must3r_hip_image_desc* descs, int n_images, float* out, void* scratch, size_t scratch_bytes,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Operator-level entry points (the same kernels the two forwards are built from), exported so that parity

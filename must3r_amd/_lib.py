@@ -15,8 +15,10 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 8
+ABI_VERSION = 9
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
+RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
+IMG_U8_HWC, IMG_F32_CHW = 0, 1
 
 # every symbol include/must3r_hip.h declares
 EXPORTS = (
@@ -32,6 +34,7 @@ EXPORTS = (
     "must3r_hip_postprocess_act", "must3r_hip_postprocess_cam_act",
     "must3r_hip_op_sparse24_pack", "must3r_hip_op_gemm_sp",
     "must3r_hip_set_option", "must3r_hip_cp_slot_bytes", "must3r_hip_cp_slot_bytes16", "must3r_hip_op_gemm_fold256", "must3r_hip_has_fp8_attention",
+    "must3r_hip_resample_coeffs", "must3r_hip_image_scratch_bytes", "must3r_hip_resample",
 )
 
 
@@ -64,6 +67,15 @@ class DecodeArgs(C.Structure):
                 ("mem", C.POINTER(C.c_void_p)), ("feats", C.c_void_p),
                 ("mem_capacity", C.c_int32), ("n_scenes", C.c_int32), ("mem_scene_stride", C.c_int64),
                 ("cp", C.POINTER(Cp)), ("causal", C.c_int32)]
+
+
+class ImageDesc(C.Structure):
+    """must3r_hip_image_desc: one image of a must3r_hip_resample call (include/must3r_hip.h, ABI 9)."""
+    _fields_ = [("src", C.c_void_p), ("src_format", C.c_int32), ("channels", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("row_stride", C.c_int64), ("plane_stride", C.c_int64),
+                ("crop_y", C.c_int32), ("crop_x", C.c_int32), ("crop_h", C.c_int32), ("crop_w", C.c_int32),
+                ("resize_h", C.c_int32), ("resize_w", C.c_int32),
+                ("out_y", C.c_int32), ("out_x", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("out_offset", C.c_int64)]
 
 
 class ProfRecord(C.Structure):
@@ -132,6 +144,10 @@ def load():
     lib.must3r_hip_cp_slot_bytes.restype = C.c_size_t
     lib.must3r_hip_cp_slot_bytes16.argtypes = [vp, i32]
     lib.must3r_hip_cp_slot_bytes16.restype = C.c_size_t
+    lib.must3r_hip_resample_coeffs.argtypes = [i32, i32, i32, C.POINTER(C.c_int), vp, vp]
+    lib.must3r_hip_image_scratch_bytes.argtypes = [i32, C.POINTER(ImageDesc), i32]
+    lib.must3r_hip_image_scratch_bytes.restype = C.c_size_t
+    lib.must3r_hip_resample.argtypes = [i32, C.POINTER(ImageDesc), i32, vp, vp, C.c_size_t, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("must3r_hip_abi_version", "must3r_hip_attention_scratch_bytes",

@@ -225,6 +225,16 @@ int launch_weighted_spoc(const float* feat, const float* attn, int Bn, int N, in
 // SLAM keyframe test (slam/nns.py, slam/tools.py:9-31): exact 1-NN distances by brute force, view-direction quadrants; nn.hip
 int launch_nn_query(const float* db, long long n_db, const float* q, long long n_q, float* out_dist, hipStream_t s, const char** err);
 int launch_quadrant_ids(const float* pts, long long n, const float* cam_center_host, int div, int* out, hipStream_t s, const char** err);
+
+// image ingestion (demo/inference.py:63-76 load_images, slam/model.py:99-120 preproc_frame): host coefficient builder, scratch plan and the
+// two-pass batched resampler; image.hip
+}  // namespace m3r
+struct must3r_hip_image_desc;
+namespace m3r {
+int image_coeffs(int mode, int in, int out, int* ksize, int32_t* bounds, void* weights, const char** err);
+size_t image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n);
+int launch_resample(int mode, const must3r_hip_image_desc* descs, int n, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
+                    const char** err);
 // postprocess(compute_cam=True): activation + focal (Weiszfeld) + weighted rigid registration, cam.hip
 size_t cam_scratch_bytes(int n_views, int H, int W);
 int launch_postprocess_cam(const float* pm, int linear, int n_views, int H, int W, float* pts3d, float* pts3d_local, float* conf,

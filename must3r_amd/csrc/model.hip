@@ -1525,6 +1525,26 @@ extern "C" int must3r_hip_quadrant_ids(const float* pts, int64_t n, const float*
     return 0;
 }
 
+extern "C" int must3r_hip_resample_coeffs(int mode, int in_size, int out_size, int* ksize, int32_t* bounds, void* weights) {
+    const char* err = nullptr;
+    if (image_coeffs(mode, in_size, out_size, ksize, bounds, weights, &err)) return fail("%s", err);
+    return 0;
+}
+
+extern "C" size_t must3r_hip_image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n_images) {
+    return image_scratch_bytes(mode, descs, n_images);
+}
+
+extern "C" int must3r_hip_resample(int mode, const must3r_hip_image_desc* descs, int n_images, float* out, void* scratch, size_t scratch_bytes,
+                                   void* stream) {
+    if (n_images < 0) return fail("resample: negative image count");
+    if (n_images == 0) return 0;
+    if (!descs || !out) return fail("resample: null argument");
+    const char* err = nullptr;
+    if (launch_resample(mode, descs, n_images, out, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
 extern "C" size_t must3r_hip_postprocess_cam_scratch_bytes(int n_views, int H, int W) {
     if (n_views <= 0 || H <= 0 || W <= 0) return 0;
     return cam_scratch_bytes(n_views, H, W);
