@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 9
+#define MUST3R_HIP_ABI_VERSION 10
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -341,6 +341,37 @@ int must3r_hip_op_attention(int dtype, const void* Q, const void* K, const void*
                             int ldq, int ldk, int ldv, int ldo, int heads,
                             const int32_t* views_dev, int n_views, int max_nq,
                             int nsplit, void* scratch, int total_q_rows, void* stream);
+/* ABI 10.  The attention routes the decoder launches, reachable one by one (tests): every field of the launch the decoder sets, and the context-parallel
+ * stages.  Forwards to the same launchers as must3r_hip_decode; nothing here changes what must3r_hip_op_attention does.
+ *   stage 0: the plain launch -- (m, l) pre-fill (split-KV without dense_rows only), main kernel, combine (split-KV only) -> O
+ *   stage 1: one rank's partial -- pre-fill (as stage 0), main kernel, merge of the nsplit (>= 2) local splits into slot_o / slot_ml (p16: O / l in the 16-bit type)
+ *   stage 2: the partial of a rank without keys: O = 0, (m, l) = (-inf, 0) for total_q_rows rows -> slot_o / slot_ml
+ *   stage 3: the final merge of nslots partials at slot_o + s * stride_o (elements of the partial's O type) / slot_ml + s * stride_ml (floats) -> O
+ * Layouts of a partial: O [total_q_rows][heads * 64] (fp32, or the 16-bit type with p16), (m, l) [total_q_rows][heads][2] fp32.
+ * A query row whose view has no valid key (nk = 0, or every key excluded) gets O = 0 on every route.  With split-KV, dense_rows = 1 promises that every row
+ * below total_q_rows belongs to a view of the launch (no pre-fill); without it, rows outside every view are left untouched.  `picked` (optional) receives
+ * the main kernel stages 0 and 1 ran ("attn3/q16", "attn3/q32"); stages 2 and 3 leave it alone. */
+typedef struct must3r_hip_attn_op {
+    int32_t dtype;                     /* MUST3R_BF16 / MUST3R_F16 */
+    const void* Q; const void* K; const void* V; void* O;
+    int32_t ldq, ldk, ldv, ldo;        /* row strides in elements */
+    int32_t heads;
+    const int32_t* views_dev;          /* DEVICE int32 [n_views][6] as must3r_hip_op_attention */
+    int32_t n_views;
+    int32_t view0_inline;              /* 1: n_views must be 1 and the view is `view0` (views_dev is not read) */
+    int32_t view0[6];
+    int32_t max_nq, max_nk;            /* max over views of nq / nk (max_nk 0: unknown) */
+    int32_t q_prescaled;               /* 1: Q carries 1/8 * log2(e) already (the decoder's projections fold it in); 0: the kernel scales */
+    int32_t nsplit;                    /* <= 1: single pass */
+    void* scratch;                     /* must3r_hip_attention_scratch_bytes(nsplit, total_q_rows, heads) bytes when nsplit > 1 */
+    int32_t total_q_rows, dense_rows;
+    int32_t stage;                     /* 0 .. 3 above */
+    void* slot_o; float* slot_ml;      /* stage 1 / 2: the output partial; stage 3: slot 0 */
+    int32_t p16, nslots;
+    int64_t stride_o, stride_ml;       /* stage 3 */
+    const char** picked;
+} must3r_hip_attn_op;
+int must3r_hip_op_attention_ex(const must3r_hip_attn_op* d, void* stream);
 
 /* y = LN(x (+ add)) * w + b over rows of C; optional outputs may be NULL */
 int must3r_hip_op_layernorm(int dtype, const float* x, const float* add, const float* w, const float* b,

@@ -15,7 +15,7 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 9
+ABI_VERSION = 10
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
@@ -35,6 +35,7 @@ EXPORTS = (
     "must3r_hip_op_sparse24_pack", "must3r_hip_op_gemm_sp",
     "must3r_hip_set_option", "must3r_hip_cp_slot_bytes", "must3r_hip_cp_slot_bytes16", "must3r_hip_op_gemm_fold256", "must3r_hip_has_fp8_attention",
     "must3r_hip_resample_coeffs", "must3r_hip_image_scratch_bytes", "must3r_hip_resample",
+    "must3r_hip_op_attention_ex",
 )
 
 
@@ -78,6 +79,17 @@ class ImageDesc(C.Structure):
                 ("out_y", C.c_int32), ("out_x", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("out_offset", C.c_int64)]
 
 
+class AttnOp(C.Structure):
+    """must3r_hip_attn_op: one attention route of the decoder, or one context-parallel stage (include/must3r_hip.h, ABI 10)."""
+    _fields_ = [("dtype", C.c_int32), ("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p),
+                ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32), ("heads", C.c_int32),
+                ("views_dev", C.c_void_p), ("n_views", C.c_int32), ("view0_inline", C.c_int32), ("view0", C.c_int32 * 6),
+                ("max_nq", C.c_int32), ("max_nk", C.c_int32), ("q_prescaled", C.c_int32),
+                ("nsplit", C.c_int32), ("scratch", C.c_void_p), ("total_q_rows", C.c_int32), ("dense_rows", C.c_int32),
+                ("stage", C.c_int32), ("slot_o", C.c_void_p), ("slot_ml", C.c_void_p), ("p16", C.c_int32), ("nslots", C.c_int32),
+                ("stride_o", C.c_int64), ("stride_ml", C.c_int64), ("picked", C.POINTER(C.c_char_p))]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -115,6 +127,7 @@ def load():
                                        vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.must3r_hip_rope_table.argtypes = [fp, fp, i32, vp]
     lib.must3r_hip_op_attention.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp]
+    lib.must3r_hip_op_attention_ex.argtypes = [C.POINTER(AttnOp), vp]
     lib.must3r_hip_attention_scratch_bytes.argtypes = [i32, i32, i32]
     lib.must3r_hip_attention_scratch_bytes.restype = C.c_size_t
     lib.must3r_hip_op_layernorm.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, fp, vp]

@@ -1097,11 +1097,17 @@ __global__ void attn_combine_kernel(const AttnArgs p, const int nsplit, float* _
 #pragma unroll
             for (int c = 0; c < CH; ++c) mstar = fmaxf(mstar, mv[c]);
         }
-        if (mstar == -INFINITY) {   // row not produced by any view of this launch (a partial: the row of a rank without keys)
+        if (mstar == -INFINITY) {   // no split holds a valid key of this row
+            // A row of a view without any valid key gets O = 0, as on the single-pass route (l = 0).  Rows no view of the launch produced keep
+            // their contents: they exist only without dense_rows, and attn_ml_init_kernel marks them with l = -1 (a kernel block writes l >= 0).
+            bool produced = p.dense_rows != 0;
+            for (int sc = 0; sc < nsplit && !produced; ++sc) produced = ml0[(size_t)sc * ml_stride + 1] >= 0.f;
             if constexpr (TO_PARTIAL) {
                 if (cp16) *reinterpret_cast<v4*>(reinterpret_cast<T*>(cp_o) + row * D + col) = cvt4<T>(f32x4{0.f, 0.f, 0.f, 0.f});
                 else *reinterpret_cast<f32x4*>(cp_o + row * D + col) = f32x4{0.f, 0.f, 0.f, 0.f};
-                if ((col & 63) == 0) { cp_ml[(row * p.heads + head) * 2] = -INFINITY; cp_ml[(row * p.heads + head) * 2 + 1] = 0.f; }
+                if ((col & 63) == 0) { cp_ml[(row * p.heads + head) * 2] = -INFINITY; cp_ml[(row * p.heads + head) * 2 + 1] = produced ? 0.f : -1.f; }
+            } else if (produced) {
+                *reinterpret_cast<v4*>(reinterpret_cast<T*>(p.O) + row * p.ldo + col) = cvt4<T>(f32x4{0.f, 0.f, 0.f, 0.f});
             }
             continue;
         }
@@ -1139,11 +1145,11 @@ __global__ void attn_combine_kernel(const AttnArgs p, const int nsplit, float* _
     }
 }
 
-// fills (m, l) = (-inf, 0) so rows no block writes are recognisable by the combine pass
+// fills (m, l) = (-inf, -1) so rows no block writes are recognisable by the combine pass (a block writes l >= 0, also for a row without a valid key)
 __global__ void attn_ml_init_kernel(float* ml, size_t n2) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) {
         ml[i * 2] = -INFINITY;
-        ml[i * 2 + 1] = 0.f;
+        ml[i * 2 + 1] = -1.f;
     }
 }
 

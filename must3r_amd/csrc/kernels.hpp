@@ -170,7 +170,9 @@ int launch_attention(DType dt, const AttnArgs& a, hipStream_t s, const char** er
 // launches too small to fill the chip with 128-query blocks run the 16-row-per-wave 16 x 16 kernel (16-bit operands only): the model
 // does not quantise Q / K for those
 bool attention_is_small(int nviews, int heads, int max_nq, int nsplit);
-// the three launches of a split-KV attention, separately (profiling): (m,l) pre-fill, main kernel, combine
+// the three launches of a split-KV attention, separately (profiling): (m,l) pre-fill, main kernel, combine.  A query row whose view has no valid key
+// (nk = 0 or every key excluded) gets O = 0 on every route: single pass (l = 0), combine and final merge (dense_rows, or a row a kernel block wrote:
+// the pre-fill leaves l = -1 in the rows no view produces, and those keep their contents)
 int launch_attention_phase(DType dt, const AttnArgs& a, int phase, hipStream_t s, const char** err);
 const char* attention_last_kernel();   // main kernel of the calling thread's last phase-1 launch
 

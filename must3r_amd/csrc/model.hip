@@ -1658,6 +1658,52 @@ extern "C" int must3r_hip_op_attention(int dtype, const void* Q, const void* K, 
     return 0;
 }
 
+// ABI 10 (tests): the launches of decode() one by one -- stage 0 = static attention(), stages 1 / 2 / 3 = the context-parallel local partial / empty partial / final merge
+extern "C" int must3r_hip_op_attention_ex(const must3r_hip_attn_op* d, void* stream) {
+    if (!d) return fail("op_attention_ex: null descriptor");
+    if (d->dtype != MUST3R_BF16 && d->dtype != MUST3R_F16) return fail("op_attention_ex: bad dtype");
+    if (d->stage < 0 || d->stage > 3) return fail("op_attention_ex: stage must be 0 .. 3");
+    if (d->view0_inline && d->n_views != 1) return fail("op_attention_ex: view0_inline needs n_views = 1");
+    const DType dt = (DType)d->dtype;
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Q = d->Q; a.K = d->K; a.V = d->V; a.O = d->O;
+    a.ldq = d->ldq; a.ldk = d->ldk; a.ldv = d->ldv; a.ldo = d->ldo; a.heads = d->heads;
+    a.views = reinterpret_cast<const AttnView*>(d->views_dev); a.nviews = d->n_views;
+    if (d->view0_inline) {
+        a.view0_inline = 1;
+        a.view0 = AttnView{d->view0[0], d->view0[1], d->view0[2], d->view0[3], d->view0[4], d->view0[5]};
+    }
+    a.max_nq = d->max_nq; a.max_nk = d->max_nk; a.scale = 0.125f; a.q_prescaled = d->q_prescaled ? 1 : 0;
+    a.total_q_rows = d->total_q_rows; a.dense_rows = d->dense_rows ? 1 : 0;
+    if (d->nsplit > 1) {
+        if (!d->scratch || d->total_q_rows <= 0) return fail("op_attention_ex: split-KV needs scratch and total_q_rows");
+        a.nsplit = d->nsplit;
+        a.part_o = reinterpret_cast<float*>(d->scratch);
+        a.part_ml = a.part_o + (size_t)d->nsplit * d->total_q_rows * d->heads * 64;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const char* err = "";
+    switch (d->stage) {
+    case 0:
+        if (launch_attention(dt, a, s, &err)) return fail("%s", err);
+        break;
+    case 1:
+        if (d->nsplit < 2) return fail("op_attention_ex: a local partial needs nsplit >= 2");
+        if (launch_attention_phase(dt, a, 0, s, &err) || launch_attention_phase(dt, a, 1, s, &err) ||
+            launch_attention_partial_merge(dt, a, reinterpret_cast<float*>(d->slot_o), d->slot_ml, d->p16, s, &err)) return fail("%s", err);
+        break;
+    case 2:
+        if (launch_attention_partial_empty(reinterpret_cast<float*>(d->slot_o), d->slot_ml, d->total_q_rows, d->heads, d->p16, s, &err)) return fail("%s", err);
+        break;
+    default:
+        if (launch_attention_partial_final(dt, a, reinterpret_cast<const float*>(d->slot_o), d->slot_ml, d->stride_o, d->stride_ml, d->nslots, d->p16, s, &err))
+            return fail("%s", err);
+    }
+    if (d->picked && d->stage < 2) *d->picked = attention_last_kernel();
+    return 0;
+}
+
 extern "C" int must3r_hip_op_layernorm(int dtype, const float* x, const float* add, const float* w, const float* b, void* out16,
                                        void* out16_lo, float* out32, float* copy32, int M, int C, float eps, void* stream) {
     if (dtype != MUST3R_BF16 && dtype != MUST3R_F16) return fail("op_layernorm: bad dtype");

@@ -1,7 +1,8 @@
 // Validated A/B switches of libmust3r_hip.  ONE table: name, default, allowed range.  A switch takes its value from
 // must3r_hip_set_option (include/must3r_hip.h, ABI 8) or, at first use, from the environment variable M3R_<NAME>; a value outside the range is
 // refused (set_option: status 1 + error string; environment: one line on stderr, the default is used).  The switches are measuring instruments:
-// every one keeps the results inside the precision mode's tolerance, and all but SPARSE_LO / LNFOLD / LNFOLD256 keep them bit-identical.
+// every one keeps the results inside the precision mode's tolerance, and all but SPARSE_LO / LNFOLD / LNFOLD256 / ATTN_LZ keep them bit-identical (ATTN_LZ = 0:
+// P = 2^(s - m) is rounded against other references m).
 #pragma once
 
 namespace m3r {
