@@ -1,22 +1,27 @@
 #!/usr/bin/env python
 """Headline benchmark: views/sec for MUSt3R_512 (ViT-L encoder / ViT-B memory decoder), 20-view 512x384 scenes.
 
-    python bench.py --gpus 1 --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, runs W warm-up steps and K timed steps, writes the last step's outputs if --dump-outputs is given, and prints
+the headline line.  Everything else -- the per-kernel roofline pass, the stage split, the one-scene-at-a-time leg, the other step
+size, the other precisions, the other configurations, the CPU and eager-PyTorch baselines with the parity against the CPU oracle --
+is measured after the timed steps of a ``--full`` run only (the ``--no-*`` options and ``--step-only`` narrow what it adds).
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM: S (``--scenes``, default 28; 20 in r03-r04)
 independent scenes of 20 views per rank -- every scene: encode 20, memory update with the demo schedule [2,1,...,1] (20-view
 memory), render 20 against its final memory, fp32 activation (BASELINE.json configs[2]).  The S scenes
 are IN FLIGHT TOGETHER: they ride the batch dimension of the reference's decoder API (decoder.py:170-186), one native call per
 schedule step, so the strictly sequential memory update runs its GEMMs on S x 768 rows instead of 768.
-  N = 1 : ``value`` = S x 20 views per step / time.  ``single_scene`` carries the S = 1 numbers (one scene at a time: the
+  N = 1 : ``value`` = S x 20 views per step / time.  ``single_scene`` (--full) carries the S = 1 numbers (one scene at a time: the
           figure of rounds 1-2) with its stage split and kernel classes.
   N > 1 : REPLICAS -- every rank runs its own S scenes (the metric's whole-node definition, SURVEY.md section 8e: independent
           scenes shard with no data-path collective); barrier + max over ranks around the timed region.  The view-SHARDED
           forms of one scene (RCCL all-gather of the encoded keyframe tokens over xGMI, replicated sequential update:
-          must3r_amd/parallel.py) are timed in the same run and reported under ``configs``.
-Prints ONE JSON line on rank 0.  ``configs`` carries the other BASELINE.json configurations measured in the same run (never
-part of ``value``):
+          must3r_amd/parallel.py) are timed in the same --full run and reported under ``configs``.
+Prints ONE JSON line on rank 0.  With ``--full``, ``configs`` carries the other BASELINE.json configurations measured in the same
+run (never part of ``value``):
   configs[1]  MUSt3R_224 10-view 224x224 scene
   configs[3]  200-frame online streaming memory (N = 1: one GPU; N > 1: frames sharded, all-gather, replicated update)
   configs[4]  mixed-resolution scene 512 x {384,336,288,256,160} x 4 views through forward_list, 16-bit and fp8 (MX) attention
@@ -137,16 +142,21 @@ def main():
     ap.add_argument("--precision", default="fp16wa", choices=["bf16", "fp16", "fp16w2", "fp16wa"],
                     help="MFMA operand mode; fp16wa (fp16, split weights except in the Mlp Linears) and fp16w2 (all weights split) meet the "
                          "1e-3 parity target")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-views", type=int, default=20, help="views of the scene the CPU oracle runs (20 = the metric's own workload)")
-    ap.add_argument("--no-alt", action="store_true")
-    ap.add_argument("--no-single", action="store_true", help="skip the one-scene-at-a-time leg (the PMC passes use this)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the extra BASELINE.json configurations")
-    ap.add_argument("--step-only", action="store_true", help="the S-scene step and nothing else (no single-scene leg, other configurations, other "
-                    "precisions, cam timing or CPU baseline): every launch of the process belongs to the step, so a rocprofv3 --kernel-trace of "
-                    "this command has per-symbol averages that equal the line's (scripts/gpu_profile_r04.sh)")
-    ap.add_argument("--stream-frames", type=int, default=200)
-    ap.add_argument("--cpu-timeout", type=float, default=420.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and report everything beside the headline as well: per-kernel classes and roofline (one "
+                         "extra, untimed step), stage split, one scene at a time, the other step size, the other precisions, the other "
+                         "BASELINE.json configurations, postprocess timing, the CPU oracle and eager-PyTorch baselines and the parity "
+                         "against the CPU oracle.  The options below narrow what it adds; a run without --full does none of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU / eager-PyTorch baselines and the parity")
+    ap.add_argument("--cpu-views", type=int, default=20, help="with --full: views of the scene the CPU oracle runs (20 = the metric's own workload)")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the other precisions and the other step size")
+    ap.add_argument("--no-single", action="store_true", help="with --full: skip the one-scene-at-a-time leg")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the extra BASELINE.json configurations")
+    ap.add_argument("--step-only", action="store_true", help="with --full: the S-scene step and its per-kernel figures and nothing else (no "
+                    "single-scene leg, other configurations, other precisions, cam timing or CPU baseline): every launch of the process belongs to "
+                    "the step, so a rocprofv3 --kernel-trace of this command has per-symbol averages that equal the line's (scripts/gpu_profile_r06.sh)")
+    ap.add_argument("--stream-frames", type=int, default=200, help="with --full: frames of the streaming configuration")
+    ap.add_argument("--cpu-timeout", type=float, default=420.0, help="with --full: seconds the CPU oracle may take")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, or float64 for integer "
                          "outputs): every array a caller of run_scenes / run_scene receives, each reduced to a fixed, seeded sample of at most "
@@ -227,6 +237,35 @@ def main():
     del last_out
     views_per_step = Sn * V * world
     value = views_per_step * args.steps / dt
+    flops = Sn * world * scene_flops(N, V, V)
+    line = {
+        "metric": "views/sec (whole node) MUSt3R_512 20-view 512x384; pointmap max-abs-err vs ref",
+        "value": round(value, 2), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "value_definition": f"{Sn} independent 20-view scenes in flight per GPU ({views_per_step} views per step) / step time; value_single_scene: one scene at a time",
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": dtype_label, "data": "synthetic",
+        "config": {"workload": f"MUSt3R_512 {V}-view 384x512 scenes, S={Sn} independent scenes IN FLIGHT per GPU ({views_per_step} views/step); one at a time: value_single_scene",
+                   "value_definition": f"{Sn} independent {V}-view scenes in flight per GPU / step time (every scene: encode {V} + update [2,1,..,1] + render {V} + activation)",
+                   "model": "MUSt3R_512 ViT-L encoder / ViT-B memory decoder, random init, feedback single_mlp, memory_mode kv",
+                   "views_per_step": views_per_step, "scenes_in_flight_per_gpu": Sn, "views_per_scene": V, "keyframes_per_scene": V,
+                   "H": H, "W": W, "ms_per_scene": round(dt / args.steps / Sn * 1e3, 3),
+                   "parallelism": "single GPU" if world == 1 else f"{world} replicas (independent scenes per rank, no data-path collective; "
+                                                                   f"barrier + max over ranks) [{backend}]"},
+        "scene_tflop": round(scene_flops(N, V, V) / 1e12, 2),
+        "end_to_end_mfma_frac": round(flops * args.steps / dt / 1e12 / PEAK_TFLOPS[args.precision], 4),
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
+    # ---- --full: everything below runs after the timed steps and adds to `line`, never to `value`
 
     def profile_classes(fn):
         """per-kernel-class timing with HIP events on the launch stream (one extra, untimed pass of fn)"""
@@ -703,7 +742,6 @@ def main():
                 cpu_baseline = {"value": None, "error": repr(e)[:300], "kind": "port"}
 
     if rank == 0:
-        flops = Sn * world * scene_flops(N, V, V)
         # second half of BASELINE.json's metric ("...; pointmap max-abs-err vs ref"), inside `config` so that the driver's record keeps it: the BENCHED step's own
         # scene 0 (all views, all pixels) against the fp32 CPU oracle of the same scene, which this run pinned on the real-reference fixture (cpu_baseline)
         pkey = "step_scene0_of_" + str(Sn)
@@ -720,28 +758,15 @@ def main():
                                 " from the real reference's outputs (tests/golden/must3r512_v20.npz); the same scene against the real-reference fixtures, all pixels of "
                                 "the worst views included, is asserted in tests/test_zz_r04_gpu.py",
                           "normalisation": "per view: ||d_v||inf / ||ref_v||inf over all pixels and channels of the raw [H, W, 7] head output"}
+        # like for like with BENCH_r03 / r04: the same step with 20 scenes in flight, measured in this run (null when --no-alt / N > 1 skipped it)
         s20 = next((r["value"] for r in (sweep or []) if r.get("scenes_in_flight") == 20), round(value, 2) if Sn == 20 else None)
-        line = {
-            "metric": "views/sec (whole node) MUSt3R_512 20-view 512x384; pointmap max-abs-err vs ref",
-            "value": round(value, 2), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            # BASELINE.md section 2 (r04 wording): `value` = whole-GPU throughput with S independent scenes in flight; `value_single_scene` = the same
-            # scene ONE AT A TIME (V / wall-time(scene): the definition rounds 1-2 reported as `value` -- r01 243, r02 285, r03 322)
-            "value_single_scene": (single or {}).get("value") if Sn > 1 else round(value, 2),
-            "value_definition": f"{Sn} independent 20-view scenes in flight per GPU ({views_per_step} views per step) / step time; value_single_scene: one scene at a time",
-            # like for like with BENCH_r03 / r04: the same step with 20 scenes in flight, measured in this run (null when --no-alt / N > 1 skipped it)
-            "value_r04_definition": s20,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": dtype_label, "data": "synthetic",
-            "config": {"workload": f"MUSt3R_512 {V}-view 384x512 scenes, S={Sn} independent scenes IN FLIGHT per GPU ({views_per_step} views/step); one at a time: value_single_scene",
-                       # (the driver's record keeps `config`: the definition of `value` and the like-for-like batch-1 figure travel here as well as at the top level)
-                       "value_definition": f"{Sn} independent {V}-view scenes in flight per GPU / step time (every scene: encode {V} + update [2,1,..,1] + render {V} + activation)",
-                       "value_single_scene": (single or {}).get("value") if Sn > 1 else round(value, 2),
-                       "model": "MUSt3R_512 ViT-L encoder / ViT-B memory decoder, random init, feedback single_mlp, memory_mode kv",
-                       "views_per_step": views_per_step, "scenes_in_flight_per_gpu": Sn, "views_per_scene": V, "keyframes_per_scene": V,
-                       "H": H, "W": W, "ms_per_scene": round(dt / args.steps / Sn * 1e3, 3),
-                       "parity": parity_cfg, "value_r04_definition": s20,
-                       "parallelism": "single GPU" if world == 1 else f"{world} replicas (independent scenes per rank, no data-path collective; "
-                                                                       f"barrier + max over ranks) [{backend}]"},
+        # BASELINE.md section 2 (r04 wording): `value` = whole-GPU throughput with S independent scenes in flight; `value_single_scene` = the same
+        # scene ONE AT A TIME (V / wall-time(scene): the definition rounds 1-2 reported as `value` -- r01 243, r02 285, r03 322)
+        v1 = (single or {}).get("value") if Sn > 1 else round(value, 2)
+        # (the driver's record keeps `config`: the definition of `value` and the like-for-like batch-1 figure travel here as well as at the top level)
+        line["config"].update({"value_single_scene": v1, "parity": parity_cfg, "value_r04_definition": s20})
+        line.update({
+            "value_single_scene": v1, "value_r04_definition": s20,
             "roofline": roofline, "roofline_attention": roofline_attention, "roofline_gemm": roofline_gemm, "cpu_baseline": cpu_baseline, "torch_rocm_baseline": torch_rocm_baseline,
             "parity_vs_cpu_oracle": parity,
             "kernel_classes": classes, "stages_ms": stages, "single_scene": single, "alt": alt, "scenes_in_flight_sweep": sweep, "configs": configs, "postprocess_cam": cam,
@@ -749,12 +774,8 @@ def main():
             "multi_gpu": ("this line is a 1-GPU run; no RCCL run of the N > 1 paths has happened in the build environment (one GPU per box): the "
                           "view-sharded path is covered by world-size-2 gloo tests and a 2-rank gloo dry run of this script" if world == 1 else
                           f"{world} ranks, backend {backend}"),
-            "scene_tflop": round(scene_flops(N, V, V) / 1e12, 2),
-            "end_to_end_mfma_frac": round(flops * args.steps / dt / 1e12 / PEAK_TFLOPS[args.precision], 4),
-        }
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+        })
+    finish()
 
 
 if __name__ == "__main__":

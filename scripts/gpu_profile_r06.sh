@@ -1,6 +1,6 @@
 #!/bin/bash
 # r06 closing evidence (r06: the same passes at the r06 closing commit): everything the bench line's roofline numbers can be recomputed from, taken at ONE commit.
-#   1. rocprofv3 --kernel-trace --stats of `bench.py --step-only` (the S-scene step and nothing else: per-symbol averages = the line's)
+#   1. rocprofv3 --kernel-trace --stats of `bench.py --full --step-only` (the S-scene step and its per-kernel figures: per-symbol averages = the line's)
 #   2. separate --pmc passes of the SAME command (kernel-trace only; --steps 1 --warmup 1):
 #        L2 -> fabric read requests by size | write requests by size | TCC_HIT_sum TCC_MISS_sum | SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVES GRBM_GUI_ACTIVE
 #   S (scenes in flight) for the PMC passes: $M3R_PMC_SCENES (default 28 = the benched step, r06: counters restricted to the GEMM and attention symbols with
@@ -17,7 +17,7 @@ S_PMC=${M3R_PMC_SCENES:-28}
 mkdir -p $O
 rm -rf $O/prof_step
 echo "== kernel trace of the step (S=$S_STEP)"
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_step -o step -- python bench.py --gpus 1 --steps 3 --warmup 1 --scenes $S_STEP --step-only > $O/r06_step_line.json 2> $O/r06_step.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_step -o step -- python bench.py --gpus 1 --steps 3 --warmup 1 --scenes $S_STEP --full --step-only > $O/r06_step_line.json 2> $O/r06_step.err
 echo "rc=$?"; tail -c 300 $O/r06_step_line.json | head -c 300; echo
 python scripts/prof_summary.py $(ls $O/prof_step/*.db $O/prof_step/*/*.db 2>/dev/null | tail -1) $O/r06_step_kernel_stats.txt | head -14
 find $O/prof_step -name "*.db" -size +20M -delete; find $O/prof_step -name "*.csv" -size +8M -delete
@@ -26,7 +26,7 @@ pmc_pass() {   # $1 = tag, rest = counters
   rm -rf $O/pmc_$TAG
   echo "== pmc $TAG: $* (S=$S_PMC)"
   timeout 420 rocprofv3 --kernel-trace --kernel-include-regex "gemm|attn" --pmc "$@" --output-format csv -d $O/pmc_$TAG -o run -- \
-      python bench.py --gpus 1 --steps 1 --warmup 1 --scenes $S_PMC --step-only > $O/pmc_$TAG.log 2>&1
+      python bench.py --gpus 1 --steps 1 --warmup 1 --scenes $S_PMC --full --step-only > $O/pmc_$TAG.log 2>&1
   echo "rc=$?"
   python - "$TAG" "$S_PMC" "$@" <<'PY'
 import sys, glob, json, csv, re, collections

@@ -11,7 +11,7 @@ from util import load_golden, rel_inf
 
 # must3r224_v10 = BASELINE.json configs[1] at full depth (10 views, [2,1,...,1]); the 20-view 384x512 fixture
 # (must3r512_v20, configs[2]) costs ~90 s of CPU per pass: the oracle is pinned on it by bench.py's cpu_baseline leg
-# (oracle/cpu_baseline.py --check-fixture) on every bench run instead of here.
+# (oracle/cpu_baseline.py --check-fixture) on every `bench.py --full` run instead of here.
 CASES = {"tiny_48x64_v4": TINY, "small_224_v3": SMALL, "must3r224_v2": MUST3R_224, "must3r224_v10": MUST3R_224}
 
 
