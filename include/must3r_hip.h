@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 10
+#define MUST3R_HIP_ABI_VERSION 11
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -223,6 +223,37 @@ int must3r_hip_layernorm_act_f32(const float* x, const float* gamma, const float
 int must3r_hip_topk_gather(const float* feat, const float* attn, int n_images, int N, int C, int k, float* out_feat,
                            float* out_attn, int64_t* out_idx, void* stream);
 int must3r_hip_weighted_spoc(const float* feat, const float* attn, int n_images, int N, int C, float* out, void* stream);
+
+/* ---- ABI 11: ASMK back-end of the retrieval mode (demo/inference.py:31-60 MUSt3R_Retriever.__call__; retrieval/processor.py:83-96:
+ * binary kernel, use_idf False, multiple_assignment 1 for build_ivf and 5 for query_ivf, similarity_threshold 0, alpha 3, topk None).
+ * The same images are database and query; the local features are forward_local's rows, image i owning rows [off_i, off_{i+1}).
+ * Deterministic: no atomics, every output has one writer and a fixed order of operations.
+ * must3r_hip_asmk_centroid_sqnorm: out[K] = |c|^2 of a codebook [K,D] fp32, once per codebook.
+ * must3r_hip_asmk_quantize: ids int32 [M,k] = the k nearest centroids of each feature row (squared L2, ranked by |c|^2 - 2 x.c on the
+ *   fp32 MFMA), ascending; an exact tie goes to the lower centroid id; a NaN distance (non-finite input) ranks as +inf, so every id is in [0, K).  One k = 5 search serves both sides: its first column is the
+ *   database assignment.  Needs D % 64 == 0, 1 <= k <= 8, k <= K, 16-byte aligned feat / centroids, and `scratch` of
+ *   must3r_hip_asmk_quantize_scratch_bytes(M, K, k) device bytes.
+ * must3r_hip_asmk_aggregate: per image and side (k_use = 1: database, 5: query, of the k_ids columns of `ids`): W = the ascending distinct
+ *   words of its assignments; for w in W, r_w = sum of (x_j - c_w) over the rows j assigned to w, in ascending j, in fp32, each difference
+ *   rounded and then added ((des[mask] - centroid).sum(0) on float32 arrays); bit d of w = r_w[d] > 0.  offsets_dev: DEVICE int32
+ *   [n_images + 1]; image i writes |W| words (int32) at slot off_i * k_use of `words` [M * k_use] and its bits (uint32 [D / 32] per
+ *   word, bit d % 32 of word d / 32) at the same slot of `bits`, and counts[i] = |W|.  max_rows: the largest off_{i+1} - off_i; an image
+ *   with more than 4096 (word, row) pairs (rows * k_use) is refused (counts[i] = -1 if the promise is broken), and so is an image with
+ *   an id outside [0, K) of the codebook [K, D] (counts[i] = -1; no centroid row is read for it).
+ * must3r_hip_asmk_scores: out float64 [n_q, n_d] (row = query, column = database: the reference's `scores` after its un-ranking,
+ *   demo/inference.py:57-58): for w in W_q and W_d, ascending: h = popcount(bits_q xor bits_d), s = 1 - 2h/D, sigma = s^alpha if
+ *   s >= threshold else 0 (fp32); score = sum sigma in float64, then with `normalize` / sqrt(|W_d|) / sqrt(|W_q|) (0 for an empty side).
+ *   PARITY UNPINNED upstream: the 1/sqrt(|W|) normalisation and the tie order. */
+int must3r_hip_asmk_centroid_sqnorm(const float* centroids, int K, int D, float* out, void* stream);
+size_t must3r_hip_asmk_quantize_scratch_bytes(int M, int K, int k);
+int must3r_hip_asmk_quantize(const float* feat, int M, const float* centroids, const float* c_sqnorm, int K, int D, int k, int32_t* ids,
+                             void* scratch, size_t scratch_bytes, void* stream);
+int must3r_hip_asmk_aggregate(const float* feat, const float* centroids, int K, int D, const int32_t* ids, int k_ids, int k_use,
+                              const int32_t* offsets_dev, int n_images, int max_rows, int32_t* words, uint32_t* bits, int32_t* counts,
+                              void* stream);
+int must3r_hip_asmk_scores(const int32_t* words_q, const uint32_t* bits_q, const int32_t* counts_q, const int32_t* offsets_q, int k_q, int n_q,
+                           const int32_t* words_d, const uint32_t* bits_d, const int32_t* counts_d, const int32_t* offsets_d, int k_d, int n_d,
+                           int D, float alpha, float threshold, int normalize, double* out, void* stream);
 
 /* SLAM keyframe test, SURVEY.md section 8f rank 3 (slam/model.py:62-91 get_overlap_score; slam/nns.py:40-92).
  * must3r_hip_nn_query replaces KDTree_scipy.query (nns.py:52-57: scipy KDTree.query(k=1), Euclidean): out_dist[i] =

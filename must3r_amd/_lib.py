@@ -15,7 +15,7 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 10
+ABI_VERSION = 11
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
@@ -36,6 +36,8 @@ EXPORTS = (
     "must3r_hip_set_option", "must3r_hip_cp_slot_bytes", "must3r_hip_cp_slot_bytes16", "must3r_hip_op_gemm_fold256", "must3r_hip_has_fp8_attention",
     "must3r_hip_resample_coeffs", "must3r_hip_image_scratch_bytes", "must3r_hip_resample",
     "must3r_hip_op_attention_ex",
+    "must3r_hip_asmk_centroid_sqnorm", "must3r_hip_asmk_quantize_scratch_bytes", "must3r_hip_asmk_quantize", "must3r_hip_asmk_aggregate",
+    "must3r_hip_asmk_scores",
 )
 
 
@@ -161,6 +163,12 @@ def load():
     lib.must3r_hip_image_scratch_bytes.argtypes = [i32, C.POINTER(ImageDesc), i32]
     lib.must3r_hip_image_scratch_bytes.restype = C.c_size_t
     lib.must3r_hip_resample.argtypes = [i32, C.POINTER(ImageDesc), i32, vp, vp, C.c_size_t, vp]
+    lib.must3r_hip_asmk_centroid_sqnorm.argtypes = [vp, i32, i32, vp, vp]
+    lib.must3r_hip_asmk_quantize_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.must3r_hip_asmk_quantize_scratch_bytes.restype = C.c_size_t
+    lib.must3r_hip_asmk_quantize.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, vp, C.c_size_t, vp]
+    lib.must3r_hip_asmk_aggregate.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    lib.must3r_hip_asmk_scores.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, fp, fp, i32, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("must3r_hip_abi_version", "must3r_hip_attention_scratch_bytes",

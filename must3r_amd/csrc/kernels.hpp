@@ -224,6 +224,17 @@ int launch_ln_act_f32(const float* x, const float* gamma, const float* beta, flo
 int launch_topk_gather(const float* feat, const float* attn, int Bn, int N, int C, int k, float* out_feat, float* out_attn,
                        long long* out_idx, hipStream_t s, const char** err);
 int launch_weighted_spoc(const float* feat, const float* attn, int Bn, int N, int C, float* out, hipStream_t s, const char** err);
+// ASMK back-end of the retrieval mode (demo/inference.py:31-60, retrieval/processor.py:83-96): centroid norms, top-k quantizer on the
+// fp32 MFMA, per-image residual aggregation with sign bits, binary-kernel scores; asmk.hip
+int launch_asmk_sqnorm(const float* C, int K, int D, float* out, hipStream_t s, const char** err);
+size_t asmk_quantize_scratch_bytes(int M, int K, int k);
+int launch_asmk_quantize(const float* X, int M, const float* C, const float* csq, int K, int D, int k, int* ids, void* scratch,
+                         size_t scratch_bytes, hipStream_t s, const char** err);
+int launch_asmk_aggregate(const float* X, const float* C, int K, int D, const int* ids, int k_ids, int k_use, const int* offsets, int n_images,
+                          int max_rows, int* words, unsigned* bits, int* counts, hipStream_t s, const char** err);
+int launch_asmk_scores(const int* wq, const unsigned* bq, const int* cq, const int* oq, int kq, int n_q, const int* wd, const unsigned* bd,
+                       const int* cd, const int* od, int kd, int n_d, int D, float alpha, float tau, int normalize, double* out,
+                       hipStream_t s, const char** err);
 // SLAM keyframe test (slam/nns.py, slam/tools.py:9-31): exact 1-NN distances by brute force, view-direction quadrants; nn.hip
 int launch_nn_query(const float* db, long long n_db, const float* q, long long n_q, float* out_dist, hipStream_t s, const char** err);
 int launch_quadrant_ids(const float* pts, long long n, const float* cam_center_host, int div, int* out, hipStream_t s, const char** err);

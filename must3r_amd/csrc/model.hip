@@ -1507,6 +1507,53 @@ extern "C" int must3r_hip_weighted_spoc(const float* feat, const float* attn, in
     return 0;
 }
 
+extern "C" int must3r_hip_asmk_centroid_sqnorm(const float* centroids, int K, int D, float* out, void* stream) {
+    if (K < 0 || D <= 0) return fail("asmk_centroid_sqnorm: bad shape");
+    if (K == 0) return 0;
+    if (!centroids || !out) return fail("asmk_centroid_sqnorm: null argument");
+    const char* err = nullptr;
+    if (launch_asmk_sqnorm(centroids, K, D, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
+extern "C" size_t must3r_hip_asmk_quantize_scratch_bytes(int M, int K, int k) { return asmk_quantize_scratch_bytes(M, K, k); }
+
+extern "C" int must3r_hip_asmk_quantize(const float* feat, int M, const float* centroids, const float* c_sqnorm, int K, int D, int k, int32_t* ids,
+                                        void* scratch, size_t scratch_bytes, void* stream) {
+    if (M < 0 || K <= 0 || D <= 0) return fail("asmk_quantize: bad shape");
+    if (M == 0) return 0;
+    if (!feat || !centroids || !c_sqnorm || !ids) return fail("asmk_quantize: null argument");
+    const char* err = nullptr;
+    if (launch_asmk_quantize(feat, M, centroids, c_sqnorm, K, D, k, ids, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), &err))
+        return fail("%s", err);
+    return 0;
+}
+
+extern "C" int must3r_hip_asmk_aggregate(const float* feat, const float* centroids, int K, int D, const int32_t* ids, int k_ids, int k_use,
+                                         const int32_t* offsets_dev, int n_images, int max_rows, int32_t* words, uint32_t* bits, int32_t* counts,
+                                         void* stream) {
+    if (n_images < 0 || K <= 0 || D <= 0) return fail("asmk_aggregate: bad shape");
+    if (n_images == 0) return 0;
+    if (!feat || !centroids || !ids || !offsets_dev || !words || !bits || !counts) return fail("asmk_aggregate: null argument");
+    const char* err = nullptr;
+    if (launch_asmk_aggregate(feat, centroids, K, D, ids, k_ids, k_use, offsets_dev, n_images, max_rows, words, bits, counts,
+                              reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
+extern "C" int must3r_hip_asmk_scores(const int32_t* words_q, const uint32_t* bits_q, const int32_t* counts_q, const int32_t* offsets_q, int k_q,
+                                      int n_q, const int32_t* words_d, const uint32_t* bits_d, const int32_t* counts_d, const int32_t* offsets_d,
+                                      int k_d, int n_d, int D, float alpha, float threshold, int normalize, double* out, void* stream) {
+    if (n_q < 0 || n_d < 0 || D <= 0 || k_q < 1 || k_d < 1) return fail("asmk_scores: bad shape");
+    if (n_q == 0 || n_d == 0) return 0;
+    if (!words_q || !bits_q || !counts_q || !offsets_q || !words_d || !bits_d || !counts_d || !offsets_d || !out)
+        return fail("asmk_scores: null argument");
+    const char* err = nullptr;
+    if (launch_asmk_scores(words_q, bits_q, counts_q, offsets_q, k_q, n_q, words_d, bits_d, counts_d, offsets_d, k_d, n_d, D, alpha, threshold,
+                           normalize, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
 extern "C" int must3r_hip_nn_query(const float* db, int64_t n_db, const float* q, int64_t n_q, float* out, void* stream) {
     if (n_db < 0 || n_q < 0) return fail("nn_query: negative count");
     if (n_q == 0) return 0;

@@ -7,9 +7,16 @@ reference retrieval checkpoint works unchanged; ``forward_local`` / ``forward_gl
 PCA projection (``must3r_hip_affine``, fp64 MFMA; ``Whitener(l2norm=dim)`` -> ``must3r_hip_l2_normalize``), the projector Linears (fp32
 MFMA, exact products; hidden layers of a multi-layer projector: ``must3r_hip_layernorm_act_f32``), token attention
 (``must3r_hip_row_norm``), top-k selection + gather (``must3r_hip_topk_gather``) or weighted sum pooling
-(``must3r_hip_weighted_spoc``).  No CPU fallback.  Learning the whitening (``pcawhitenlearn_shrinkage``) and the ASMK
-codebook stay on the host as in the reference (out of scope: SURVEY.md section 8f rank 4 is the front-end only).
+(``must3r_hip_weighted_spoc``).  No CPU fallback.
+
+``Retriever`` / ``MUSt3R_Retriever`` (processor.py:62-96, demo/inference.py:31-60) add the back-end: the checkpoint's front-end, the
+ASMK codebook next to it and ``must3r_amd.asmk.ASMK`` (quantize, aggregate and score on the GPU, ABI 11), so the encoder tokens
+become the reference's N x N score matrix without leaving the device.  Learning the whitening (``pcawhitenlearn_shrinkage``) and
+training the codebook (k-means) stay out of scope, as in the reference's inference path.
 """
+import os
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -202,3 +209,64 @@ class RetrievalModel(nn.Module):
 
     def forward(self, x):
         return self.forward_global(x)
+
+
+def codebook_path(modelname):
+    """processor.py:83-86: ``<dir>/<checkpoint name without its last _part>_codebook.pkl``."""
+    dname, bname = os.path.split(modelname)
+    return os.path.join(dname, "_".join(bname.split("_")[:-1]) + "_codebook.pkl")
+
+
+class Retriever:
+    """processor.py:62-96 (construction): the retrieval front-end of a checkpoint and its ASMK codebook, on ``device``."""
+
+    def __init__(self, modelname, backbone, device="cuda", verbose=True):
+        from .asmk import ASMK, load_codebook
+        if not os.path.isfile(modelname):
+            raise FileNotFoundError(modelname)
+        if backbone is None:
+            raise ValueError("Retriever needs the encoder (backbone) the checkpoint was trained on")
+        if verbose:
+            print(f"Loading retrieval model from {modelname}")
+        ckpt = torch.load(modelname, "cpu", weights_only=False)
+        a = ckpt["args"]
+        self.model = RetrievalModel(backbone, freeze_backbone=a.freeze_backbone, prewhiten=a.prewhiten,
+                                    hdims=list(map(int, a.hdims.split("_"))) if len(a.hdims) > 0 else "",
+                                    residual=getattr(a, "residual", False), postwhiten=a.postwhiten, featweights=a.featweights,
+                                    nfeat=a.nfeat).to(device)
+        self.device = device
+        msg = self.model.load_state_dict(ckpt["model"], strict=False)
+        if not all(k.startswith("backbone") for k in msg.missing_keys) or len(msg.unexpected_keys) != 0:
+            raise RuntimeError(f"{modelname}: missing {msg.missing_keys}, unexpected {msg.unexpected_keys}")
+        self.imsize = a.imsize
+        cb = codebook_path(modelname)
+        if not os.path.isfile(cb):
+            raise FileNotFoundError(f"ASMK codebook not found next to the checkpoint: {cb}")
+        self.asmk = ASMK(load_codebook(cb, nclusters=getattr(a, "nclusters", None), device=device), alpha=3.0, similarity_threshold=0.0)
+
+
+class MUSt3R_Retriever(Retriever):
+    """demo/inference.py:31-60: encoder tokens of the images -> float64 numpy [n, n] scores (row = query, column = database)."""
+
+    @torch.no_grad()
+    def local_features(self, enc, device):
+        """forward_local of every image's tokens ``enc[i]`` [1, N_i, C], images with equal token counts in one call -> (feat [M, C]
+        on the device, offsets [n + 1]) with image i on rows [offsets[i], offsets[i+1])."""
+        groups = {}
+        for i, e in enumerate(enc):
+            groups.setdefault(tuple(e.shape[1:]), []).append(i)
+        per_image = [None] * len(enc)
+        for idx in groups.values():
+            x = torch.cat([enc[i].to(device) for i in idx], dim=0)
+            feat, _, _ = self.model.forward_local(x)
+            for j, i in enumerate(idx):
+                per_image[i] = feat[j]
+        offsets = np.zeros((len(enc) + 1,), dtype=np.int64)
+        offsets[1:] = np.cumsum([f.shape[0] for f in per_image])
+        dim = self.asmk.codebook.shape[1]
+        feat = torch.cat(per_image, dim=0) if per_image else torch.empty((0, dim), device=device)
+        return feat.contiguous(), offsets
+
+    def __call__(self, enc, device):
+        feat, offsets = self.local_features(enc, device)
+        return self.asmk.scores_numpy(feat, offsets)
