@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 11
+#define MUST3R_HIP_ABI_VERSION 12
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -262,6 +262,25 @@ int must3r_hip_asmk_scores(const int32_t* words_q, const uint32_t* bits_q, const
  * out[i] in [0, 2*divider^2). */
 int must3r_hip_nn_query(const float* db_xyz, int64_t n_db, const float* q_xyz, int64_t n_q, float* out_dist, void* stream);
 int must3r_hip_quadrant_ids(const float* pts_xyz, int64_t n, const float* cam_center_host3, int divider, int32_t* out, void* stream);
+
+/* ---- ABI 12: exact 1-NN index over the keyframe map (replaces the full scan of must3r_hip_nn_query for a map queried many times) ----
+ * Build once per change of the point set, query any number of times; everything runs on `stream` into caller-owned device buffers.
+ * divider = 0: one segment over all points (KDTree_scipy, nns.py:40-57); divider d in [1, 8]: 2 d^2 quadrant segments
+ * (QuandrantSearcher, nns.py:60-92), a point's quadrant being quadrant_ids[i] (must3r_hip_quadrant_ids of its add batch's cam centre).
+ * must3r_hip_nn_index_build: xyz fp32 [n][3] and quadrant_ids int32 [n] (read only when divider > 0) on the device, n <= 2^30;
+ *   index: must3r_hip_nn_index_bytes(n, divider) bytes, scratch: must3r_hip_nn_index_scratch_bytes(n) bytes (free after the build).
+ *   Non-finite points are dropped.  Two builds of the same input give byte-identical index buffers (no order decided by atomics).
+ *   Leaves hold 2^NN_LEAF_LOG2 points (must3r_hip_set_option, default 5).
+ * must3r_hip_nn_index_query: out_dist[i] = the distance must3r_hip_nn_query gives for q_i over the points of q_i's quadrant (the ray
+ *   q_i - cam_center_host3, as must3r_hip_quadrant_ids; cam_center_host3 is not read when divider = 0), bit for bit; +inf for an
+ *   empty quadrant and for a non-finite query.  divider must be the build's: the index records it, and a query with another divider
+ *   writes NaN to every out_dist[i].  No scratch: out_dist holds the query quadrant ids first.  A query is walked by 2^NN_QUERY_LANES_LOG2
+ *   lanes together (must3r_hip_set_option, default 3; the distances do not depend on it). */
+size_t must3r_hip_nn_index_bytes(int64_t n, int divider);
+size_t must3r_hip_nn_index_scratch_bytes(int64_t n);
+int must3r_hip_nn_index_build(const float* xyz, const int32_t* quadrant_ids, int64_t n, int divider, void* index, void* scratch, void* stream);
+int must3r_hip_nn_index_query(const void* index, const float* q_xyz, int64_t n_q, const float* cam_center_host3, int divider, float* out_dist,
+                              void* stream);
 
 /* ---- ABI 9: image ingestion -- the reference's three image loaders in front of the forwards ----
  * must3r/demo/inference.py:63-76 load_images: ImgNorm (ToTensor, Normalize(0.5, 0.5)), then get_resize_function

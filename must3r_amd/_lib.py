@@ -15,7 +15,7 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 11
+ABI_VERSION = 12
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
@@ -38,6 +38,7 @@ EXPORTS = (
     "must3r_hip_op_attention_ex",
     "must3r_hip_asmk_centroid_sqnorm", "must3r_hip_asmk_quantize_scratch_bytes", "must3r_hip_asmk_quantize", "must3r_hip_asmk_aggregate",
     "must3r_hip_asmk_scores",
+    "must3r_hip_nn_index_bytes", "must3r_hip_nn_index_scratch_bytes", "must3r_hip_nn_index_build", "must3r_hip_nn_index_query",
 )
 
 
@@ -151,6 +152,12 @@ def load():
     lib.must3r_hip_weighted_spoc.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.must3r_hip_nn_query.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
     lib.must3r_hip_quadrant_ids.argtypes = [vp, C.c_int64, C.POINTER(C.c_float), i32, vp, vp]
+    lib.must3r_hip_nn_index_bytes.argtypes = [C.c_int64, i32]
+    lib.must3r_hip_nn_index_bytes.restype = C.c_size_t
+    lib.must3r_hip_nn_index_scratch_bytes.argtypes = [C.c_int64]
+    lib.must3r_hip_nn_index_scratch_bytes.restype = C.c_size_t
+    lib.must3r_hip_nn_index_build.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp]
+    lib.must3r_hip_nn_index_query.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_float), i32, vp, vp]
     lib.must3r_hip_postprocess_cam_scratch_bytes.argtypes = [i32, i32, i32]
     lib.must3r_hip_postprocess_cam_scratch_bytes.restype = C.c_size_t
     lib.must3r_hip_get_profile.argtypes = [vp, C.POINTER(ProfRecord), i32, i32]

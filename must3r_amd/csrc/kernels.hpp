@@ -238,6 +238,13 @@ int launch_asmk_scores(const int* wq, const unsigned* bq, const int* cq, const i
 // SLAM keyframe test (slam/nns.py, slam/tools.py:9-31): exact 1-NN distances by brute force, view-direction quadrants; nn.hip
 int launch_nn_query(const float* db, long long n_db, const float* q, long long n_q, float* out_dist, hipStream_t s, const char** err);
 int launch_quadrant_ids(const float* pts, long long n, const float* cam_center_host, int div, int* out, hipStream_t s, const char** err);
+// exact 1-NN index over the same points (radix-sorted Morton order per quadrant, heap of fp32 boxes, stackless query); nn_index.hip
+size_t nn_index_bytes(long long n, int divider);
+size_t nn_index_scratch_bytes(long long n);
+int launch_nn_index_build(const float* xyz, const int* qid, long long n, int divider, void* index, void* scratch, hipStream_t s,
+                          const char** err);
+int launch_nn_index_query(const void* index, const float* q, long long n_q, const float* cam_center_host, int divider, float* out_dist,
+                          hipStream_t s, const char** err);
 
 // image ingestion (demo/inference.py:63-76 load_images, slam/model.py:99-120 preproc_frame): host coefficient builder, scratch plan and the
 // two-pass batched resampler; image.hip

@@ -1572,6 +1572,29 @@ extern "C" int must3r_hip_quadrant_ids(const float* pts, int64_t n, const float*
     return 0;
 }
 
+extern "C" size_t must3r_hip_nn_index_bytes(int64_t n, int divider) { return nn_index_bytes(n, divider); }
+extern "C" size_t must3r_hip_nn_index_scratch_bytes(int64_t n) { return nn_index_scratch_bytes(n); }
+
+extern "C" int must3r_hip_nn_index_build(const float* xyz, const int32_t* quadrant_ids, int64_t n, int divider, void* index, void* scratch,
+                                         void* stream) {
+    if (n < 0) return fail("nn_index_build: negative count");
+    if (!index || (n > 0 && (!xyz || !scratch))) return fail("nn_index_build: null argument");
+    const char* err = nullptr;
+    if (launch_nn_index_build(xyz, quadrant_ids, n, divider, index, scratch, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
+extern "C" int must3r_hip_nn_index_query(const void* index, const float* q_xyz, int64_t n_q, const float* cam_center_host3, int divider,
+                                         float* out_dist, void* stream) {
+    if (n_q < 0) return fail("nn_index_query: negative count");
+    if (n_q == 0) return 0;
+    if (!index || !q_xyz || !out_dist || (divider > 0 && !cam_center_host3)) return fail("nn_index_query: null argument");
+    const char* err = nullptr;
+    if (launch_nn_index_query(index, q_xyz, n_q, cam_center_host3, divider, out_dist, reinterpret_cast<hipStream_t>(stream), &err))
+        return fail("%s", err);
+    return 0;
+}
+
 extern "C" int must3r_hip_resample_coeffs(int mode, int in_size, int out_size, int* ksize, int32_t* bounds, void* weights) {
     const char* err = nullptr;
     if (image_coeffs(mode, in_size, out_size, ksize, bounds, weights, &err)) return fail("%s", err);

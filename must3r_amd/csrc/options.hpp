@@ -25,6 +25,8 @@ enum Opt {
                            //      Measured (profiles/r06_lnfold256_ab.txt, S = 28, interleaved runs on one box): LayerNorm 68.5 -> 13.2 ms per step, GEMMs 534 -> 582 ms
                            //      (producers + 2 B per element of HBM-bound epilogue, consumers + 32 KB of statistics per tile in front of the first DMA): 559 vs 557 views/s
     OPT_G256_GM,           // r06: row-blocks per group of the tile walk of gemm256p / gemm256s (which tiles an XCD's 32 CUs hold together: GM rows x 32 / GM columns)
+    OPT_NN_LEAF_LOG2,      // log2 of the points per leaf of the 1-NN index (nn_index.hip), read at each build: 4 / 5 / 6 = 16 / 32 / 64 points
+    OPT_NN_QUERY_LANES_LOG2, // log2 of the lanes that walk one query of the 1-NN index together (nn_index.hip): 0 .. 4 = 1 .. 16 lanes
     OPT_COUNT
 };
 

@@ -1,11 +1,16 @@
-"""Offline reconstruction of a photo collection: ``must3r_inference`` of must3r/demo/inference.py:109-242 on the native path.
+"""Offline reconstruction of a photo collection or a video on the native path: must3r/demo/inference.py and the execution-mode
+dispatch of demo/gradio.py:160-217 (``get_reconstruction.py --execution_mode linseq|retrieval|vidseq|vidslam``).
 
-The reference reaches it from ``get_reconstruction.py --execution_mode retrieval|linseq`` and from demo/gradio.py:198-201.  Images
-are read by ``must3r_amd.image.load_images``, encoded by ``inference.encoder_multi_ar``, ranked by ``retrieval.MUSt3R_Retriever``
-(front-end + ASMK on the GPU), ordered by ``select_keyframes`` and reconstructed by ``inference.inference_multi_ar`` with
-``engine.postprocess(compute_cam=True)``.  The video modes (``must3r_inference_video``) are not here.
+``must3r_inference`` (demo/inference.py:109-242): images are read by ``must3r_amd.image.load_images``, encoded by
+``inference.encoder_multi_ar``, ranked by ``retrieval.MUSt3R_Retriever`` (front-end + ASMK on the GPU), ordered by
+``select_keyframes`` and reconstructed by ``inference.inference_multi_ar`` with ``engine.postprocess(compute_cam=True)``.
+``must3r_inference_video`` (:244-331): every frame in turn through ``inference.inference_video_multi_ar``; the keyframe test is a
+callback, ``id % keyframe_interval == 0`` (vidseq) or ``slam_is_keyframe`` (vidslam: the overlap score of the frame against the
+map of keyframe points, ``slam_nn.get_searcher("bvh-hip-quadrant_x2")``, which ``slam_update_scene_state`` grows).
+GLB / PLY export (``get_3D_model_from_scene``) is not here.
 """
 import datetime
+import functools
 
 import numpy as np
 import torch
@@ -13,9 +18,10 @@ import torch
 from .engine import postprocess
 from .graph import farthest_point_sampling
 from .image import load_images
-from .inference import encoder_multi_ar, inference_multi_ar
+from .inference import encoder_multi_ar, inference_multi_ar, inference_video_multi_ar
 from .model import get_dtype, get_pointmaps_activation
 from .retrieval import MUSt3R_Retriever
+from .slam_nn import choose_keyframe_from_overlap, get_overlap_score, get_searcher
 
 
 class SceneState:
@@ -152,3 +158,131 @@ def must3r_inference(model, retrieval, device, image_size, amp, filelist, num_me
             x_out[i][k] = x_out[i][k].cpu()
     rgbimg = [rgb(imgs[i], true_shape[i]) for i in range(nimgs)]
     return SceneState(x_out, rgbimg, true_shape, focals, cams2world, filenames)
+
+
+def slam_is_keyframe(subsample, min_conf_keyframe, keyframe_overlap_thr, overlap_percentile, overlap_mode, id, res, scene_state):
+    """demo/inference.py:79-93: a frame is a keyframe when its overlap score against the map is above the threshold ('nn' modes)."""
+    cam_center = res["c2w"][:3, -1]
+    res_unsqueeze = {k: v.unsqueeze(0).unsqueeze(0) for k, v in res.items()}
+    overlap_score = get_overlap_score(res_unsqueeze, scene_state, cam_center=cam_center, mode=overlap_mode, kf_x_subsamp=subsample,
+                                      min_conf_keyframe=min_conf_keyframe, percentile=overlap_percentile)
+    assert not np.isnan(overlap_score)
+    return choose_keyframe_from_overlap(overlap_score, keyframe_overlap_thr, overlap_mode)
+
+
+def slam_update_scene_state(subsample, min_conf_keyframe, res, scene_state):
+    """demo/inference.py:95-106: a keyframe's confident points (every ``subsample``-th row and column) join the map."""
+    cam_center = res["c2w"][:3, -1]
+    msk = res["conf"] > min_conf_keyframe
+    if subsample:
+        msk = msk[::subsample, ::subsample]
+        pts = res["pts3d"][::subsample, ::subsample][msk]
+    else:
+        pts = res["pts3d"][msk]
+    scene_state.add_pts(pts, cam_center=cam_center)
+    return scene_state
+
+
+def must3r_inference_video(model, device, image_size, amp, filelist, max_bs, init_num_images, batch_num_views, viser_server=None,
+                           num_refinements_iterations=0, local_context_size: int = 25,
+                           is_keyframe_function=lambda id, res, scene_state: (id % 3 == 0), scene_state=None,
+                           scene_state_update_function=lambda res, scene_state: scene_state, verbose=True):
+    """demo/inference.py:244-331 -> ``SceneState``: the frames in file order, ``init_num_images`` of them first, then
+    ``batch_num_views`` at a time, through ``inference_video_multi_ar`` with the keyframe and map callbacks."""
+    dtype = get_dtype(amp)
+    amp_on = dtype != torch.float32
+    max_bs = None if max_bs == 0 else max_bs
+    encoder, decoder = model
+    pointmaps_activation = get_pointmaps_activation(decoder, verbose=verbose)
+
+    def post_process_function(x):
+        return postprocess(x, pointmaps_activation=pointmaps_activation, compute_cam=True)
+
+    if verbose:
+        print("loading images")
+    time_start = datetime.datetime.now()
+    views = load_images(filelist, size=image_size, patch_size=encoder.patch_size, verbose=verbose, device=device)
+    if verbose:
+        print(f"loaded in {datetime.datetime.now() - time_start}")
+        print("running inference")
+    time_start = datetime.datetime.now()
+    nimgs = len(views)
+    if viser_server is not None:
+        viser_server.reset(nimgs)
+
+    imgs = [b["img"].to(device) for b in views]
+    true_shape = [torch.from_numpy(b["true_shape"]).to(device) for b in views]
+    filenames = filelist
+
+    mem_batches = [min(init_num_images, nimgs)]
+    while (sum_b := sum(mem_batches)) != nimgs:
+        mem_batches.append(min(batch_num_views, nimgs - sum_b))
+
+    with torch.autocast("cuda", dtype=dtype, enabled=amp_on):
+        x_out = inference_video_multi_ar(encoder, decoder, imgs, true_shape, mem_batches, max_bs=max_bs, verbose=verbose, device=device,
+                                         preserve_gpu_mem=True, post_process_function=post_process_function, viser_server=viser_server,
+                                         num_refinements_iterations=num_refinements_iterations, local_context_size=local_context_size,
+                                         is_keyframe_function=is_keyframe_function, scene_state=scene_state,
+                                         scene_state_update_function=scene_state_update_function)
+    if verbose:
+        print(f"inference in {datetime.datetime.now() - time_start}")
+    if viser_server is not None:
+        viser_server.reset_cam_visility()
+        viser_server.send_message("Finished")
+
+    focals = [float(x_out[i]["focal"].cpu()) for i in range(nimgs)]
+    cams2world = [x_out[i]["c2w"].cpu() for i in range(nimgs)]
+    for i in range(len(x_out)):
+        for k in x_out[i].keys():
+            x_out[i][k] = x_out[i][k].cpu()
+    rgbimg = [rgb(imgs[i], true_shape[i]) for i in range(nimgs)]
+    return SceneState(x_out, rgbimg, true_shape, focals, cams2world, filenames)
+
+
+@torch.no_grad()
+def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrieval, device, verbose, image_size, amp,
+                            filelist, max_bs, num_refinements_iterations,
+                            execution_mode, num_mem_images, render_once, vidseq_local_context_size, keyframe_interval,
+                            slam_local_context_size, subsample, min_conf_keyframe, keyframe_overlap_thr, overlap_percentile,
+                            min_conf_thr, as_pointcloud, transparent_cams, local_pointmaps, cam_size, camera_conf_thr=0.0,
+                            loaded_files=""):
+    """demo/gradio.py:160-217 -> ``(SceneState, None)``: the four execution modes with the reference's arguments.  The output
+    parameters are accepted and unused: GLB / PLY export is out of scope, and ``should_save_glb=True`` is refused."""
+    if should_save_glb:
+        raise NotImplementedError("get_reconstructed_scene: GLB / PLY export (get_3D_model_from_scene) is not part of must3r_amd; "
+                                  "call it with should_save_glb=False and export the returned SceneState yourself")
+    if filelist:
+        image_list = filelist
+    elif loaded_files:
+        image_list = loaded_files.split("\n")
+    else:
+        return None, None
+
+    if execution_mode == "vidseq" or execution_mode == "vidslam":
+        if execution_mode == "vidseq":
+            local_context_size = vidseq_local_context_size
+
+            def is_keyframe_function(id, res, scene_state):
+                return id % keyframe_interval == 0
+            scene_state = None
+
+            def scene_state_update_function(res, scene_state):
+                return scene_state
+        else:
+            local_context_size = slam_local_context_size
+            overlap_mode = "nn-norm"
+            is_keyframe_function = functools.partial(slam_is_keyframe, subsample, min_conf_keyframe, keyframe_overlap_thr,
+                                                     overlap_percentile, overlap_mode)
+            scene_state = get_searcher("bvh-hip-quadrant_x2")
+            scene_state_update_function = functools.partial(slam_update_scene_state, subsample, min_conf_keyframe)
+        scene = must3r_inference_video(model, device, image_size, amp, image_list, max_bs, init_num_images=2, batch_num_views=1,
+                                       viser_server=viser_server, num_refinements_iterations=num_refinements_iterations,
+                                       local_context_size=local_context_size, is_keyframe_function=is_keyframe_function,
+                                       scene_state=scene_state, scene_state_update_function=scene_state_update_function,
+                                       verbose=verbose)
+    else:
+        is_sequence = execution_mode == "linseq"
+        scene = must3r_inference(model, retrieval, device, image_size, amp, image_list, num_mem_images, max_bs, init_num_images=2,
+                                 batch_num_views=1, render_once=render_once, is_sequence=is_sequence, viser_server=viser_server,
+                                 num_refinements_iterations=num_refinements_iterations, verbose=verbose)
+    return scene, None

@@ -4,7 +4,9 @@ Same class / function names and call signatures as the reference (``get_searcher
 ``QuandrantSearcher`` [sic], ``get_overlap_score``), torch CUDA tensors in, numpy distances / a float score out like the
 reference.  Instead of rebuilding a scipy KD-tree over all keyframe points after every keyframe (nns.py:47-50) and
 querying it on 4 host threads (nns.py:56), the points stay in HBM and a query is an exact brute-force scan
-(``must3r_hip_nn_query``); quadrant ids (slam/tools.py:9-31) come from ``must3r_hip_quadrant_ids``.
+(``must3r_hip_nn_query``); quadrant ids (slam/tools.py:9-31) come from ``must3r_hip_quadrant_ids``.  ``BVH_hip`` /
+``BVHQuadrant_hip`` (``get_searcher("bvh-hip[-quadrant_xN]")``) give the same distances bit for bit from an index rebuilt on the
+GPU after each change of the map (``must3r_hip_nn_index_*``), so that a query no longer scans the whole map.
 ``forward_must3r`` is the SLAM agent's forward wrapper (slam/model.py:22-59).
 """
 import ctypes as C
@@ -115,8 +117,89 @@ class QuandrantSearcher(Base_NN):
         return self.query_device(pts, cam_center).double().cpu().numpy()
 
 
+class BVH_hip(Base_NN):
+    """Exact 1-NN over a growing map through the GPU index (include/must3r_hip.h ABI 12): the distances of ``BruteForce_hip``
+    (``quadrant_divider`` 0) or of ``QuandrantSearcher`` (``quadrant_divider`` N), bit for bit.  ``add_pts`` appends the points and
+    their quadrant ids (from the batch's ``cam_center``) to a device store that grows by doubling; the next query rebuilds the index
+    once, then answers every query quadrant in one launch.  Host tensors and arrays are copied to the device first: the video
+    driver hands the keyframe callbacks host results (``preserve_gpu_mem``), as the reference's does."""
+
+    def __init__(self, quadrant_divider=0):
+        super().__init__()
+        self.quadrant_divider = int(quadrant_divider)
+        self.all_points = None      # cuda fp32 [capacity, 3]; rows [0, n) valid
+        self.quadrants = None       # cuda int32 [capacity] (quadrant_divider > 0)
+        self.n = 0
+        self.index = None           # cuda uint8, must3r_hip_nn_index_bytes(n, divider)
+        self.dirty = False
+
+    def _device_pts(self, pts):
+        if not isinstance(pts, torch.Tensor):
+            pts = torch.as_tensor(np.asarray(pts, dtype=np.float32))
+        if not pts.is_cuda:
+            pts = pts.to(self.all_points.device if self.all_points is not None else torch.device("cuda", torch.cuda.current_device()))
+        return _check_pts(pts)
+
+    def add_pts(self, pts, cam_center=None, **kw):
+        pts = self._device_pts(pts)
+        need = self.n + pts.shape[0]
+        if self.all_points is None or need > self.all_points.shape[0]:
+            cap = max(need, 2 * (0 if self.all_points is None else self.all_points.shape[0]))
+            grown = torch.empty((cap, 3), dtype=torch.float32, device=pts.device)
+            grown_q = torch.zeros((cap,), dtype=torch.int32, device=pts.device)
+            if self.n:
+                grown[:self.n] = self.all_points[:self.n]
+                grown_q[:self.n] = self.quadrants[:self.n]
+            self.all_points, self.quadrants = grown, grown_q
+        self.all_points[self.n:need] = pts
+        if self.quadrant_divider and need > self.n:
+            self.quadrants[self.n:need] = quadrant_ids(pts, cam_center, self.quadrant_divider)
+        self.n = need
+        self.dirty = True
+
+    def build(self):
+        """(Re)build the index over the current map now (a query does it when the map changed)."""
+        lib = _lib.load()
+        dev = self.all_points.device if self.all_points is not None else torch.device("cuda", torch.cuda.current_device())
+        self.index = torch.empty((lib.must3r_hip_nn_index_bytes(self.n, self.quadrant_divider),), dtype=torch.uint8, device=dev)
+        scratch = torch.empty((max(1, lib.must3r_hip_nn_index_scratch_bytes(self.n)),), dtype=torch.uint8, device=dev)
+        pts, qid = (self.all_points.data_ptr(), self.quadrants.data_ptr()) if self.n else (None, None)   # an empty map: an empty index
+        with torch.cuda.device(dev):
+            _lib.check(lib.must3r_hip_nn_index_build(pts, qid, self.n, self.quadrant_divider, self.index.data_ptr(), scratch.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream))
+        self.dirty = False
+
+    def query_device(self, pts, cam_center=None, **kw):
+        pts = self._device_pts(pts)
+        if self.n == 0:
+            return torch.full((pts.shape[0],), float("inf"), dtype=torch.float32, device=pts.device)
+        if self.dirty:
+            self.build()
+        out = torch.empty((pts.shape[0],), dtype=torch.float32, device=pts.device)
+        cc = None
+        if self.quadrant_divider:
+            cc = (C.c_float * 3)(*[float(v) for v in torch.as_tensor(cam_center).reshape(3).tolist()])
+        with torch.cuda.device(pts.device):
+            _lib.check(_lib.load().must3r_hip_nn_index_query(self.index.data_ptr(), pts.data_ptr(), pts.shape[0], cc, self.quadrant_divider,
+                                                             out.data_ptr(), _stream(pts)))
+        return out
+
+    def query(self, pts, cam_center=None, **kw):
+        return self.query_device(pts, cam_center=cam_center).double().cpu().numpy()
+
+
+class BVHQuadrant_hip(BVH_hip):
+    """The quadrant form of ``BVH_hip`` for a method string 'bvh-hip-quadrant_xN' (``QuandrantSearcher``'s distances, one index)."""
+
+    def __init__(self, method):
+        super().__init__(int(method.split("quadrant_x")[-1].split("-")[0]))
+
+
 def get_searcher(method, isquadrant=False):
-    """nns.py:9-19; the reference's method strings ('kdtree-scipy', 'kdtree-scipy-quadrant_x2', 'none') are accepted."""
+    """nns.py:9-19; the reference's method strings ('kdtree-scipy', 'kdtree-scipy-quadrant_x2', 'none') are accepted, and
+    'bvh-hip' / 'bvh-hip-quadrant_xN' select the GPU index (``BVH_hip`` / ``BVHQuadrant_hip``)."""
+    if method.startswith("bvh-hip"):
+        return BVHQuadrant_hip(method) if "quadrant_x" in method and not isquadrant else BVH_hip()
     if "quadrant_x" in method and not isquadrant:
         return QuandrantSearcher(method)
     if "kdtree-scipy" in method or "bruteforce-hip" in method:
@@ -146,6 +229,13 @@ def get_overlap_score(res, overlap_tree, cam_center, mode="nn", kf_x_subsamp=Non
         dists[np.isposinf(dists)] = np.finfo(dists.dtype).max   # unseen quadrant (slam/model.py:87-88)
         outscore = np.percentile(dists, percentile)
     return outscore
+
+
+def choose_keyframe_from_overlap(overlap_score, thr, overlap_mode):
+    """slam/model.py:123-128."""
+    if "nn" in overlap_mode:
+        return overlap_score > thr
+    return overlap_score < thr
 
 
 @torch.no_grad()
