@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 12
+#define MUST3R_HIP_ABI_VERSION 13
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -281,6 +281,45 @@ size_t must3r_hip_nn_index_scratch_bytes(int64_t n);
 int must3r_hip_nn_index_build(const float* xyz, const int32_t* quadrant_ids, int64_t n, int divider, void* index, void* scratch, void* stream);
 int must3r_hip_nn_index_query(const void* index, const float* q_xyz, int64_t n_q, const float* cam_center_host3, int divider, float* out_dist,
                               void* stream);
+
+/* ---- ABI 13: scene export -- the compaction and the affine map behind get_3D_model_from_scene (demo/gradio.py:75-156) ----
+ * One read of the scene's confidences serves up to MUST3R_EXPORT_MAX_THR thresholds: must3r_hip_export_count counts, per block of
+ * MUST3R_EXPORT_BLOCK pixels and per threshold, the pixels with conf >= thr (NaN never passes; mesh = 1: the quads whose triangles
+ * (a, b, c') resp. (b, c', d) have three passing corners), scans the counts over (view, block) in view-major order on the device and
+ * returns the totals per threshold (points, or faces) in totals_host after one small copy (the call synchronises `stream`).
+ * The scatter calls then write, for threshold index k of that count, directly in file layout and in the reference's order (view by view,
+ * row-major inside a view; compaction inside a block is ordered, nothing is appended through atomics):
+ *   position  float32(((m0 x + m1 y) + m2 z) + m3) per row of the view's 3x4 fp64 matrix M, every operation rounded in fp64, one rounding
+ *             to fp32;  colour  rint(clip(c, 0, 1) * 255) in fp32 as uint8, alpha 255.
+ *   MUST3R_EXPORT_GLB: out_pos float32 [n][3] and out_col uint8 [n][4];  MUST3R_EXPORT_PLY: out_pos holds 16-byte records x y z float32,
+ *   r g b a uint8 (out_col is not read).  minmax (device, 6 floats: min xyz, max xyz of the written positions) is reduced in the same
+ *   pass through per-block partials; +inf / -inf when nothing was written.
+ * must3r_hip_export_vertices: mesh mode, every pixel of every view (not compacted) as GLB planes, vertex index = pixels of the views
+ *   before + r W + c.  must3r_hip_export_scatter_faces: uint32 [n_faces][3]; per view the surviving triangles (a,b,c'), then (c',b,a),
+ *   then (b,c',d), then (d,c',b), each group in quad row-major order (dust3r.viz.pts3d_to_trimesh + cat_meshes).
+ * views_host: host array; conf [H][W], pts [H][W][3], rgb [H][W][3] fp32 on the device, views may differ in size.  The same table,
+ * n_thr and mesh flag are passed to every call of one export; scratch: must3r_hip_export_scratch_bytes (0 with a message on a bad
+ * table), filled by export_count and read by the scatters.  A scene of 2^32 or more pixels is refused. */
+#define MUST3R_EXPORT_MAX_THR 8
+#define MUST3R_EXPORT_BLOCK 1024
+#define MUST3R_EXPORT_GLB 0
+#define MUST3R_EXPORT_PLY 1
+typedef struct must3r_hip_export_view {
+    const float* conf;
+    const float* pts;
+    const float* rgb;
+    int32_t H, W;
+    double M[12];   /* row-major 3x4 */
+} must3r_hip_export_view;
+size_t must3r_hip_export_scratch_bytes(const must3r_hip_export_view* views_host, int n_views, int n_thr, int mesh);
+int must3r_hip_export_count(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int mesh,
+                            void* scratch, size_t scratch_bytes, int64_t* totals_host, void* stream);
+int must3r_hip_export_scatter_points(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int k,
+                                     int layout, const void* scratch, void* out_pos, void* out_col, float* minmax, void* stream);
+int must3r_hip_export_vertices(const must3r_hip_export_view* views_host, int n_views, int n_thr, void* scratch, float* out_pos,
+                               void* out_col, float* minmax, void* stream);
+int must3r_hip_export_scatter_faces(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int k,
+                                    const void* scratch, uint32_t* out_faces, void* stream);
 
 /* ---- ABI 9: image ingestion -- the reference's three image loaders in front of the forwards ----
  * must3r/demo/inference.py:63-76 load_images: ImgNorm (ToTensor, Normalize(0.5, 0.5)), then get_resize_function

@@ -15,8 +15,9 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 12
+ABI_VERSION = 13
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
+EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
 
@@ -39,6 +40,8 @@ EXPORTS = (
     "must3r_hip_asmk_centroid_sqnorm", "must3r_hip_asmk_quantize_scratch_bytes", "must3r_hip_asmk_quantize", "must3r_hip_asmk_aggregate",
     "must3r_hip_asmk_scores",
     "must3r_hip_nn_index_bytes", "must3r_hip_nn_index_scratch_bytes", "must3r_hip_nn_index_build", "must3r_hip_nn_index_query",
+    "must3r_hip_export_scratch_bytes", "must3r_hip_export_count", "must3r_hip_export_scatter_points", "must3r_hip_export_vertices",
+    "must3r_hip_export_scatter_faces",
 )
 
 
@@ -91,6 +94,11 @@ class AttnOp(C.Structure):
                 ("nsplit", C.c_int32), ("scratch", C.c_void_p), ("total_q_rows", C.c_int32), ("dense_rows", C.c_int32),
                 ("stage", C.c_int32), ("slot_o", C.c_void_p), ("slot_ml", C.c_void_p), ("p16", C.c_int32), ("nslots", C.c_int32),
                 ("stride_o", C.c_int64), ("stride_ml", C.c_int64), ("picked", C.POINTER(C.c_char_p))]
+
+
+class ExportView(C.Structure):
+    """must3r_hip_export_view: one view of a scene export (include/must3r_hip.h, ABI 13)."""
+    _fields_ = [("conf", C.c_void_p), ("pts", C.c_void_p), ("rgb", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_double * 12)]
 
 
 class ProfRecord(C.Structure):
@@ -158,6 +166,13 @@ def load():
     lib.must3r_hip_nn_index_scratch_bytes.restype = C.c_size_t
     lib.must3r_hip_nn_index_build.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp]
     lib.must3r_hip_nn_index_query.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_float), i32, vp, vp]
+    evp = C.POINTER(ExportView)
+    lib.must3r_hip_export_scratch_bytes.argtypes = [evp, i32, i32, i32]
+    lib.must3r_hip_export_scratch_bytes.restype = C.c_size_t
+    lib.must3r_hip_export_count.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, vp, C.c_size_t, i64p, vp]
+    lib.must3r_hip_export_scatter_points.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.must3r_hip_export_vertices.argtypes = [evp, i32, i32, vp, vp, vp, vp, vp]
+    lib.must3r_hip_export_scatter_faces.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, vp, vp, vp]
     lib.must3r_hip_postprocess_cam_scratch_bytes.argtypes = [i32, i32, i32]
     lib.must3r_hip_postprocess_cam_scratch_bytes.restype = C.c_size_t
     lib.must3r_hip_get_profile.argtypes = [vp, C.POINTER(ProfRecord), i32, i32]

@@ -255,6 +255,18 @@ int image_coeffs(int mode, int in, int out, int* ksize, int32_t* bounds, void* w
 size_t image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n);
 int launch_resample(int mode, const must3r_hip_image_desc* descs, int n, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
                     const char** err);
+// scene export (demo/gradio.py:75-156): ordered compaction of the confident points / surviving triangles for up to 8 thresholds from
+// one count + scan, fp64 affine map with one rounding, written in GLB / PLY layout; export.hip
+}  // namespace m3r
+struct must3r_hip_export_view;
+namespace m3r {
+size_t export_scratch_bytes(const must3r_hip_export_view* views, int n_views, int n_thr, int mesh, const char** err);
+int launch_export_count(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int mesh, void* scratch,
+                        size_t scratch_bytes, long long* totals_host, hipStream_t s, const char** err);
+int launch_export_points(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, int layout, int all,
+                         const void* scratch, void* out_pos, void* out_col, float* minmax, hipStream_t s, const char** err);
+int launch_export_faces(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, const void* scratch,
+                        unsigned* out_faces, hipStream_t s, const char** err);
 // postprocess(compute_cam=True): activation + focal (Weiszfeld) + weighted rigid registration, cam.hip
 size_t cam_scratch_bytes(int n_views, int H, int W);
 int launch_postprocess_cam(const float* pm, int linear, int n_views, int H, int W, float* pts3d, float* pts3d_local, float* conf,

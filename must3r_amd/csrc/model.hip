@@ -1595,6 +1595,48 @@ extern "C" int must3r_hip_nn_index_query(const void* index, const float* q_xyz, 
     return 0;
 }
 
+extern "C" size_t must3r_hip_export_scratch_bytes(const must3r_hip_export_view* views_host, int n_views, int n_thr, int mesh) {
+    const char* err = nullptr;
+    const size_t b = export_scratch_bytes(views_host, n_views, n_thr, mesh, &err);
+    if (!b) fail("%s", err ? err : "export: bad view table");
+    return b;
+}
+
+extern "C" int must3r_hip_export_count(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int mesh,
+                                       void* scratch, size_t scratch_bytes, int64_t* totals_host, void* stream) {
+    if (!totals_host) return fail("export_count: null argument");
+    const char* err = nullptr;
+    long long tot[MUST3R_EXPORT_MAX_THR] = {0};
+    if (launch_export_count(views_host, n_views, thr_host, n_thr, mesh, scratch, scratch_bytes, tot, reinterpret_cast<hipStream_t>(stream), &err))
+        return fail("%s", err);
+    for (int k = 0; k < n_thr; ++k) totals_host[k] = tot[k];
+    return 0;
+}
+
+extern "C" int must3r_hip_export_scatter_points(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int k,
+                                                int layout, const void* scratch, void* out_pos, void* out_col, float* minmax, void* stream) {
+    const char* err = nullptr;
+    if (launch_export_points(views_host, n_views, thr_host, n_thr, k, layout, 0, scratch, out_pos, out_col, minmax,
+                             reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
+extern "C" int must3r_hip_export_vertices(const must3r_hip_export_view* views_host, int n_views, int n_thr, void* scratch, float* out_pos,
+                                          void* out_col, float* minmax, void* stream) {
+    const char* err = nullptr;
+    if (launch_export_points(views_host, n_views, nullptr, n_thr, 0, MUST3R_EXPORT_GLB, 1, scratch, out_pos, out_col, minmax,
+                             reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
+extern "C" int must3r_hip_export_scatter_faces(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int k,
+                                               const void* scratch, uint32_t* out_faces, void* stream) {
+    const char* err = nullptr;
+    if (launch_export_faces(views_host, n_views, thr_host, n_thr, k, scratch, out_faces, reinterpret_cast<hipStream_t>(stream), &err))
+        return fail("%s", err);
+    return 0;
+}
+
 extern "C" int must3r_hip_resample_coeffs(int mode, int in_size, int out_size, int* ksize, int32_t* bounds, void* weights) {
     const char* err = nullptr;
     if (image_coeffs(mode, in_size, out_size, ksize, bounds, weights, &err)) return fail("%s", err);

@@ -7,7 +7,8 @@ dispatch of demo/gradio.py:160-217 (``get_reconstruction.py --execution_mode lin
 ``must3r_inference_video`` (:244-331): every frame in turn through ``inference.inference_video_multi_ar``; the keyframe test is a
 callback, ``id % keyframe_interval == 0`` (vidseq) or ``slam_is_keyframe`` (vidslam: the overlap score of the frame against the
 map of keyframe points, ``slam_nn.get_searcher("bvh-hip-quadrant_x2")``, which ``slam_update_scene_state`` grows).
-GLB / PLY export (``get_3D_model_from_scene``) is not here.
+``get_3D_model_from_scene`` / ``export_scene_thresholds`` (demo/gradio.py:75-156): GLB / PLY files from a ``SceneState`` through
+``must3r_amd.export`` (compaction and transform on the GPU, no trimesh).
 """
 import datetime
 import functools
@@ -15,6 +16,7 @@ import functools
 import numpy as np
 import torch
 
+from . import export as _export
 from .engine import postprocess
 from .graph import farthest_point_sampling
 from .image import load_images
@@ -247,10 +249,11 @@ def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrie
                             min_conf_thr, as_pointcloud, transparent_cams, local_pointmaps, cam_size, camera_conf_thr=0.0,
                             loaded_files=""):
     """demo/gradio.py:160-217 -> ``(SceneState, None)``: the four execution modes with the reference's arguments.  The output
-    parameters are accepted and unused: GLB / PLY export is out of scope, and ``should_save_glb=True`` is refused."""
+    parameters are accepted and unused, and ``should_save_glb=True`` is refused: export the returned scene with
+    ``get_3D_model_from_scene`` or ``export_scene_thresholds``, as the reference's get_reconstruction.py does."""
     if should_save_glb:
-        raise NotImplementedError("get_reconstructed_scene: GLB / PLY export (get_3D_model_from_scene) is not part of must3r_amd; "
-                                  "call it with should_save_glb=False and export the returned SceneState yourself")
+        raise NotImplementedError("get_reconstructed_scene does not write the GLB / PLY file itself: call it with should_save_glb=False "
+                                  "and pass the returned SceneState to get_3D_model_from_scene or export_scene_thresholds")
     if filelist:
         image_list = filelist
     elif loaded_files:
@@ -286,3 +289,34 @@ def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrie
                                  batch_num_views=1, render_once=render_once, is_sequence=is_sequence, viser_server=viser_server,
                                  num_refinements_iterations=num_refinements_iterations, verbose=verbose)
     return scene, None
+
+
+@torch.no_grad()
+def get_3D_model_from_scene(outdir, verbose, scene, min_conf_thr=3.0, as_pointcloud=False, transparent_cams=False, local_pointmaps=False,
+                            cam_size=0.05, camera_conf_thr=0.0, filename="scene.glb"):
+    """demo/gradio.py:131-156 -> the path of the written file (``None`` for ``scene is None``).  A file name ending in ``ply`` writes
+    the point cloud alone (no cameras) and refuses mesh mode; anything else is a GLB with one wireframe frustum per camera whose median
+    confidence reaches ``camera_conf_thr``.  ``transparent_cams`` is accepted and has no effect.  A threshold that selects nothing
+    raises ``ValueError`` and writes no file."""
+    if scene is None:
+        return None
+    path = _export.export_scene(outdir, scene, [min_conf_thr], [filename], as_pointcloud=as_pointcloud, transparent_cams=transparent_cams,
+                                local_pointmaps=local_pointmaps, cam_size=cam_size, camera_conf_thr=camera_conf_thr, verbose=verbose)[0]
+    if path is None:
+        raise ValueError(f"get_3D_model_from_scene: no {'point' if as_pointcloud else 'triangle'} has confidence >= {min_conf_thr}")
+    return path
+
+
+@torch.no_grad()
+def export_scene_thresholds(outdir, scene, thresholds, file_type="glb", **viz_args):
+    """``scene_<thr>.<file_type>`` for every threshold (get_reconstruction.py:106-113) -> the list of written paths; a threshold that
+    selects nothing is skipped.  One count + scan on the GPU serves up to 8 thresholds (more are chunked), one scatter each.
+    ``viz_args``: ``as_pointcloud`` (default True, as the reference's CLI), ``transparent_cams``, ``local_pointmaps``, ``cam_size``,
+    ``camera_conf_thr``, ``verbose``."""
+    if scene is None:
+        return []
+    if file_type not in ("glb", "ply"):
+        raise ValueError(f"export_scene_thresholds: file_type {file_type!r} is not 'glb' or 'ply'")
+    viz_args.setdefault("as_pointcloud", True)
+    names = [f"scene_{thr}.{file_type}" for thr in thresholds]
+    return [p for p in _export.export_scene(outdir, scene, thresholds, names, **viz_args) if p is not None]
