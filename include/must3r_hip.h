@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 13
+#define MUST3R_HIP_ABI_VERSION 14
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -320,6 +320,56 @@ int must3r_hip_export_vertices(const must3r_hip_export_view* views_host, int n_v
                                void* out_col, float* minmax, void* stream);
 int must3r_hip_export_scatter_faces(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int k,
                                     const void* scratch, uint32_t* out_faces, void* stream);
+
+/* ---- ABI 14: checkpoint evaluation -- the forward values of eval.py's metric and of must3r/engine/losses.py (Regr3D, ConfLoss), and
+ * normalize_pointcloud's norm_factor (must3r/tools/geometry.py:21-84); metrics.hip ----
+ * must3r_hip_metrics_loss: one pass over a batch of B scenes x V views of H x W pixels.  Per pixel, in fp32:
+ *   g  = in_camera0[b] applied to gt_pts (world);  valid_g = valid && (|g| <= dist_clip when has_dist_clip);  sky_g = sky && !valid_g
+ *   gl = w2c[b][v] applied to gt_pts (only with pr_local);  valid_l, sky_l likewise
+ *   g, gl are divided by gt_scale[b], pr_pts and pr_local by pr_scale[b] (NULL = 1); with gt_warp resp. pr_warp[b] the global points are
+ *   first multiplied by log1p(d) / max(d, 1e-8), d their norm (normalize_pointcloud's 'warp-log1p')
+ *   loss_in_log 1: x -> x / max(|x|, 1e-8) * log1p(|x|) on both terms, 2 ('before'): on the global term only
+ *   l = |pr - g| where valid_g, sky_loss_value where sky_g (sky pixels count only when sky is given and sky_loss_value > 0)
+ *   with conf: cl = l * conf - alpha * log(conf)
+ * Outputs per (scene, view): counts int64 [B][V][2] (global, local) and sums fp64 [B][V][4] (l global, l local, cl global, cl local; the
+ * local / conf entries are 0 without pr_local / conf).  Pixels outside the selection are never read into a sum (their points may be NaN
+ * or inf).  Accumulation is fp64 per thread, wave and block; per-block partials go to a slab in scratch and are summed in index order;
+ * blocks never span two views, so the figures of a scene are bit-identical from run to run and whatever else is in the batch.
+ * Optional per-pixel outputs (all four or none): pix_g / pix_l fp32 [B][V][H][W] (l, NaN outside the selection), msk_g / msk_l uint8.
+ * must3r_hip_metrics_factor: norm_factor fp32 [B] of pts [B][V][H][W][3] (transformed by trf [B][4][4] first when given) over the valid
+ * pixels: MUST3R_NORM_AVG_DIS sum d / (nnz + 1e-8), AVG_LOG1P (also 'warp-log1p') sum log1p(d) / (nnz + 1e-8), SQRT_DIS
+ * (mean sqrt d)^2, MEDIAN_DIS the lower median, all clipped at 1e-8; SQRT / MEDIAN of an empty scene are NaN.  The median is an exact
+ * radix select over the bit patterns of the distances (3 histogram passes of 2048 / 2048 / 1024 bins); it needs dist fp32 [B][V*H*W],
+ * which receives every distance (NaN where not selected).  Blocks never span two scenes.
+ * Scratch sizes: the two *_scratch_bytes calls (0 with a message on bad sizes).  All pointers are device pointers. */
+#define MUST3R_NORM_AVG_DIS 0
+#define MUST3R_NORM_AVG_LOG1P 1
+#define MUST3R_NORM_SQRT_DIS 2
+#define MUST3R_NORM_MEDIAN_DIS 3
+typedef struct must3r_hip_metrics_loss_args {
+    int32_t n_scenes, n_views, H, W;
+    const float* gt_pts;          /* [B][V][H][W][3] world coordinates */
+    const float* in_camera0;      /* [B][4][4] row-major */
+    const float* w2c;             /* [B][V][4][4], required with pr_local */
+    const float* pr_pts;          /* [B][V][H][W][3] */
+    const float* pr_local;        /* or NULL */
+    const float* conf;            /* [B][V][H][W] or NULL */
+    const uint8_t* valid;         /* [B][V][H][W] */
+    const uint8_t* sky;           /* or NULL */
+    const float* gt_scale;        /* [B] or NULL */
+    const float* pr_scale;        /* [B] or NULL */
+    const uint8_t* pr_warp;       /* [B] or NULL */
+    int32_t gt_warp, has_dist_clip, loss_in_log;
+    float dist_clip, sky_loss_value, alpha;
+    int64_t* counts;              /* [B][V][2] */
+    double* sums;                 /* [B][V][4] */
+    float* pix_g; float* pix_l; uint8_t* msk_g; uint8_t* msk_l;   /* optional */
+} must3r_hip_metrics_loss_args;
+size_t must3r_hip_metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W);
+int must3r_hip_metrics_loss(const must3r_hip_metrics_loss_args* args, void* scratch, size_t scratch_bytes, void* stream);
+size_t must3r_hip_metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode);
+int must3r_hip_metrics_factor(const float* pts, const float* trf, const uint8_t* valid, int n_scenes, int n_views, int H, int W, int mode,
+                              float* factor, float* dist, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- ABI 9: image ingestion -- the reference's three image loaders in front of the forwards ----
  * must3r/demo/inference.py:63-76 load_images: ImgNorm (ToTensor, Normalize(0.5, 0.5)), then get_resize_function

@@ -15,9 +15,10 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 13
+ABI_VERSION = 14
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
+NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
 
@@ -42,6 +43,7 @@ EXPORTS = (
     "must3r_hip_nn_index_bytes", "must3r_hip_nn_index_scratch_bytes", "must3r_hip_nn_index_build", "must3r_hip_nn_index_query",
     "must3r_hip_export_scratch_bytes", "must3r_hip_export_count", "must3r_hip_export_scatter_points", "must3r_hip_export_vertices",
     "must3r_hip_export_scatter_faces",
+    "must3r_hip_metrics_loss_scratch_bytes", "must3r_hip_metrics_loss", "must3r_hip_metrics_factor_scratch_bytes", "must3r_hip_metrics_factor",
 )
 
 
@@ -99,6 +101,17 @@ class AttnOp(C.Structure):
 class ExportView(C.Structure):
     """must3r_hip_export_view: one view of a scene export (include/must3r_hip.h, ABI 13)."""
     _fields_ = [("conf", C.c_void_p), ("pts", C.c_void_p), ("rgb", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_double * 12)]
+
+
+class MetricsLossArgs(C.Structure):
+    """must3r_hip_metrics_loss_args: one fused loss pass over [B, V, H, W] (include/must3r_hip.h, ABI 14)."""
+    _fields_ = [("n_scenes", C.c_int32), ("n_views", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("gt_pts", C.c_void_p), ("in_camera0", C.c_void_p), ("w2c", C.c_void_p), ("pr_pts", C.c_void_p), ("pr_local", C.c_void_p),
+                ("conf", C.c_void_p), ("valid", C.c_void_p), ("sky", C.c_void_p), ("gt_scale", C.c_void_p), ("pr_scale", C.c_void_p),
+                ("pr_warp", C.c_void_p), ("gt_warp", C.c_int32), ("has_dist_clip", C.c_int32), ("loss_in_log", C.c_int32),
+                ("dist_clip", C.c_float), ("sky_loss_value", C.c_float), ("alpha", C.c_float),
+                ("counts", C.c_void_p), ("sums", C.c_void_p),
+                ("pix_g", C.c_void_p), ("pix_l", C.c_void_p), ("msk_g", C.c_void_p), ("msk_l", C.c_void_p)]
 
 
 class ProfRecord(C.Structure):
@@ -173,6 +186,12 @@ def load():
     lib.must3r_hip_export_scatter_points.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, i32, vp, vp, vp, vp, vp]
     lib.must3r_hip_export_vertices.argtypes = [evp, i32, i32, vp, vp, vp, vp, vp]
     lib.must3r_hip_export_scatter_faces.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, vp, vp, vp]
+    lib.must3r_hip_metrics_loss_scratch_bytes.argtypes = [i32, i32, i32, i32]
+    lib.must3r_hip_metrics_loss_scratch_bytes.restype = C.c_size_t
+    lib.must3r_hip_metrics_loss.argtypes = [C.POINTER(MetricsLossArgs), vp, C.c_size_t, vp]
+    lib.must3r_hip_metrics_factor_scratch_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.must3r_hip_metrics_factor_scratch_bytes.restype = C.c_size_t
+    lib.must3r_hip_metrics_factor.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]
     lib.must3r_hip_postprocess_cam_scratch_bytes.argtypes = [i32, i32, i32]
     lib.must3r_hip_postprocess_cam_scratch_bytes.restype = C.c_size_t
     lib.must3r_hip_get_profile.argtypes = [vp, C.POINTER(ProfRecord), i32, i32]

@@ -267,6 +267,15 @@ int launch_export_points(const must3r_hip_export_view* views, int n_views, const
                          const void* scratch, void* out_pos, void* out_col, float* minmax, hipStream_t s, const char** err);
 int launch_export_faces(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, const void* scratch,
                         unsigned* out_faces, hipStream_t s, const char** err);
+// checkpoint evaluation (eval.py, must3r/engine/losses.py, tools/geometry.py normalize_pointcloud): fused masked reductions; metrics.hip
+}  // namespace m3r
+struct must3r_hip_metrics_loss_args;
+namespace m3r {
+size_t metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W, const char** err);
+int launch_metrics_loss(const must3r_hip_metrics_loss_args* a, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err);
+size_t metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode, const char** err);
+int launch_metrics_factor(const float* pts, const float* trf, const unsigned char* valid, int n_scenes, int n_views, int H, int W, int mode,
+                          float* factor, float* dist, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err);
 // postprocess(compute_cam=True): activation + focal (Weiszfeld) + weighted rigid registration, cam.hip
 size_t cam_scratch_bytes(int n_views, int H, int W);
 int launch_postprocess_cam(const float* pm, int linear, int n_views, int H, int W, float* pts3d, float* pts3d_local, float* conf,

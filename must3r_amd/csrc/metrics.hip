@@ -1,0 +1,499 @@
+// Checkpoint evaluation (eval.py:133-150; must3r/engine/losses.py Regr3D / ConfLoss; must3r/tools/geometry.py normalize_pointcloud):
+// masked reductions over [B, V, H, W] pointmaps, forward values only.
+//
+//   metrics_loss_kernel<PIX>    grid (blocks per view, B V): thread t of a block owns pixels 4t .. 4t+3 of a 1024-pixel chunk and walks the
+//                               view in steps of gridDim.x chunks.  The mask bytes are read first; the points of a 4-pixel group with no
+//                               selected pixel are not read at all.  Rigid transforms, scales, warp, log map and the L21 distance in fp32
+//                               with every operation rounded (this file is built with -ffp-contract=off); sums in fp64 per thread, then
+//                               wave (xor butterfly) and block (LDS, wave order) -> slab[view][block][6].  PIX: also the per-pixel values.
+//   metrics_loss_final_kernel   one thread per view adds the view's partials in block order -> counts int64 [2], sums fp64 [4]
+//   metrics_factor_kernel<MODE> grid (blocks per scene, B): the same walk over the V H W pixels of a scene; sum of d, log1p(d) or sqrt(d)
+//                               over the valid pixels.  MEDIAN: writes d (NaN where not selected) and counts the top 11 bits of its pattern.
+//   metrics_hist_kernel         radix-select passes 2 and 3 over the stored distances: the patterns that share the prefix found so far
+//   metrics_select_kernel       one block per scene: the bin that holds the wanted rank -> longer prefix, smaller rank; clears the bins
+//   metrics_factor_final_kernel one thread per scene: partials in block order -> norm_factor fp32, clipped at 1e-8
+//
+// Nothing here uses floating-point atomics; the histograms use integer ones, whose result does not depend on their order.  The block
+// count of a view (scene) depends on H W (V H W) alone, so a scene's figures do not depend on the rest of the batch.
+#include <cstdint>
+#include "common.hpp"
+#include "kernels.hpp"
+#include "../../include/must3r_hip.h"
+
+namespace m3r {
+namespace {
+
+constexpr int MET_T = 256;                       // threads per block
+constexpr int MET_CHUNK = MET_T * 4;             // pixels per block and step
+constexpr int MET_VIEW_BLOCKS = 32;              // at most, per view
+constexpr int MET_SCENE_BLOCKS = 128;            // at most, per scene
+constexpr int RS_BINS = 2048;
+
+struct LossDev {
+    must3r_hip_metrics_loss_args a;
+    unsigned n_pix;
+};
+
+__device__ __forceinline__ void ld12(const float* __restrict__ q, const unsigned i, const unsigned n, float (&o)[12]) {
+    if (i + 4 <= n && ((reinterpret_cast<uintptr_t>(q) & 15) == 0)) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float4 v = reinterpret_cast<const float4*>(q)[j];
+            o[4 * j] = v.x; o[4 * j + 1] = v.y; o[4 * j + 2] = v.z; o[4 * j + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) o[j] = i + j / 3 < n ? q[j] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void ld4(const float* __restrict__ q, const unsigned i, const unsigned n, float (&o)[4]) {
+    if (i + 4 <= n && ((reinterpret_cast<uintptr_t>(q) & 15) == 0)) {
+        const float4 v = *reinterpret_cast<const float4*>(q);
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = i + j < n ? q[j] : 0.f;
+    }
+}
+
+// four mask bytes at q (pixel i of n): packed little-endian, 0 past the end
+__device__ __forceinline__ unsigned ld4b(const unsigned char* __restrict__ q, const unsigned i, const unsigned n) {
+    if (i + 4 <= n && ((reinterpret_cast<uintptr_t>(q) & 3) == 0)) return *reinterpret_cast<const unsigned*>(q);
+    unsigned r = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r |= (i + j < n ? (unsigned)q[j] : 0u) << (8 * j);
+    return r;
+}
+
+__device__ __forceinline__ void st4f(float* __restrict__ q, const unsigned i, const unsigned n, const float (&v)[4]) {
+    if (i + 4 <= n && ((reinterpret_cast<uintptr_t>(q) & 15) == 0)) {
+        *reinterpret_cast<float4*>(q) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (i + j < n) q[j] = v[j];
+    }
+}
+
+__device__ __forceinline__ float norm3(const float x, const float y, const float z) { return sqrtf((x * x + y * y) + z * z); }
+
+// rows 0..2 of a row-major 4x4
+__device__ __forceinline__ void rigid(const float (&T)[12], const float x, const float y, const float z, float (&o)[3]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) o[r] = ((T[4 * r] * x + T[4 * r + 1] * y) + T[4 * r + 2] * z) + T[4 * r + 3];
+}
+
+// normalize_pointcloud's warp and scale: x * (log1p(d) / max(d, 1e-8)) when warp, then / scale
+__device__ __forceinline__ void warp_scale(float (&p)[3], const bool warp, const float scale) {
+    if (warp) {
+        const float d = norm3(p[0], p[1], p[2]);
+        const float f = log1pf(d) / fmaxf(d, 1e-8f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] *= f;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] /= scale;
+}
+
+// apply_log_to_norm
+__device__ __forceinline__ void log_map(float (&p)[3]) {
+    const float d = norm3(p[0], p[1], p[2]);
+    const float c = fmaxf(d, 1e-8f), l = log1pf(d);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = p[k] / c * l;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// block total of K per-thread values in lane / wave order -> out[k] (thread 0 writes); s: K * MET_T / 64 doubles of LDS
+template <int K>
+__device__ __forceinline__ void block_sum_store(const double (&v)[K], double* s, double* __restrict__ out) {
+    const unsigned wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double w = wave_sum_f64(v[k]);
+        if ((threadIdx.x & 63) == 0) s[wave * K + k] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double r = s[threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < MET_T / 64; ++w) r += s[w * K + threadIdx.x];
+        out[threadIdx.x] = r;
+    }
+}
+
+template <bool PIX>
+__global__ void __launch_bounds__(MET_T) metrics_loss_kernel(const LossDev p, double* __restrict__ slab) {
+    __shared__ double s_red[6 * MET_T / 64];
+    const must3r_hip_metrics_loss_args& a = p.a;
+    const unsigned bv = blockIdx.y, b = bv / (unsigned)a.n_views, n = p.n_pix;
+    const size_t base = (size_t)bv * n;
+    const bool local = a.pr_local != nullptr, use_sky = a.sky != nullptr && a.sky_loss_value > 0.f, has_conf = a.conf != nullptr;
+    float T0[12], T1[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        T0[k] = a.in_camera0[16 * (size_t)b + k];
+        T1[k] = local ? a.w2c[16 * (size_t)bv + k] : 0.f;
+    }
+    const float gs = a.gt_scale ? a.gt_scale[b] : 1.f, ps = a.pr_scale ? a.pr_scale[b] : 1.f;
+    const bool gwarp = a.gt_warp != 0, pwarp = a.pr_warp && a.pr_warp[b] != 0;
+    const bool log_g = a.loss_in_log != 0, log_l = a.loss_in_log == 1;
+    double acc[6] = {0, 0, 0, 0, 0, 0};           // l global, l local, cl global, cl local, count global, count local
+    for (unsigned i0 = (blockIdx.x * MET_T + threadIdx.x) * 4; i0 < n; i0 += gridDim.x * MET_CHUNK) {
+        const unsigned vm = ld4b(a.valid + base + i0, i0, n);
+        const unsigned sm = use_sky ? ld4b(a.sky + base + i0, i0, n) : 0u;
+        float og[4], ol[4];
+        unsigned mg = 0, ml = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) og[j] = ol[j] = __uint_as_float(0x7fc00000u);
+        if (vm | sm) {
+            float g[12], q[12], ql[12], c[4];
+            // ground truth is only needed (and only trusted) under the valid mask
+            if (vm) ld12(a.gt_pts + 3 * (base + i0), i0, n, g);
+            if (vm) ld12(a.pr_pts + 3 * (base + i0), i0, n, q);
+            if (vm && local) ld12(a.pr_local + 3 * (base + i0), i0, n, ql);
+            if (has_conf) ld4(a.conf + base + i0, i0, n, c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool v = (vm >> (8 * j)) & 0xff, s = (sm >> (8 * j)) & 0xff;
+                if (!v && !s) continue;
+                float wg[3] = {0.f, 0.f, 0.f}, wl[3] = {0.f, 0.f, 0.f};
+                bool vg = v, vl = v;
+                if (v) {
+                    rigid(T0, g[3 * j], g[3 * j + 1], g[3 * j + 2], wg);
+                    if (a.has_dist_clip) vg = norm3(wg[0], wg[1], wg[2]) <= a.dist_clip;
+                    if (local) {
+                        rigid(T1, g[3 * j], g[3 * j + 1], g[3 * j + 2], wl);
+                        if (a.has_dist_clip) vl = norm3(wl[0], wl[1], wl[2]) <= a.dist_clip;
+                    }
+                }
+                const bool sg = s && !vg, sl = s && !vl;
+                const float cj = has_conf ? c[j] : 1.f;
+                const float lc = has_conf ? a.alpha * logf(cj) : 0.f;
+                if (vg || sg) {
+                    float l = a.sky_loss_value;
+                    if (!sg) {
+                        float pr[3] = {q[3 * j], q[3 * j + 1], q[3 * j + 2]};
+                        warp_scale(wg, gwarp, gs);
+                        warp_scale(pr, pwarp, ps);
+                        if (log_g) { log_map(wg); log_map(pr); }
+                        l = norm3(pr[0] - wg[0], pr[1] - wg[1], pr[2] - wg[2]);
+                    }
+                    acc[0] += (double)l;
+                    if (has_conf) acc[2] += (double)(l * cj - lc);
+                    acc[4] += 1.0;
+                    og[j] = l;
+                    mg |= 1u << (8 * j);
+                }
+                if (local && (vl || sl)) {
+                    float l = a.sky_loss_value;
+                    if (!sl) {
+                        float pr[3] = {ql[3 * j], ql[3 * j + 1], ql[3 * j + 2]};
+                        warp_scale(wl, false, gs);
+                        warp_scale(pr, false, ps);
+                        if (log_l) { log_map(wl); log_map(pr); }
+                        l = norm3(pr[0] - wl[0], pr[1] - wl[1], pr[2] - wl[2]);
+                    }
+                    acc[1] += (double)l;
+                    if (has_conf) acc[3] += (double)(l * cj - lc);
+                    acc[5] += 1.0;
+                    ol[j] = l;
+                    ml |= 1u << (8 * j);
+                }
+            }
+        }
+        if (PIX) {
+            st4f(a.pix_g + base + i0, i0, n, og);
+            st4f(a.pix_l + base + i0, i0, n, ol);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (i0 + j < n) {
+                    a.msk_g[base + i0 + j] = (unsigned char)((mg >> (8 * j)) & 1u);
+                    a.msk_l[base + i0 + j] = (unsigned char)((ml >> (8 * j)) & 1u);
+                }
+            }
+        }
+    }
+    block_sum_store<6>(acc, s_red, slab + ((size_t)bv * gridDim.x + blockIdx.x) * 6);
+}
+
+__global__ void __launch_bounds__(64) metrics_loss_final_kernel(const double* __restrict__ slab, const int n_bv, const int n_blocks,
+                                                                long long* __restrict__ counts, double* __restrict__ sums) {
+    const int bv = blockIdx.x * 64 + threadIdx.x;
+    if (bv >= n_bv) return;
+    double r[6] = {0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < n_blocks; ++k) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) r[j] += slab[((size_t)bv * n_blocks + k) * 6 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sums[4 * (size_t)bv + j] = r[j];
+    counts[2 * (size_t)bv] = (long long)r[4];
+    counts[2 * (size_t)bv + 1] = (long long)r[5];
+}
+
+struct SelState {                                // radix select, per scene
+    unsigned prefix;
+    unsigned pad;
+    unsigned long long rank, count;
+};
+
+// MODE: MUST3R_NORM_*
+template <int MODE>
+__global__ void __launch_bounds__(MET_T) metrics_factor_kernel(const float* __restrict__ pts, const float* __restrict__ trf,
+                                                               const unsigned char* __restrict__ valid, const unsigned n,
+                                                               float* __restrict__ dist, double* __restrict__ slab,
+                                                               unsigned* __restrict__ hist) {
+    constexpr bool MEDIAN = MODE == MUST3R_NORM_MEDIAN_DIS;
+    __shared__ double s_red[2 * MET_T / 64];
+    __shared__ unsigned s_hist[MEDIAN ? RS_BINS : 1];
+    const unsigned b = blockIdx.y;
+    const size_t base = (size_t)b * n;
+    float T[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T[k] = trf ? trf[16 * (size_t)b + k] : 0.f;
+    if (MEDIAN) {
+        for (int k = threadIdx.x; k < RS_BINS; k += MET_T) s_hist[k] = 0;
+        __syncthreads();
+    }
+    double acc[2] = {0, 0};
+    for (unsigned i0 = (blockIdx.x * MET_T + threadIdx.x) * 4; i0 < n; i0 += gridDim.x * MET_CHUNK) {
+        const unsigned vm = ld4b(valid + base + i0, i0, n);
+        float od[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) od[j] = __uint_as_float(0x7fc00000u);
+        if (vm) {
+            float g[12];
+            ld12(pts + 3 * (base + i0), i0, n, g);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (!((vm >> (8 * j)) & 0xff)) continue;
+                float w[3] = {g[3 * j], g[3 * j + 1], g[3 * j + 2]};
+                if (trf) rigid(T, g[3 * j], g[3 * j + 1], g[3 * j + 2], w);
+                const float d = norm3(w[0], w[1], w[2]);
+                if (MODE == MUST3R_NORM_AVG_DIS) { acc[0] += (double)d; acc[1] += 1.0; }
+                if (MODE == MUST3R_NORM_AVG_LOG1P) { acc[0] += (double)log1pf(d); acc[1] += 1.0; }
+                // nanmean / nanmedian skip the NaN distances of valid pixels too
+                if (MODE == MUST3R_NORM_SQRT_DIS && d == d) { acc[0] += (double)sqrtf(d); acc[1] += 1.0; }
+                if (MEDIAN && d == d) {
+                    od[j] = d;
+                    atomicAdd(&s_hist[__float_as_uint(d) >> 21], 1u);
+                }
+            }
+        }
+        if (MEDIAN) st4f(dist + base + i0, i0, n, od);
+    }
+    if (MEDIAN) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < RS_BINS; k += MET_T) {
+            const unsigned c = s_hist[k];
+            if (c) atomicAdd(&hist[(size_t)b * RS_BINS + k], c);
+        }
+    } else {
+        block_sum_store<2>(acc, s_red, slab + ((size_t)b * gridDim.x + blockIdx.x) * 2);
+    }
+}
+
+// distances whose pattern >> (shift + bits) equals the scene's prefix: count bin (pattern >> shift) & (2^bits - 1)
+__global__ void __launch_bounds__(MET_T) metrics_hist_kernel(const float* __restrict__ dist, const unsigned n, const SelState* __restrict__ state,
+                                                             const int shift, const int bits, unsigned* __restrict__ hist) {
+    __shared__ unsigned s_hist[RS_BINS];
+    const unsigned b = blockIdx.y;
+    const size_t base = (size_t)b * n;
+    const unsigned prefix = state[b].prefix, mask = (1u << bits) - 1u;
+    for (int k = threadIdx.x; k < RS_BINS; k += MET_T) s_hist[k] = 0;
+    __syncthreads();
+    for (unsigned i0 = (blockIdx.x * MET_T + threadIdx.x) * 4; i0 < n; i0 += gridDim.x * MET_CHUNK) {
+        float d[4];
+        ld4(dist + base + i0, i0, n, d);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned u = __float_as_uint(d[j]);
+            if (i0 + j < n && d[j] == d[j] && (u >> (shift + bits)) == prefix) atomicAdd(&s_hist[(u >> shift) & mask], 1u);
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < RS_BINS; k += MET_T) {
+        const unsigned c = s_hist[k];
+        if (c) atomicAdd(&hist[(size_t)b * RS_BINS + k], c);
+    }
+}
+
+// first: the rank wanted is that of the lower median of all counted elements
+__global__ void __launch_bounds__(MET_T) metrics_select_kernel(unsigned* __restrict__ hist, SelState* __restrict__ state, const int bits,
+                                                               const int first) {
+    constexpr int PER = RS_BINS / MET_T;
+    __shared__ unsigned long long s_pre[MET_T + 1];
+    unsigned* h = hist + (size_t)blockIdx.x * RS_BINS;
+    unsigned c[PER];
+    unsigned long long tot = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { c[k] = h[threadIdx.x * PER + k]; tot += c[k]; }
+    s_pre[threadIdx.x + 1] = tot;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s_pre[0] = 0;
+        for (int t = 1; t <= MET_T; ++t) s_pre[t] += s_pre[t - 1];
+    }
+    __syncthreads();
+    SelState st = state[blockIdx.x];
+    if (first) {
+        st.count = s_pre[MET_T];
+        st.rank = st.count ? (st.count - 1) / 2 : 0;
+        st.prefix = 0;
+    }
+    __syncthreads();                               // every thread has read the state
+    if (st.count && s_pre[threadIdx.x] <= st.rank && st.rank < s_pre[threadIdx.x + 1]) {
+        unsigned long long cum = s_pre[threadIdx.x];
+        int k = 0;
+        while (cum + c[k] <= st.rank) { cum += c[k]; ++k; }
+        st.prefix = (st.prefix << bits) | (unsigned)(threadIdx.x * PER + k);
+        st.rank -= cum;
+        st.pad = 0;
+        state[blockIdx.x] = st;
+    } else if (!st.count && threadIdx.x == 0) {
+        st.pad = 0;
+        state[blockIdx.x] = st;
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) h[threadIdx.x * PER + k] = 0;
+}
+
+__global__ void __launch_bounds__(64) metrics_factor_final_kernel(const double* __restrict__ slab, const SelState* __restrict__ state,
+                                                                  const int n_scenes, const int n_blocks, const int mode,
+                                                                  float* __restrict__ factor) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n_scenes) return;
+    float f;
+    if (mode == MUST3R_NORM_MEDIAN_DIS) {
+        f = state[b].count ? __uint_as_float(state[b].prefix) : __uint_as_float(0x7fc00000u);
+    } else {
+        double s = 0, c = 0;
+        for (int k = 0; k < n_blocks; ++k) { s += slab[((size_t)b * n_blocks + k) * 2]; c += slab[((size_t)b * n_blocks + k) * 2 + 1]; }
+        if (mode == MUST3R_NORM_SQRT_DIS) {
+            const float m = (float)(s / c);          // 0 / 0 = NaN, as nanmean of nothing
+            f = m * m;
+        } else {
+            f = (float)(s / (c + 1e-8));
+        }
+    }
+    factor[b] = f < 1e-8f ? 1e-8f : f;             // clip(min=1e-8); NaN stays NaN
+}
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int blocks_for(long long n, int cap) {
+    const long long c = (n + MET_CHUNK - 1) / MET_CHUNK;
+    return (int)(c < cap ? c : cap);
+}
+
+int check_sizes(const char* who, int n_scenes, int n_views, int H, int W, const char** err) {
+    static thread_local char msg[128];
+    const char* what = nullptr;
+    if (n_scenes <= 0) what = "n_scenes must be positive";
+    else if (n_views <= 0) what = "n_views must be positive";
+    else if (H <= 0 || W <= 0) what = "H and W must be positive";
+    else if ((long long)n_views * H * W >= (1LL << 31)) what = "a scene has 2^31 or more pixels";
+    else if ((long long)n_scenes * n_views > 65535) what = "more than 65535 views in a batch";
+    if (!what) return 0;
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    *err = msg;
+    return 1;
+}
+
+struct FactorPlan { int n_blocks; size_t off_hist, off_state, bytes; };
+
+void factor_plan(int n_scenes, int n_views, int H, int W, FactorPlan* p) {
+    p->n_blocks = blocks_for((long long)n_views * H * W, MET_SCENE_BLOCKS);
+    size_t off = align256((size_t)n_scenes * p->n_blocks * 2 * sizeof(double));
+    p->off_hist = off;
+    off = align256(off + (size_t)n_scenes * RS_BINS * sizeof(unsigned));
+    p->off_state = off;
+    off = align256(off + (size_t)n_scenes * sizeof(SelState));
+    p->bytes = off;
+}
+
+}  // namespace
+
+size_t metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W, const char** err) {
+    if (check_sizes("metrics_loss", n_scenes, n_views, H, W, err)) return 0;
+    return align256((size_t)n_scenes * n_views * blocks_for((long long)H * W, MET_VIEW_BLOCKS) * 6 * sizeof(double));
+}
+
+int launch_metrics_loss(const must3r_hip_metrics_loss_args* a, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err) {
+    if (!a) { *err = "metrics_loss: null argument block"; return 1; }
+    if (check_sizes("metrics_loss", a->n_scenes, a->n_views, a->H, a->W, err)) return 1;
+    if (!a->gt_pts || !a->in_camera0 || !a->pr_pts || !a->valid || !a->counts || !a->sums || !scratch) {
+        *err = "metrics_loss: null argument"; return 1;
+    }
+    if (a->pr_local && !a->w2c) { *err = "metrics_loss: the local term needs w2c"; return 1; }
+    if (a->loss_in_log < 0 || a->loss_in_log > 2) { *err = "metrics_loss: loss_in_log must be 0, 1 or 2"; return 1; }
+    const int n_pix_out = (a->pix_g != nullptr) + (a->pix_l != nullptr) + (a->msk_g != nullptr) + (a->msk_l != nullptr);
+    if (n_pix_out != 0 && n_pix_out != 4) { *err = "metrics_loss: the per-pixel outputs come all four or not at all"; return 1; }
+    if (scratch_bytes < metrics_loss_scratch_bytes(a->n_scenes, a->n_views, a->H, a->W, err)) {
+        *err = "metrics_loss: scratch too small"; return 1;
+    }
+    LossDev p;
+    p.a = *a;
+    p.n_pix = (unsigned)((long long)a->H * a->W);
+    const int n_bv = a->n_scenes * a->n_views, nb = blocks_for(p.n_pix, MET_VIEW_BLOCKS);
+    double* slab = reinterpret_cast<double*>(scratch);
+    const dim3 g((unsigned)nb, (unsigned)n_bv), t(MET_T);
+    if (n_pix_out) hipLaunchKernelGGL(metrics_loss_kernel<true>, g, t, 0, s, p, slab);
+    else hipLaunchKernelGGL(metrics_loss_kernel<false>, g, t, 0, s, p, slab);
+    hipLaunchKernelGGL(metrics_loss_final_kernel, dim3((unsigned)((n_bv + 63) / 64)), dim3(64), 0, s, slab, n_bv, nb,
+                       reinterpret_cast<long long*>(a->counts), a->sums);
+    if (hipGetLastError() != hipSuccess) { *err = "metrics_loss: launch failed"; return 1; }
+    return 0;
+}
+
+size_t metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode, const char** err) {
+    if (check_sizes("metrics_factor", n_scenes, n_views, H, W, err)) return 0;
+    if (mode < MUST3R_NORM_AVG_DIS || mode > MUST3R_NORM_MEDIAN_DIS) { *err = "metrics_factor: unknown mode"; return 0; }
+    FactorPlan p;
+    factor_plan(n_scenes, n_views, H, W, &p);
+    return p.bytes;
+}
+
+int launch_metrics_factor(const float* pts, const float* trf, const unsigned char* valid, int n_scenes, int n_views, int H, int W, int mode,
+                          float* factor, float* dist, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err) {
+    if (check_sizes("metrics_factor", n_scenes, n_views, H, W, err)) return 1;
+    if (mode < MUST3R_NORM_AVG_DIS || mode > MUST3R_NORM_MEDIAN_DIS) { *err = "metrics_factor: unknown mode"; return 1; }
+    if (!pts || !valid || !factor || !scratch) { *err = "metrics_factor: null argument"; return 1; }
+    if (mode == MUST3R_NORM_MEDIAN_DIS && !dist) { *err = "metrics_factor: median_dis needs the distance buffer"; return 1; }
+    FactorPlan p;
+    factor_plan(n_scenes, n_views, H, W, &p);
+    if (scratch_bytes < p.bytes) { *err = "metrics_factor: scratch too small"; return 1; }
+    char* sc = reinterpret_cast<char*>(scratch);
+    double* slab = reinterpret_cast<double*>(sc);
+    unsigned* hist = reinterpret_cast<unsigned*>(sc + p.off_hist);
+    SelState* state = reinterpret_cast<SelState*>(sc + p.off_state);
+    const unsigned n = (unsigned)((long long)n_views * H * W);
+    const dim3 g((unsigned)p.n_blocks, (unsigned)n_scenes), t(MET_T);
+    if (mode == MUST3R_NORM_MEDIAN_DIS) {
+        if (hipMemsetAsync(sc + p.off_hist, 0, p.bytes - p.off_hist, s) != hipSuccess) { *err = "metrics_factor: clearing the bins failed"; return 1; }
+        hipLaunchKernelGGL(metrics_factor_kernel<MUST3R_NORM_MEDIAN_DIS>, g, t, 0, s, pts, trf, valid, n, dist, slab, hist);
+        hipLaunchKernelGGL(metrics_select_kernel, dim3((unsigned)n_scenes), t, 0, s, hist, state, 11, 1);
+        hipLaunchKernelGGL(metrics_hist_kernel, g, t, 0, s, dist, n, state, 10, 11, hist);
+        hipLaunchKernelGGL(metrics_select_kernel, dim3((unsigned)n_scenes), t, 0, s, hist, state, 11, 0);
+        hipLaunchKernelGGL(metrics_hist_kernel, g, t, 0, s, dist, n, state, 0, 10, hist);
+        hipLaunchKernelGGL(metrics_select_kernel, dim3((unsigned)n_scenes), t, 0, s, hist, state, 10, 0);
+    } else if (mode == MUST3R_NORM_AVG_DIS) {
+        hipLaunchKernelGGL(metrics_factor_kernel<MUST3R_NORM_AVG_DIS>, g, t, 0, s, pts, trf, valid, n, dist, slab, hist);
+    } else if (mode == MUST3R_NORM_AVG_LOG1P) {
+        hipLaunchKernelGGL(metrics_factor_kernel<MUST3R_NORM_AVG_LOG1P>, g, t, 0, s, pts, trf, valid, n, dist, slab, hist);
+    } else {
+        hipLaunchKernelGGL(metrics_factor_kernel<MUST3R_NORM_SQRT_DIS>, g, t, 0, s, pts, trf, valid, n, dist, slab, hist);
+    }
+    hipLaunchKernelGGL(metrics_factor_final_kernel, dim3((unsigned)((n_scenes + 63) / 64)), dim3(64), 0, s, slab, state, n_scenes, p.n_blocks, mode,
+                       factor);
+    if (hipGetLastError() != hipSuccess) { *err = "metrics_factor: launch failed"; return 1; }
+    return 0;
+}
+
+}  // namespace m3r

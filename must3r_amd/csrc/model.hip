@@ -1637,6 +1637,34 @@ extern "C" int must3r_hip_export_scatter_faces(const must3r_hip_export_view* vie
     return 0;
 }
 
+extern "C" size_t must3r_hip_metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W) {
+    const char* err = nullptr;
+    const size_t b = metrics_loss_scratch_bytes(n_scenes, n_views, H, W, &err);
+    if (!b) fail("%s", err ? err : "metrics_loss: bad sizes");
+    return b;
+}
+
+extern "C" int must3r_hip_metrics_loss(const must3r_hip_metrics_loss_args* args, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* err = nullptr;
+    if (launch_metrics_loss(args, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
+extern "C" size_t must3r_hip_metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode) {
+    const char* err = nullptr;
+    const size_t b = metrics_factor_scratch_bytes(n_scenes, n_views, H, W, mode, &err);
+    if (!b) fail("%s", err ? err : "metrics_factor: bad sizes");
+    return b;
+}
+
+extern "C" int must3r_hip_metrics_factor(const float* pts, const float* trf, const uint8_t* valid, int n_scenes, int n_views, int H, int W,
+                                         int mode, float* factor, float* dist, void* scratch, size_t scratch_bytes, void* stream) {
+    const char* err = nullptr;
+    if (launch_metrics_factor(pts, trf, valid, n_scenes, n_views, H, W, mode, factor, dist, scratch, scratch_bytes,
+                              reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
 extern "C" int must3r_hip_resample_coeffs(int mode, int in_size, int out_size, int* ksize, int32_t* bounds, void* weights) {
     const char* err = nullptr;
     if (image_coeffs(mode, in_size, out_size, ksize, bounds, weights, &err)) return fail("%s", err);

@@ -418,3 +418,11 @@ def inference(encoder, decoder, imgs, true_shape, mem_batches, verbose=False, ma
         parts.append(pm.squeeze(1))
     pointmaps = torch.cat(parts)
     return pointmaps_0, pointmaps.view(B, n, *pointmaps.shape[1:])
+
+
+def concat_preds(out0, out):
+    """engine/inference.py:691-695: the first-pass results in front of the rendered ones, for every key both dicts hold."""
+    for k in out.keys():
+        if k in out0:
+            out[k] = torch.cat([out0[k], out[k]], dim=1)
+    return out

@@ -165,3 +165,49 @@ def make_retrieval_state_dict(dim, seed=0, prewhiten=True, postwhiten=True, hdim
             sd[f"projector.{3 * j + 1}.bias"] = 0.1 * torch.randn((h,), generator=g)
         d = h
     return sd
+
+
+class SyntheticScenes:
+    """Seeded scenes with ground truth in the reference's view format (what its dataset classes hand ``eval.py`` / the losses), for tests
+    and scripts/bench_metrics.py: a wavy depth field seen by ``n_views`` cameras on a small arc, world points = camera pose applied to the
+    back-projected depth.  ``dataset[i]`` is a list of ``n_views`` dicts: ``img`` fp32 [3,H,W] in [-1,1], ``true_shape`` int32 [2],
+    ``camera_pose`` fp32 [4,4] (camera to world), ``pts3d`` fp32 [H,W,3] (world; NaN where invalid, as datasets mark it), ``valid_mask``
+    bool [H,W], ``sky_mask`` bool [H,W], ``is_metric_scale`` bool.  ``invalid_frac`` of the pixels is invalid, the upper rows of them sky."""
+
+    def __init__(self, n_scenes, n_views, H, W, seed=0, invalid_frac=0.15, focal=None):
+        self.n_scenes, self.n_views, self.H, self.W, self.seed = int(n_scenes), int(n_views), int(H), int(W), int(seed)
+        self.invalid_frac = float(invalid_frac)
+        self.focal = float(focal) if focal is not None else 0.9 * max(H, W)
+
+    def set_epoch(self, epoch):
+        pass
+
+    def __len__(self):
+        return self.n_scenes
+
+    def __getitem__(self, idx):
+        if not 0 <= idx < self.n_scenes:
+            raise IndexError(idx)
+        g = torch.Generator().manual_seed(self.seed * 100003 + idx)
+        H, W, f = self.H, self.W, self.focal
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+        phase = torch.rand((3,), generator=g) * 6.2831853
+        views = []
+        for v in range(self.n_views):
+            ang = 0.08 * v + 0.02 * float(torch.randn((), generator=g))
+            c, s = math.cos(ang), math.sin(ang)
+            pose = torch.eye(4)
+            pose[:3, :3] = torch.tensor([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
+            pose[:3, 3] = torch.tensor([0.25 * v, 0.03 * v, 0.0]) + 0.02 * torch.randn((3,), generator=g)
+            z = 3.0 + 0.5 * torch.sin(xs / W * 5.0 + phase[0] + 0.3 * v) + 0.3 * torch.cos(ys / H * 4.0 + phase[1]) \
+                + 0.02 * torch.randn((H, W), generator=g)
+            local = torch.stack(((xs - W / 2) / f * z, (ys - H / 2) / f * z, z), dim=-1)
+            world = local @ pose[:3, :3].T + pose[:3, 3]
+            valid = torch.rand((H, W), generator=g) >= self.invalid_frac
+            sky = ~valid & (ys < H / 4)
+            world = torch.where(valid[..., None], world, torch.full_like(world, float("nan")))
+            shade = ((z - 2.2) / 1.6).clamp(0, 1) * 2 - 1
+            img = torch.stack((shade, torch.sin(xs / 7.0 + phase[2]) * 0.5, torch.cos(ys / 5.0) * 0.5), dim=0)
+            views.append(dict(img=img.contiguous(), true_shape=torch.tensor([H, W], dtype=torch.int32), camera_pose=pose,
+                              pts3d=world.contiguous(), valid_mask=valid, sky_mask=sky, is_metric_scale=torch.tensor(True)))
+        return views
