@@ -22,31 +22,6 @@ NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
 
-# every symbol include/must3r_hip.h declares
-EXPORTS = (
-    "must3r_hip_abi_version", "must3r_hip_last_error", "must3r_hip_create", "must3r_hip_destroy",
-    "must3r_hip_load_weight", "must3r_hip_finalize_weights", "must3r_hip_encode", "must3r_hip_decode",
-    "must3r_hip_postprocess", "must3r_hip_op_gemm", "must3r_hip_rope_table", "must3r_hip_op_attention",
-    "must3r_hip_op_layernorm", "must3r_hip_op_im2col", "must3r_hip_op_cast", "must3r_hip_set_profiling",
-    "must3r_hip_get_profile", "must3r_hip_debug_tr_probe", "must3r_hip_attention_scratch_bytes",
-    "must3r_hip_postprocess_cam", "must3r_hip_postprocess_cam_scratch_bytes",
-    "must3r_hip_nn_query", "must3r_hip_quadrant_ids",
-    "must3r_hip_affine", "must3r_hip_row_norm", "must3r_hip_l2_normalize", "must3r_hip_layernorm_act_f32", "must3r_hip_topk_gather", "must3r_hip_weighted_spoc",
-    "must3r_hip_op_gemm_lnfold",
-    "must3r_hip_postprocess_act", "must3r_hip_postprocess_cam_act",
-    "must3r_hip_op_sparse24_pack", "must3r_hip_op_gemm_sp",
-    "must3r_hip_set_option", "must3r_hip_cp_slot_bytes", "must3r_hip_cp_slot_bytes16", "must3r_hip_op_gemm_fold256", "must3r_hip_has_fp8_attention",
-    "must3r_hip_resample_coeffs", "must3r_hip_image_scratch_bytes", "must3r_hip_resample",
-    "must3r_hip_op_attention_ex",
-    "must3r_hip_asmk_centroid_sqnorm", "must3r_hip_asmk_quantize_scratch_bytes", "must3r_hip_asmk_quantize", "must3r_hip_asmk_aggregate",
-    "must3r_hip_asmk_scores",
-    "must3r_hip_nn_index_bytes", "must3r_hip_nn_index_scratch_bytes", "must3r_hip_nn_index_build", "must3r_hip_nn_index_query",
-    "must3r_hip_export_scratch_bytes", "must3r_hip_export_count", "must3r_hip_export_scatter_points", "must3r_hip_export_vertices",
-    "must3r_hip_export_scatter_faces",
-    "must3r_hip_metrics_loss_scratch_bytes", "must3r_hip_metrics_loss", "must3r_hip_metrics_factor_scratch_bytes", "must3r_hip_metrics_factor",
-)
-
-
 class Config(C.Structure):
     _fields_ = [("img_size", C.c_int32), ("patch_size", C.c_int32),
                 ("enc_dim", C.c_int32), ("enc_depth", C.c_int32), ("enc_heads", C.c_int32),
@@ -118,6 +93,74 @@ class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
 
+# every symbol include/must3r_hip.h declares, in its order: name -> (restype, argtypes)
+vp, i32, i64, fp, sz, cstr, P = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_char_p, C.POINTER
+PROTOTYPES = {
+    "must3r_hip_last_error": (cstr, []),
+    "must3r_hip_has_fp8_attention": (i32, []),
+    "must3r_hip_abi_version": (i32, []),
+    "must3r_hip_set_option": (i32, [cstr, i64]),
+    "must3r_hip_create": (i32, [P(Config), i32, P(vp)]),
+    "must3r_hip_destroy": (None, [vp]),
+    "must3r_hip_load_weight": (i32, [vp, cstr, vp, i32, i32, P(i64)]),
+    "must3r_hip_finalize_weights": (i32, [vp, i32]),
+    "must3r_hip_encode": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+    "must3r_hip_cp_slot_bytes": (sz, [vp, i32]),
+    "must3r_hip_cp_slot_bytes16": (sz, [vp, i32]),
+    "must3r_hip_decode": (i32, [vp, P(DecodeArgs), vp]),
+    "must3r_hip_postprocess": (i32, [vp, vp, vp, vp, sz, vp]),
+    "must3r_hip_postprocess_act": (i32, [vp, i32, vp, vp, vp, sz, vp]),
+    "must3r_hip_postprocess_cam_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_postprocess_cam": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "must3r_hip_postprocess_cam_act": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "must3r_hip_affine": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
+    "must3r_hip_row_norm": (i32, [vp, i32, i32, vp, vp]),
+    "must3r_hip_l2_normalize": (i32, [vp, i64, i32, i64, vp, vp]),
+    "must3r_hip_layernorm_act_f32": (i32, [vp, vp, vp, fp, i32, i32, i32, vp, vp]),
+    "must3r_hip_topk_gather": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "must3r_hip_weighted_spoc": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "must3r_hip_asmk_quantize_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_asmk_centroid_sqnorm": (i32, [vp, i32, i32, vp, vp]),
+    "must3r_hip_asmk_quantize": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, sz, vp]),
+    "must3r_hip_asmk_aggregate": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
+    "must3r_hip_asmk_scores": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, fp, fp, i32, vp, vp]),
+    "must3r_hip_nn_query": (i32, [vp, i64, vp, i64, vp, vp]),
+    "must3r_hip_quadrant_ids": (i32, [vp, i64, P(fp), i32, vp, vp]),
+    "must3r_hip_nn_index_bytes": (sz, [i64, i32]),
+    "must3r_hip_nn_index_scratch_bytes": (sz, [i64]),
+    "must3r_hip_nn_index_build": (i32, [vp, vp, i64, i32, vp, vp, vp]),
+    "must3r_hip_nn_index_query": (i32, [vp, vp, i64, P(fp), i32, vp, vp]),
+    "must3r_hip_export_scratch_bytes": (sz, [P(ExportView), i32, i32, i32]),
+    "must3r_hip_export_count": (i32, [P(ExportView), i32, P(fp), i32, i32, vp, sz, P(i64), vp]),
+    "must3r_hip_export_scatter_points": (i32, [P(ExportView), i32, P(fp), i32, i32, i32, vp, vp, vp, vp, vp]),
+    "must3r_hip_export_vertices": (i32, [P(ExportView), i32, i32, vp, vp, vp, vp, vp]),
+    "must3r_hip_export_scatter_faces": (i32, [P(ExportView), i32, P(fp), i32, i32, vp, vp, vp]),
+    "must3r_hip_metrics_loss_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_metrics_loss": (i32, [P(MetricsLossArgs), vp, sz, vp]),
+    "must3r_hip_metrics_factor_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "must3r_hip_metrics_factor": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "must3r_hip_resample_coeffs": (i32, [i32, i32, i32, P(i32), vp, vp]),
+    "must3r_hip_image_scratch_bytes": (sz, [i32, P(ImageDesc), i32]),
+    "must3r_hip_resample": (i32, [i32, P(ImageDesc), i32, vp, vp, sz, vp]),
+    "must3r_hip_op_gemm": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "must3r_hip_op_sparse24_pack": (i32, [vp, i32, i32, vp, vp, vp]),
+    "must3r_hip_op_gemm_sp": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
+    "must3r_hip_op_gemm_lnfold": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, fp, vp, i32, vp, vp, i32, i32, fp, i32, vp]),
+    "must3r_hip_op_gemm_fold256": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, fp, vp, vp, vp, i32, i32, fp, i32, vp]),
+    "must3r_hip_rope_table": (i32, [fp, fp, i32, vp]),
+    "must3r_hip_attention_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_op_attention": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp]),
+    "must3r_hip_op_attention_ex": (i32, [P(AttnOp), vp]),
+    "must3r_hip_op_layernorm": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, fp, vp]),
+    "must3r_hip_op_im2col": (i32, [i32, vp, vp, i32, i32, i32, vp]),
+    "must3r_hip_op_cast": (i32, [i32, vp, vp, vp, sz, vp]),
+    "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
+    "must3r_hip_set_profiling": (i32, [vp, i32]),
+    "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),
+}
+EXPORTS = tuple(PROTOTYPES)
+
+
 class HipError(RuntimeError):
     pass
 
@@ -135,90 +178,19 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(make -C must3r_amd/csrc). must3r_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    vp, i32, i64p, fp = C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_float
-    lib.must3r_hip_abi_version.restype = i32
-    lib.must3r_hip_last_error.restype = C.c_char_p
-    lib.must3r_hip_create.argtypes = [C.POINTER(Config), i32, C.POINTER(vp)]
-    lib.must3r_hip_destroy.argtypes = [vp]
-    lib.must3r_hip_destroy.restype = None
-    lib.must3r_hip_load_weight.argtypes = [vp, C.c_char_p, vp, i32, i32, i64p]
-    lib.must3r_hip_finalize_weights.argtypes = [vp, i32]
-    lib.must3r_hip_encode.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, vp]
-    lib.must3r_hip_decode.argtypes = [vp, C.POINTER(DecodeArgs), vp]
-    lib.must3r_hip_postprocess.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_postprocess_act.argtypes = [vp, i32, vp, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_op_gemm.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32,
-                                       vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.must3r_hip_rope_table.argtypes = [fp, fp, i32, vp]
-    lib.must3r_hip_op_attention.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp]
-    lib.must3r_hip_op_attention_ex.argtypes = [C.POINTER(AttnOp), vp]
-    lib.must3r_hip_attention_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.must3r_hip_attention_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_op_layernorm.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, fp, vp]
-    lib.must3r_hip_op_gemm_lnfold.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, fp, vp, i32, vp, vp, i32, i32, fp, i32, vp]
-    lib.must3r_hip_op_gemm_fold256.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, fp, vp, vp, vp, i32, i32, fp, i32, vp]
-    lib.must3r_hip_op_sparse24_pack.argtypes = [vp, i32, i32, vp, vp, vp]
-    lib.must3r_hip_op_gemm_sp.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp]
-    lib.must3r_hip_op_im2col.argtypes = [i32, vp, vp, i32, i32, i32, vp]
-    lib.must3r_hip_op_cast.argtypes = [i32, vp, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_debug_tr_probe.argtypes = [vp, vp]
-    lib.must3r_hip_set_profiling.argtypes = [vp, i32]
-    lib.must3r_hip_postprocess_cam.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_postprocess_cam_act.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_affine.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp]
-    lib.must3r_hip_row_norm.argtypes = [vp, i32, i32, vp, vp]
-    lib.must3r_hip_l2_normalize.argtypes = [vp, C.c_int64, i32, C.c_int64, vp, vp]
-    lib.must3r_hip_layernorm_act_f32.argtypes = [vp, vp, vp, fp, i32, i32, i32, vp, vp]
-    lib.must3r_hip_topk_gather.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.must3r_hip_weighted_spoc.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    lib.must3r_hip_nn_query.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
-    lib.must3r_hip_quadrant_ids.argtypes = [vp, C.c_int64, C.POINTER(C.c_float), i32, vp, vp]
-    lib.must3r_hip_nn_index_bytes.argtypes = [C.c_int64, i32]
-    lib.must3r_hip_nn_index_bytes.restype = C.c_size_t
-    lib.must3r_hip_nn_index_scratch_bytes.argtypes = [C.c_int64]
-    lib.must3r_hip_nn_index_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_nn_index_build.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp]
-    lib.must3r_hip_nn_index_query.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_float), i32, vp, vp]
-    evp = C.POINTER(ExportView)
-    lib.must3r_hip_export_scratch_bytes.argtypes = [evp, i32, i32, i32]
-    lib.must3r_hip_export_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_export_count.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, vp, C.c_size_t, i64p, vp]
-    lib.must3r_hip_export_scatter_points.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.must3r_hip_export_vertices.argtypes = [evp, i32, i32, vp, vp, vp, vp, vp]
-    lib.must3r_hip_export_scatter_faces.argtypes = [evp, i32, C.POINTER(C.c_float), i32, i32, vp, vp, vp]
-    lib.must3r_hip_metrics_loss_scratch_bytes.argtypes = [i32, i32, i32, i32]
-    lib.must3r_hip_metrics_loss_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_metrics_loss.argtypes = [C.POINTER(MetricsLossArgs), vp, C.c_size_t, vp]
-    lib.must3r_hip_metrics_factor_scratch_bytes.argtypes = [i32, i32, i32, i32, i32]
-    lib.must3r_hip_metrics_factor_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_metrics_factor.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_postprocess_cam_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.must3r_hip_postprocess_cam_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_get_profile.argtypes = [vp, C.POINTER(ProfRecord), i32, i32]
-    lib.must3r_hip_set_option.argtypes = [C.c_char_p, C.c_longlong]
-    lib.must3r_hip_cp_slot_bytes.argtypes = [vp, i32]
-    lib.must3r_hip_cp_slot_bytes.restype = C.c_size_t
-    lib.must3r_hip_cp_slot_bytes16.argtypes = [vp, i32]
-    lib.must3r_hip_cp_slot_bytes16.restype = C.c_size_t
-    lib.must3r_hip_resample_coeffs.argtypes = [i32, i32, i32, C.POINTER(C.c_int), vp, vp]
-    lib.must3r_hip_image_scratch_bytes.argtypes = [i32, C.POINTER(ImageDesc), i32]
-    lib.must3r_hip_image_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_resample.argtypes = [i32, C.POINTER(ImageDesc), i32, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_asmk_centroid_sqnorm.argtypes = [vp, i32, i32, vp, vp]
-    lib.must3r_hip_asmk_quantize_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.must3r_hip_asmk_quantize_scratch_bytes.restype = C.c_size_t
-    lib.must3r_hip_asmk_quantize.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, vp, C.c_size_t, vp]
-    lib.must3r_hip_asmk_aggregate.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
-    lib.must3r_hip_asmk_scores.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, fp, fp, i32, vp, vp]
-    for name in EXPORTS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(lib, name)
-        if fn.restype is C.c_int and name not in ("must3r_hip_abi_version", "must3r_hip_attention_scratch_bytes",
-                                                    "must3r_hip_postprocess_cam_scratch_bytes", "must3r_hip_cp_slot_bytes"):
-            fn.restype = i32
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.must3r_hip_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.must3r_hip_abi_version()} != {ABI_VERSION}; rebuild")
     _lib = lib
     return lib
+
+
+def stream_ptr(device):
+    """Handle of the current stream of ``device``, as the ``stream`` arguments of the library take it."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 def check(rc):

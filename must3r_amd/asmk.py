@@ -124,10 +124,6 @@ def load_codebook(path, nclusters=None, device="cuda"):
     return t
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _cuda_f32(x, what):
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise RuntimeError(f"must3r_amd.asmk: {what} must be a CUDA tensor; the HIP path has no CPU fallback")
@@ -145,7 +141,7 @@ def centroid_sqnorm(codebook, refresh=False):
     K, D = c.shape
     out = torch.empty((K,), dtype=torch.float32, device=c.device)
     with torch.cuda.device(c.device):
-        _lib.check(_lib.load().must3r_hip_asmk_centroid_sqnorm(c.data_ptr(), K, D, out.data_ptr(), _stream(c)))
+        _lib.check(_lib.load().must3r_hip_asmk_centroid_sqnorm(c.data_ptr(), K, D, out.data_ptr(), _lib.stream_ptr(c.device)))
     codebook._asmk_sqnorm = (codebook._version, out)
     return out
 
@@ -164,7 +160,7 @@ def quantize(feat, codebook, k, c_sqnorm=None):
         nbytes = lib.must3r_hip_asmk_quantize_scratch_bytes(M, K, k)
         scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=x.device)
         _lib.check(lib.must3r_hip_asmk_quantize(x.data_ptr(), M, c.data_ptr(), csq.data_ptr(), K, D, k, ids.data_ptr(), scratch.data_ptr(),
-                                                nbytes, _stream(x)))
+                                                nbytes, _lib.stream_ptr(x.device)))
     return ids
 
 
@@ -200,7 +196,7 @@ def aggregate(feat, codebook, ids, offsets, k_use):
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().must3r_hip_asmk_aggregate(x.data_ptr(), c.data_ptr(), K, D, ids.data_ptr(), ids.shape[1], k_use,
                                                          off_dev.data_ptr(), n, rows, words.data_ptr(), bits.data_ptr(), counts.data_ptr(),
-                                                         _stream(x)))
+                                                         _lib.stream_ptr(x.device)))
     bad = torch.nonzero(counts < 0).flatten()
     if bad.numel():   # the kernel refused these images before reading any centroid row through their ids
         raise ValueError(f"aggregate: images {bad.tolist()[:8]} have centroid ids outside [0, {K})")
@@ -218,7 +214,7 @@ def scores_from_aggregates(query, database, offsets, k_query, k_db, D, alpha=3.0
         _lib.check(_lib.load().must3r_hip_asmk_scores(wq.data_ptr(), bq.data_ptr(), cq.data_ptr(), off_dev.data_ptr(), k_query, n,
                                                       wd.data_ptr(), bd.data_ptr(), cd.data_ptr(), off_dev.data_ptr(), k_db, n, D,
                                                       float(alpha), float(similarity_threshold), 1 if normalize else 0, out.data_ptr(),
-                                                      torch.cuda.current_stream(dev).cuda_stream))
+                                                      _lib.stream_ptr(dev)))
     return out
 
 

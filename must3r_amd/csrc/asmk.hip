@@ -18,8 +18,8 @@
 //                           database word in the query's list in LDS), h = popcount(xor), s = 1 - 2h/D, sigma = s^alpha if
 //                           s >= tau else 0 in fp32, summed in fp64 in ascending word order, then / sqrt(|W_d|) / sqrt(|W_q|).
 // No atomics: every output element has one writer and a fixed order of operations.
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
 
 namespace m3r {
 
@@ -327,17 +327,22 @@ static void quant_plan(int M, int K, int* tiles_per_split, int* S) {
     *S = (n_tiles + *tiles_per_split - 1) / *tiles_per_split;
 }
 
-size_t asmk_quantize_scratch_bytes(int M, int K, int k) {
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" size_t must3r_hip_asmk_quantize_scratch_bytes(int M, int K, int k) {
     if (M <= 0 || K <= 0 || k <= 0) return 0;
     int tps, S;
     quant_plan(M, K, &tps, &S);
     return (size_t)S * M * k * (sizeof(float) + sizeof(int));
 }
 
-int launch_asmk_sqnorm(const float* C, int K, int D, float* out, hipStream_t s, const char** err) {
-    if (K <= 0) return 0;
-    hipLaunchKernelGGL(csq_kernel, dim3((K + 3) / 4), dim3(256), 0, s, C, K, D, out);
-    if (hipGetLastError() != hipSuccess) { *err = "asmk_centroid_sqnorm: launch failed"; return 1; }
+extern "C" int must3r_hip_asmk_centroid_sqnorm(const float* C, int K, int D, float* out, void* stream) {
+    if (K < 0 || D <= 0) return fail("asmk_centroid_sqnorm: bad shape");
+    if (K == 0) return 0;
+    if (!C || !out) return fail("asmk_centroid_sqnorm: null argument");
+    hipLaunchKernelGGL(csq_kernel, dim3((K + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), C, K, D, out);
+    if (hipGetLastError() != hipSuccess) return fail("asmk_centroid_sqnorm: launch failed");
     return 0;
 }
 
@@ -348,18 +353,21 @@ static void launch_quant_k(const float* X, int M, const float* C, const float* c
     hipLaunchKernelGGL(quantize_merge_kernel<KK>, dim3((M + 255) / 256), dim3(256), 0, s, pd, pi, M, S, ids);
 }
 
-int launch_asmk_quantize(const float* X, int M, const float* C, const float* csq, int K, int D, int k, int* ids, void* scratch,
-                         size_t scratch_bytes, hipStream_t s, const char** err) {
-    if (M <= 0) return 0;
-    if (D <= 0 || D % 64) { *err = "asmk_quantize: D must be a positive multiple of 64"; return 1; }
-    if (k < 1 || k > 8) { *err = "asmk_quantize: k must be in [1, 8]"; return 1; }
-    if (k > K) { *err = "asmk_quantize: k exceeds the number of centroids"; return 1; }
-    if (((size_t)X | (size_t)C) & 15) { *err = "asmk_quantize: feat and centroids must be 16-byte aligned"; return 1; }
-    if (!scratch || scratch_bytes < asmk_quantize_scratch_bytes(M, K, k)) { *err = "asmk_quantize: scratch too small"; return 1; }
+extern "C" int must3r_hip_asmk_quantize(const float* X, int M, const float* C, const float* csq, int K, int D, int k, int32_t* ids, void* scratch,
+                                        size_t scratch_bytes, void* stream) {
+    if (M < 0 || K <= 0 || D <= 0) return fail("asmk_quantize: bad shape");
+    if (M == 0) return 0;
+    if (!X || !C || !csq || !ids) return fail("asmk_quantize: null argument");
+    if (D <= 0 || D % 64) return fail("asmk_quantize: D must be a positive multiple of 64");
+    if (k < 1 || k > 8) return fail("asmk_quantize: k must be in [1, 8]");
+    if (k > K) return fail("asmk_quantize: k exceeds the number of centroids");
+    if (((size_t)X | (size_t)C) & 15) return fail("asmk_quantize: feat and centroids must be 16-byte aligned");
+    if (!scratch || scratch_bytes < must3r_hip_asmk_quantize_scratch_bytes(M, K, k)) return fail("asmk_quantize: scratch too small");
     int tps, S;
     quant_plan(M, K, &tps, &S);
     float* pd = reinterpret_cast<float*>(scratch);
     int* pi = reinterpret_cast<int*>(pd + (size_t)S * M * k);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (k) {
         case 1: launch_quant_k<1>(X, M, C, csq, K, D, tps, S, pd, pi, ids, s); break;
         case 2: launch_quant_k<2>(X, M, C, csq, K, D, tps, S, pd, pi, ids, s); break;
@@ -370,35 +378,36 @@ int launch_asmk_quantize(const float* X, int M, const float* C, const float* csq
         case 7: launch_quant_k<7>(X, M, C, csq, K, D, tps, S, pd, pi, ids, s); break;
         default: launch_quant_k<8>(X, M, C, csq, K, D, tps, S, pd, pi, ids, s); break;
     }
-    if (hipGetLastError() != hipSuccess) { *err = "asmk_quantize: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("asmk_quantize: launch failed");
     return 0;
 }
 
-int launch_asmk_aggregate(const float* X, const float* C, int K, int D, const int* ids, int k_ids, int k_use, const int* offsets, int n_images,
-                          int max_rows, int* words, unsigned* bits, int* counts, hipStream_t s, const char** err) {
-    if (n_images <= 0) return 0;
-    if (D <= 0 || D % 64) { *err = "asmk_aggregate: D must be a positive multiple of 64"; return 1; }
-    if (K <= 0) { *err = "asmk_aggregate: the codebook must have at least one centroid"; return 1; }
-    if (k_use < 1 || k_use > k_ids) { *err = "asmk_aggregate: k_use must be in [1, k_ids]"; return 1; }
-    if (max_rows < 0 || (long long)max_rows * k_use > AGG_MAX_PAIRS) {
-        *err = "asmk_aggregate: an image has more (word, row) pairs than the per-image LDS sort holds (rows * k_use <= 4096)";
-        return 1;
-    }
-    hipLaunchKernelGGL(aggregate_kernel, dim3(n_images), dim3(1024), 0, s, X, C, K, D, ids, k_ids, k_use, offsets, words, bits, counts);
-    if (hipGetLastError() != hipSuccess) { *err = "asmk_aggregate: launch failed"; return 1; }
+extern "C" int must3r_hip_asmk_aggregate(const float* X, const float* C, int K, int D, const int32_t* ids, int k_ids, int k_use,
+                                         const int32_t* offsets, int n_images, int max_rows, int32_t* words, uint32_t* bits, int32_t* counts,
+                                         void* stream) {
+    if (n_images < 0 || K <= 0 || D <= 0) return fail("asmk_aggregate: bad shape");
+    if (n_images == 0) return 0;
+    if (!X || !C || !ids || !offsets || !words || !bits || !counts) return fail("asmk_aggregate: null argument");
+    if (D <= 0 || D % 64) return fail("asmk_aggregate: D must be a positive multiple of 64");
+    if (k_use < 1 || k_use > k_ids) return fail("asmk_aggregate: k_use must be in [1, k_ids]");
+    if (max_rows < 0 || (long long)max_rows * k_use > AGG_MAX_PAIRS)
+        return fail("asmk_aggregate: an image has more (word, row) pairs than the per-image LDS sort holds (rows * k_use <= 4096)");
+    hipLaunchKernelGGL(aggregate_kernel, dim3(n_images), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), X, C, K, D, ids, k_ids, k_use,
+                       offsets, words, bits, counts);
+    if (hipGetLastError() != hipSuccess) return fail("asmk_aggregate: launch failed");
     return 0;
 }
 
-int launch_asmk_scores(const int* wq, const unsigned* bq, const int* cq, const int* oq, int kq, int n_q, const int* wd, const unsigned* bd,
-                       const int* cd, const int* od, int kd, int n_d, int D, float alpha, float tau, int normalize, double* out,
-                       hipStream_t s, const char** err) {
-    if (n_q <= 0 || n_d <= 0) return 0;
-    if (D <= 0 || D % 64) { *err = "asmk_scores: D must be a positive multiple of 64"; return 1; }
+extern "C" int must3r_hip_asmk_scores(const int32_t* wq, const uint32_t* bq, const int32_t* cq, const int32_t* oq, int kq, int n_q,
+                                      const int32_t* wd, const uint32_t* bd, const int32_t* cd, const int32_t* od, int kd, int n_d, int D,
+                                      float alpha, float tau, int normalize, double* out, void* stream) {
+    if (n_q < 0 || n_d < 0 || D <= 0 || kq < 1 || kd < 1) return fail("asmk_scores: bad shape");
+    if (n_q == 0 || n_d == 0) return 0;
+    if (!wq || !bq || !cq || !oq || !wd || !bd || !cd || !od || !out) return fail("asmk_scores: null argument");
+    if (D <= 0 || D % 64) return fail("asmk_scores: D must be a positive multiple of 64");
     const int slices = max(1, min(64, (n_d + 31) / 32));   // up to 32 database images per block
-    hipLaunchKernelGGL(scores_kernel, dim3(n_q, slices), dim3(256), 0, s, wq, bq, cq, oq, kq, wd, bd, cd, od, kd, n_d, D, alpha, tau,
-                       normalize, out);
-    if (hipGetLastError() != hipSuccess) { *err = "asmk_scores: launch failed"; return 1; }
+    hipLaunchKernelGGL(scores_kernel, dim3(n_q, slices), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), wq, bq, cq, oq, kq, wd, bd, cd, od, kd,
+                       n_d, D, alpha, tau, normalize, out);
+    if (hipGetLastError() != hipSuccess) return fail("asmk_scores: launch failed");
     return 0;
 }
-
-}  // namespace m3r

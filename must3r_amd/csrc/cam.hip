@@ -13,8 +13,8 @@
 // per-pixel terms are the reference's fp32 expressions.  The 3x3 Procrustes problem is solved by one thread per view
 // with Horn's quaternion form (largest eigenvector of a 4x4 symmetric matrix, cyclic Jacobi in fp64), which equals
 // U diag(1,1,det(UV^T)) V^T of the SVD form without the sign case analysis.
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
 
 namespace m3r {
 
@@ -333,7 +333,11 @@ __global__ void __launch_bounds__(CAM_T) cam_kernel(const CamArgs p) {
     if (g == 0 && threadIdx.x == 0) p.sums[v] = (double)focal;
 }
 
-size_t cam_scratch_bytes(int n_views, int H, int W) {
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" size_t must3r_hip_postprocess_cam_scratch_bytes(int n_views, int H, int W) {
+    if (n_views <= 0 || H <= 0 || W <= 0) return 0;
     const int P = H * W;
     const int gmax = (P + CAM_T - 1) / CAM_T;
     // partials sized for the largest G any launch can pick, + one counter per view
@@ -341,29 +345,31 @@ size_t cam_scratch_bytes(int n_views, int H, int W) {
     return (size_t)n_views * gmax * (3 * 16 + 16 * 8) + (size_t)n_views * 8 + 256;
 }
 
-int launch_postprocess_cam(const float* pm, int linear, int n_views, int H, int W, float* p3, float* pl, float* cf, float* focal,
-                           float* c2w, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err) {
-    if (n_views <= 0) return 0;
+extern "C" int must3r_hip_postprocess_cam_act(const float* pm, int activation, int n_views, int H, int W, float* p3, float* pl, float* cf,
+                                              float* focal, float* c2w, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n_views < 0 || H <= 0 || W <= 0) return fail("postprocess_cam: bad shape");
+    if (activation != MUST3R_ACT_NORM_EXP && activation != MUST3R_ACT_LINEAR) return fail("postprocess_cam: unknown activation %d", activation);
+    if (n_views == 0) return 0;
+    if (!pm || !p3 || !pl || !cf || !focal || !c2w || !scratch) return fail("postprocess_cam: null argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int P = H * W;
-    if (P <= 0) { *err = "postprocess_cam: empty image"; return 1; }
-    if (scratch_bytes < cam_scratch_bytes(n_views, H, W)) { *err = "postprocess_cam: scratch too small"; return 1; }
+    if (P <= 0) return fail("postprocess_cam: empty image");
+    if (scratch_bytes < must3r_hip_postprocess_cam_scratch_bytes(n_views, H, W)) return fail("postprocess_cam: scratch too small");
     int dev = 0, ncu = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cam_kernel, CAM_T, 0) != hipSuccess || per_cu < 1) {
-        *err = "postprocess_cam: occupancy query failed";
-        return 1;
-    }
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cam_kernel, CAM_T, 0) != hipSuccess || per_cu < 1)
+        return fail("postprocess_cam: occupancy query failed");
     const int slots = ncu * per_cu;                                   // blocks that can be resident together
     const int gmin = (P + CAM_T * CAM_PPT - 1) / (CAM_T * CAM_PPT);   // fewest blocks per view (register cache bound)
     const int gmax = (P + CAM_T - 1) / CAM_T;
-    if (gmin > slots) { *err = "postprocess_cam: image too large for the per-view register cache"; return 1; }
+    if (gmin > slots) return fail("postprocess_cam: image too large for the per-view register cache");
     const int vmax = slots / gmin;                                    // views per launch
     // scratch: [slots | partial | focal]; the slots must read all-ones (the "not yet published" sentinel)
     const size_t slot_bytes = (size_t)n_views * 3 * gmax * 16;
     dbl2* slot_base = reinterpret_cast<dbl2*>(scratch);
     double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + slot_bytes);
     double* sums = partial + (size_t)n_views * gmax * 16;
-    if (hipMemsetAsync(slot_base, 0xFF, slot_bytes, s) != hipSuccess) { *err = "postprocess_cam: memset failed"; return 1; }
+    if (hipMemsetAsync(slot_base, 0xFF, slot_bytes, s) != hipSuccess) return fail("postprocess_cam: memset failed");
     for (int v0 = 0; v0 < n_views; v0 += vmax) {
         const int nv = (n_views - v0 < vmax) ? n_views - v0 : vmax;
         int G = slots / nv;
@@ -380,18 +386,20 @@ int launch_postprocess_cam(const float* pm, int linear, int n_views, int H, int 
         a.sums = sums + v0;
         a.partial = partial + (size_t)v0 * gmax * 16;
         a.slots = slot_base + (size_t)v0 * 3 * gmax;
-        a.V = nv; a.G = G; a.H = H; a.W = W; a.linear = linear ? 1 : 0;
+        a.V = nv; a.G = G; a.H = H; a.W = W; a.linear = activation == MUST3R_ACT_LINEAR;
         a.ppt = (P + G * CAM_T - 1) / (G * CAM_T);
         void* args[] = {&a};
         if (hipLaunchCooperativeKernel(reinterpret_cast<const void*>(cam_kernel), dim3(nv * G), dim3(CAM_T), args, 0, s) != hipSuccess) {
             (void)hipGetLastError();
-            *err = "postprocess_cam: cooperative launch failed";
-            return 1;
+            return fail("postprocess_cam: cooperative launch failed");
         }
         hipLaunchKernelGGL(cam_solve_kernel, dim3(nv), dim3(64), 0, s, a.partial, a.sums, G, focal + v0, c2w + (size_t)v0 * 16);
-        if (hipGetLastError() != hipSuccess) { *err = "postprocess_cam: solve launch failed"; return 1; }
+        if (hipGetLastError() != hipSuccess) return fail("postprocess_cam: solve launch failed");
     }
     return 0;
 }
 
-}  // namespace m3r
+extern "C" int must3r_hip_postprocess_cam(const float* pm, int n_views, int H, int W, float* p3, float* pl, float* cf, float* focal, float* c2w,
+                                          void* scratch, size_t scratch_bytes, void* stream) {
+    return must3r_hip_postprocess_cam_act(pm, MUST3R_ACT_NORM_EXP, n_views, H, W, p3, pl, cf, focal, c2w, scratch, scratch_bytes, stream);
+}

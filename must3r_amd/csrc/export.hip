@@ -18,9 +18,8 @@
 // uint32][totals channels x int64][partials n_blocks x 6 float].
 #include <vector>
 #include <cstdint>
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
-#include "../../include/must3r_hip.h"
 
 namespace m3r {
 namespace {
@@ -380,19 +379,19 @@ __global__ void __launch_bounds__(EXP_T) export_faces_kernel(const ExpView* __re
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // validates the table and lays the scratch out; 0 = fine
-int export_plan(const must3r_hip_export_view* views, int n_views, int n_thr, int mesh, ExpPlan* p, const char** err) {
-    if (!views) { *err = "export: null view table"; return 1; }
-    if (n_views <= 0) { *err = "export: the view table is empty"; return 1; }
-    if (n_thr < 1 || n_thr > EXP_MAXK) { *err = "export: the number of thresholds is outside [1, 8]"; return 1; }
+int export_plan(const must3r_hip_export_view* views, int n_views, int n_thr, int mesh, ExpPlan* p) {
+    if (!views) return fail("export: null view table");
+    if (n_views <= 0) return fail("export: the view table is empty");
+    if (n_thr < 1 || n_thr > EXP_MAXK) return fail("export: the number of thresholds is outside [1, 8]");
     long long blocks = 0, pix = 0;
     for (int i = 0; i < n_views; ++i) {
         const must3r_hip_export_view& v = views[i];
-        if (v.H <= 0 || v.W <= 0) { *err = "export: a view has a non-positive size"; return 1; }
+        if (v.H <= 0 || v.W <= 0) return fail("export: a view has a non-positive size");
         const long long n = (long long)v.H * v.W;
-        if (n >= (1LL << 31)) { *err = "export: a view has 2^31 or more pixels"; return 1; }
+        if (n >= (1LL << 31)) return fail("export: a view has 2^31 or more pixels");
         pix += n;
         blocks += (n + EXP_BLOCK - 1) / EXP_BLOCK;
-        if (pix >= (1LL << 32)) { *err = "export: the scene has 2^32 or more vertices (uint32 indices)"; return 1; }
+        if (pix >= (1LL << 32)) return fail("export: the scene has 2^32 or more vertices (uint32 indices)");
     }
     p->n_blocks = blocks;
     p->n_pix = pix;
@@ -408,27 +407,30 @@ int export_plan(const must3r_hip_export_view* views, int n_views, int n_thr, int
     return 0;
 }
 
-int check_pointers(const must3r_hip_export_view* views, int n_views, const char** err) {
+int check_pointers(const must3r_hip_export_view* views, int n_views) {
     for (int i = 0; i < n_views; ++i)
-        if (!views[i].conf || !views[i].pts || !views[i].rgb) { *err = "export: a view has a null plane"; return 1; }
+        if (!views[i].conf || !views[i].pts || !views[i].rgb) return fail("export: a view has a null plane");
     return 0;
 }
 
 }  // namespace
+}  // namespace m3r
+using namespace m3r;
 
-size_t export_scratch_bytes(const must3r_hip_export_view* views, int n_views, int n_thr, int mesh, const char** err) {
+extern "C" size_t must3r_hip_export_scratch_bytes(const must3r_hip_export_view* views, int n_views, int n_thr, int mesh) {
     ExpPlan p;
-    if (export_plan(views, n_views, n_thr, mesh, &p, err)) return 0;
+    if (export_plan(views, n_views, n_thr, mesh, &p)) return 0;
     return p.bytes;
 }
 
-int launch_export_count(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int mesh, void* scratch,
-                        size_t scratch_bytes, long long* totals_host, hipStream_t s, const char** err) {
+extern "C" int must3r_hip_export_count(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int mesh, void* scratch,
+                                       size_t scratch_bytes, int64_t* totals_host, void* stream) {
+    if (!totals_host) return fail("export_count: null argument");
     ExpPlan p;
-    if (export_plan(views, n_views, n_thr, mesh, &p, err)) return 1;
-    if (!thr || !scratch || !totals_host) { *err = "export_count: null argument"; return 1; }
-    if (check_pointers(views, n_views, err)) return 1;
-    if (scratch_bytes < p.bytes) { *err = "export_count: scratch too small"; return 1; }
+    if (export_plan(views, n_views, n_thr, mesh, &p)) return 1;
+    if (!thr || !scratch) return fail("export_count: null argument");
+    if (check_pointers(views, n_views)) return 1;
+    if (scratch_bytes < p.bytes) return fail("export_count: scratch too small");
     std::vector<ExpView> table((size_t)n_views);
     unsigned bb = 0;
     unsigned long long vb = 0;
@@ -442,70 +444,79 @@ int launch_export_count(const must3r_hip_export_view* views, int n_views, const 
         bb += (d.n_pix + EXP_BLOCK - 1) / EXP_BLOCK;
         vb += d.n_pix;
     }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* sc = reinterpret_cast<char*>(scratch);
     ExpView* dv = reinterpret_cast<ExpView*>(sc);
     unsigned* prefix = reinterpret_cast<unsigned*>(sc + p.off_prefix);
     long long* totals = reinterpret_cast<long long*>(sc + p.off_totals);
-    if (hipMemcpyAsync(dv, table.data(), table.size() * sizeof(ExpView), hipMemcpyHostToDevice, s) != hipSuccess) {
-        *err = "export_count: view table upload failed"; return 1;
-    }
+    if (hipMemcpyAsync(dv, table.data(), table.size() * sizeof(ExpView), hipMemcpyHostToDevice, s) != hipSuccess)
+        return fail("export_count: view table upload failed");
     ExpThr t;
     for (int k = 0; k < EXP_MAXK; ++k) t.v[k] = k < n_thr ? thr[k] : INFINITY;
     const long long stride = p.n_blocks + 1;
     if (mesh) hipLaunchKernelGGL(export_count_kernel<true>, dim3((unsigned)p.n_blocks), dim3(EXP_T), 0, s, dv, n_views, t, n_thr, prefix, stride);
     else hipLaunchKernelGGL(export_count_kernel<false>, dim3((unsigned)p.n_blocks), dim3(EXP_T), 0, s, dv, n_views, t, n_thr, prefix, stride);
     hipLaunchKernelGGL(export_scan_kernel, dim3(p.channels), dim3(1024), 0, s, prefix, stride, p.n_blocks, totals);
-    if (hipGetLastError() != hipSuccess) { *err = "export_count: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("export_count: launch failed");
     long long tot[2 * EXP_MAXK];
     // the table vector must outlive its upload: the stream is drained here, before it goes out of scope
     if (hipMemcpyAsync(tot, totals, (size_t)p.channels * sizeof(long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        *err = "export_count: reading the totals failed"; return 1;
-    }
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail("export_count: reading the totals failed");
     for (int k = 0; k < n_thr; ++k) totals_host[k] = mesh ? 2 * (tot[2 * k] + tot[2 * k + 1]) : tot[k];
     return 0;
 }
 
-int launch_export_points(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, int layout, int all,
-                         const void* scratch, void* out_pos, void* out_col, float* minmax, hipStream_t s, const char** err) {
+// the points that pass threshold k in either layout (all = 0), or every vertex of the mesh in the GLB layout (all = 1)
+static int launch_export_points(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, int layout, int all,
+                                const void* scratch, void* out_pos, void* out_col, float* minmax, void* stream) {
     ExpPlan p;
     const int mesh = all ? 1 : 0;
-    if (export_plan(views, n_views, n_thr, mesh, &p, err)) return 1;
-    if (!scratch || !out_pos || !minmax || (!all && !thr)) { *err = "export_scatter: null argument"; return 1; }
-    if (!all && (k < 0 || k >= n_thr)) { *err = "export_scatter: threshold index outside the count's"; return 1; }
-    if (layout != MUST3R_EXPORT_GLB && layout != MUST3R_EXPORT_PLY) { *err = "export_scatter: unknown layout"; return 1; }
-    if (layout == MUST3R_EXPORT_GLB && !out_col) { *err = "export_scatter: the GLB layout needs a colour plane"; return 1; }
-    if (layout == MUST3R_EXPORT_PLY && (reinterpret_cast<uintptr_t>(out_pos) & 15)) { *err = "export_scatter: PLY records must be 16-byte aligned"; return 1; }
+    if (export_plan(views, n_views, n_thr, mesh, &p)) return 1;
+    if (!scratch || !out_pos || !minmax || (!all && !thr)) return fail("export_scatter: null argument");
+    if (!all && (k < 0 || k >= n_thr)) return fail("export_scatter: threshold index outside the count's");
+    if (layout != MUST3R_EXPORT_GLB && layout != MUST3R_EXPORT_PLY) return fail("export_scatter: unknown layout");
+    if (layout == MUST3R_EXPORT_GLB && !out_col) return fail("export_scatter: the GLB layout needs a colour plane");
+    if (layout == MUST3R_EXPORT_PLY && (reinterpret_cast<uintptr_t>(out_pos) & 15)) return fail("export_scatter: PLY records must be 16-byte aligned");
     const char* sc = reinterpret_cast<const char*>(scratch);
     const ExpView* dv = reinterpret_cast<const ExpView*>(sc);
     const unsigned* prefix = reinterpret_cast<const unsigned*>(sc + p.off_prefix) + (all ? 0 : (size_t)k * (size_t)(p.n_blocks + 1));
     float* partials = const_cast<float*>(reinterpret_cast<const float*>(sc + p.off_partials));
     const float t = all ? 0.f : thr[k];
     const dim3 g((unsigned)p.n_blocks), b(EXP_T);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* op = reinterpret_cast<float*>(out_pos);
     unsigned* oc = reinterpret_cast<unsigned*>(out_col);
     if (all) hipLaunchKernelGGL((export_points_kernel<false, true>), g, b, 0, s, dv, n_views, t, prefix, op, oc, partials);
     else if (layout == MUST3R_EXPORT_PLY) hipLaunchKernelGGL((export_points_kernel<true, false>), g, b, 0, s, dv, n_views, t, prefix, op, oc, partials);
     else hipLaunchKernelGGL((export_points_kernel<false, false>), g, b, 0, s, dv, n_views, t, prefix, op, oc, partials);
     hipLaunchKernelGGL(export_minmax_kernel, dim3(1), dim3(1024), 0, s, partials, p.n_blocks, minmax);
-    if (hipGetLastError() != hipSuccess) { *err = "export_scatter: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("export_scatter: launch failed");
     return 0;
 }
 
-int launch_export_faces(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, const void* scratch,
-                        unsigned* out_faces, hipStream_t s, const char** err) {
+extern "C" int must3r_hip_export_scatter_points(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, int layout,
+                                                const void* scratch, void* out_pos, void* out_col, float* minmax, void* stream) {
+    return launch_export_points(views, n_views, thr, n_thr, k, layout, 0, scratch, out_pos, out_col, minmax, stream);
+}
+
+extern "C" int must3r_hip_export_vertices(const must3r_hip_export_view* views, int n_views, int n_thr, void* scratch, float* out_pos, void* out_col,
+                                          float* minmax, void* stream) {
+    return launch_export_points(views, n_views, nullptr, n_thr, 0, MUST3R_EXPORT_GLB, 1, scratch, out_pos, out_col, minmax, stream);
+}
+
+extern "C" int must3r_hip_export_scatter_faces(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k,
+                                               const void* scratch, uint32_t* out_faces, void* stream) {
     ExpPlan p;
-    if (export_plan(views, n_views, n_thr, 1, &p, err)) return 1;
-    if (!scratch || !out_faces || !thr) { *err = "export_scatter_faces: null argument"; return 1; }
-    if (k < 0 || k >= n_thr) { *err = "export_scatter_faces: threshold index outside the count's"; return 1; }
+    if (export_plan(views, n_views, n_thr, 1, &p)) return 1;
+    if (!scratch || !out_faces || !thr) return fail("export_scatter_faces: null argument");
+    if (k < 0 || k >= n_thr) return fail("export_scatter_faces: threshold index outside the count's");
     const char* sc = reinterpret_cast<const char*>(scratch);
     const ExpView* dv = reinterpret_cast<const ExpView*>(sc);
     const size_t stride = (size_t)(p.n_blocks + 1);
     const unsigned* prefix = reinterpret_cast<const unsigned*>(sc + p.off_prefix);
-    hipLaunchKernelGGL(export_faces_kernel, dim3((unsigned)p.n_blocks), dim3(EXP_T), 0, s, dv, n_views, thr[k], prefix + (size_t)(2 * k) * stride,
-                       prefix + (size_t)(2 * k + 1) * stride, out_faces);
-    if (hipGetLastError() != hipSuccess) { *err = "export_scatter_faces: launch failed"; return 1; }
+    hipLaunchKernelGGL(export_faces_kernel, dim3((unsigned)p.n_blocks), dim3(EXP_T), 0, reinterpret_cast<hipStream_t>(stream), dv, n_views, thr[k],
+                       prefix + (size_t)(2 * k) * stride, prefix + (size_t)(2 * k + 1) * stride, out_faces);
+    if (hipGetLastError() != hipSuccess) return fail("export_scatter_faces: launch failed");
     return 0;
 }
-
-}  // namespace m3r

@@ -21,16 +21,14 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <tuple>
 #include <utility>
 #include <vector>
 
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
-#include "../../include/must3r_hip.h"
 
 namespace m3r {
 
@@ -170,16 +168,6 @@ static void build_coeffs(int mode, int in, int out, int ksize, int32_t* bounds, 
         bounds[2 * xx] = xmin;
         bounds[2 * xx + 1] = xmax;
     }
-}
-
-int image_coeffs(int mode, int in, int out, int* ksize, int32_t* bounds, void* weights, const char** err) {
-    if (mode < MUST3R_RESAMPLE_AA_BILINEAR || mode > MUST3R_RESAMPLE_NEAREST_EXACT) { *err = "resample_coeffs: unknown mode"; return 1; }
-    if (in <= 0 || out <= 0) { *err = "resample_coeffs: sizes must be positive"; return 1; }
-    const int k = ksize_of(mode, in, out);
-    if (ksize) *ksize = k;
-    if (bounds && weights) build_coeffs(mode, in, out, k, bounds, weights);
-    else if (bounds || weights) { *err = "resample_coeffs: pass both bounds and weights, or neither (ksize query)"; return 1; }
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -337,13 +325,6 @@ struct ResamplePlan {
     int max_blocks_h = 0, max_blocks_v = 0;
 };
 
-static thread_local char g_msg[256];
-static int bad(const char** err, const char* fmt, int a, int b = 0) {
-    snprintf(g_msg, sizeof(g_msg), fmt, a, b);
-    *err = g_msg;
-    return 1;
-}
-
 // Coefficients of the axes this thread has resampled lately: a stream of frames of one size builds its LANCZOS tables (double precision,
 // sin per tap) once, not once per call.
 struct CoefEntry {
@@ -375,14 +356,14 @@ struct StageSlot {
 };
 constexpr int kStageSlots = 4;
 
-static int stage_upload(void* dst, const void* src, size_t bytes, hipStream_t s, const char** err) {
+static int stage_upload(void* dst, const void* src, size_t bytes, hipStream_t s) {
     static thread_local StageSlot slots[kStageSlots];
     static thread_local int next = 0;
     StageSlot& slot = slots[next];
     next = (next + 1) % kStageSlots;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { *err = "resample: hipGetDevice failed"; return 1; }
-    if (slot.used && hipEventSynchronize(slot.ev) != hipSuccess) { *err = "resample: staging event wait failed"; return 1; }
+    if (hipGetDevice(&dev) != hipSuccess) return fail("resample: hipGetDevice failed");
+    if (slot.used && hipEventSynchronize(slot.ev) != hipSuccess) return fail("resample: staging event wait failed");
     slot.used = false;
     if (slot.dev != dev || slot.cap < bytes) {
         if (slot.pin) (void)hipHostFree(slot.pin);
@@ -392,21 +373,21 @@ static int stage_upload(void* dst, const void* src, size_t bytes, hipStream_t s,
         slot.cap = 0;
         slot.dev = -1;
         const size_t cap = std::max(bytes, (size_t)1 << 16);
-        if (hipHostMalloc(&slot.pin, cap) != hipSuccess) { slot.pin = nullptr; *err = "resample: pinned staging allocation failed"; return 1; }
-        if (hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming) != hipSuccess) { slot.ev = nullptr; *err = "resample: event creation failed"; return 1; }
+        if (hipHostMalloc(&slot.pin, cap) != hipSuccess) { slot.pin = nullptr; return fail("resample: pinned staging allocation failed"); }
+        if (hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming) != hipSuccess) { slot.ev = nullptr; return fail("resample: event creation failed"); }
         slot.cap = cap;
         slot.dev = dev;
     }
     std::memcpy(slot.pin, src, bytes);
-    if (hipMemcpyAsync(dst, slot.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess) { *err = "resample: table upload failed"; return 1; }
-    if (hipEventRecord(slot.ev, s) != hipSuccess) { *err = "resample: staging event record failed"; return 1; }
+    if (hipMemcpyAsync(dst, slot.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return fail("resample: table upload failed");
+    if (hipEventRecord(slot.ev, s) != hipSuccess) return fail("resample: staging event record failed");
     slot.used = true;
     return 0;
 }
 
-static int plan_resample(int mode, const must3r_hip_image_desc* ds, int n, float* out, ResamplePlan& P, const char** err) {
-    if (mode < MUST3R_RESAMPLE_AA_BILINEAR || mode > MUST3R_RESAMPLE_NEAREST_EXACT) return bad(err, "resample: unknown mode %d", mode);
-    if (n < 0 || n > 65535) return bad(err, "resample: %d images (0 ... 65535 per call)", n);
+static int plan_resample(int mode, const must3r_hip_image_desc* ds, int n, float* out, ResamplePlan& P) {
+    if (mode < MUST3R_RESAMPLE_AA_BILINEAR || mode > MUST3R_RESAMPLE_NEAREST_EXACT) return fail("resample: unknown mode %d", mode);
+    if (n < 0 || n > 65535) return fail("resample: %d images (0 ... 65535 per call)", n);
     const bool pil = mode == MUST3R_RESAMPLE_PIL_LANCZOS || mode == MUST3R_RESAMPLE_PIL_BICUBIC;
     // coefficient arrays, one per distinct (in, out) axis; words: bounds 2 x out, then weights ksize x out
     std::map<std::pair<int, int>, std::pair<int, int>> axes;   // (in, out) -> (word offset, ksize)
@@ -426,24 +407,24 @@ static int plan_resample(int mode, const must3r_hip_image_desc* ds, int n, float
     size_t tmp_bytes = 0;
     for (int m = 0; m < n; ++m) {
         const must3r_hip_image_desc& s = ds[m];
-        if (!s.src) return bad(err, "resample: image %d has no source", m);
-        if (s.src_format != MUST3R_IMG_U8_HWC && s.src_format != MUST3R_IMG_F32_CHW) return bad(err, "resample: image %d: unknown source format %d", m, s.src_format);
-        if (pil && s.src_format != MUST3R_IMG_U8_HWC) return bad(err, "resample: image %d: the PIL modes resample uint8 images (MUST3R_IMG_U8_HWC)", m);
-        if (s.channels < 1 || s.channels > 4) return bad(err, "resample: image %d: %d channels (1 ... 4)", m, s.channels);
-        if (s.H <= 0 || s.W <= 0) return bad(err, "resample: image %d is empty (%d rows)", m, s.H);
+        if (!s.src) return fail("resample: image %d has no source", m);
+        if (s.src_format != MUST3R_IMG_U8_HWC && s.src_format != MUST3R_IMG_F32_CHW) return fail("resample: image %d: unknown source format %d", m, s.src_format);
+        if (pil && s.src_format != MUST3R_IMG_U8_HWC) return fail("resample: image %d: the PIL modes resample uint8 images (MUST3R_IMG_U8_HWC)", m);
+        if (s.channels < 1 || s.channels > 4) return fail("resample: image %d: %d channels (1 ... 4)", m, s.channels);
+        if (s.H <= 0 || s.W <= 0) return fail("resample: image %d is empty (%d rows)", m, s.H);
         if (s.crop_h <= 0 || s.crop_w <= 0 || s.crop_y < 0 || s.crop_x < 0 || s.crop_y + s.crop_h > s.H || s.crop_x + s.crop_w > s.W)
-            return bad(err, "resample: image %d: crop box outside the %d-row source", m, s.H);
-        if (s.resize_h <= 0 || s.resize_w <= 0) return bad(err, "resample: image %d: empty target size", m);
+            return fail("resample: image %d: crop box outside the %d-row source", m, s.H);
+        if (s.resize_h <= 0 || s.resize_w <= 0) return fail("resample: image %d: empty target size", m);
         if (s.out_h <= 0 || s.out_w <= 0 || s.out_y < 0 || s.out_x < 0 || s.out_y + s.out_h > s.resize_h || s.out_x + s.out_w > s.resize_w)
-            return bad(err, "resample: image %d: output window outside the %d-row resampled image", m, s.resize_h);
-        if (s.out_offset < 0) return bad(err, "resample: image %d: negative output offset", m);
+            return fail("resample: image %d: output window outside the %d-row resampled image", m, s.resize_h);
+        if (s.out_offset < 0) return fail("resample: image %d: negative output offset", m);
         const long long esz = s.src_format == MUST3R_IMG_U8_HWC ? 1 : 4;
         if (s.src_format == MUST3R_IMG_U8_HWC) {
-            if (s.row_stride < (long long)s.W * s.channels) return bad(err, "resample: image %d: row stride below W x channels bytes", m);
+            if (s.row_stride < (long long)s.W * s.channels) return fail("resample: image %d: row stride below W x channels bytes", m);
         } else {
-            if (((uintptr_t)s.src & 3) != 0) return bad(err, "resample: image %d: fp32 source not 4-byte aligned", m);
-            if (s.row_stride < s.W) return bad(err, "resample: image %d: row stride below W elements", m);
-            if (s.channels > 1 && s.plane_stride < (long long)(s.H - 1) * s.row_stride + s.W) return bad(err, "resample: image %d: plane stride too small", m);
+            if (((uintptr_t)s.src & 3) != 0) return fail("resample: image %d: fp32 source not 4-byte aligned", m);
+            if (s.row_stride < s.W) return fail("resample: image %d: row stride below W elements", m);
+            if (s.channels > 1 && s.plane_stride < (long long)(s.H - 1) * s.row_stride + s.W) return fail("resample: image %d: plane stride too small", m);
         }
         const std::pair<int, int> X = axis(s.crop_w, s.resize_w), Y = axis(s.crop_h, s.resize_h);
         ImgDev& d = dev[m];
@@ -483,11 +464,11 @@ static int plan_resample(int mode, const must3r_hip_image_desc* ds, int n, float
         d.tiles_h = (s.out_w + RS_T - 1) / RS_T;
         d.tiles_v = (s.out_w + RS_VCOLS - 1) / RS_VCOLS;
         const long long bh = (long long)d.rows * d.tiles_h, bv = ((long long)s.out_h * d.tiles_v + RS_T / 64 - 1) / (RS_T / 64);
-        if (bh > 0x7fffffffLL || bv > 0x7fffffffLL) return bad(err, "resample: image %d too large", m);
+        if (bh > 0x7fffffffLL || bv > 0x7fffffffLL) return fail("resample: image %d too large", m);
         P.max_blocks_h = std::max(P.max_blocks_h, (int)bh);
         P.max_blocks_v = std::max(P.max_blocks_v, (int)bv);
     }
-    if (coef.size() > 0x7fffffffULL) return bad(err, "resample: coefficient tables too large", 0);
+    if (coef.size() > 0x7fffffffULL) return fail("resample: coefficient tables too large");
     P.desc_off = 1024;
     P.coef_off = up256(P.desc_off + sizeof(ImgDev) * n);
     P.tmp_off = up256(P.coef_off + coef.size() * 4);
@@ -503,26 +484,37 @@ static int plan_resample(int mode, const must3r_hip_image_desc* ds, int n, float
     return 0;
 }
 
-size_t image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n) {
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" int must3r_hip_resample_coeffs(int mode, int in, int out, int* ksize, int32_t* bounds, void* weights) {
+    if (mode < MUST3R_RESAMPLE_AA_BILINEAR || mode > MUST3R_RESAMPLE_NEAREST_EXACT) return fail("resample_coeffs: unknown mode");
+    if (in <= 0 || out <= 0) return fail("resample_coeffs: sizes must be positive");
+    const int k = ksize_of(mode, in, out);
+    if (ksize) *ksize = k;
+    if (bounds && weights) build_coeffs(mode, in, out, k, bounds, weights);
+    else if (bounds || weights) return fail("resample_coeffs: pass both bounds and weights, or neither (ksize query)");
+    return 0;
+}
+
+extern "C" size_t must3r_hip_image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n) {
     ResamplePlan P;
-    const char* err = nullptr;
-    if (n <= 0 || !descs || plan_resample(mode, descs, n, nullptr, P, &err)) return 0;
+    if (n <= 0 || !descs || plan_resample(mode, descs, n, nullptr, P)) return 0;
     return P.total;
 }
 
-int launch_resample(int mode, const must3r_hip_image_desc* descs, int n, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
-                    const char** err) {
-    ResamplePlan P;
-    if (plan_resample(mode, descs, n, out, P, err)) return 1;
+extern "C" int must3r_hip_resample(int mode, const must3r_hip_image_desc* descs, int n, float* out, void* scratch, size_t scratch_bytes,
+                                   void* stream) {
+    if (n < 0) return fail("resample: negative image count");
     if (n == 0) return 0;
-    if (!scratch) { *err = "resample: null scratch"; return 1; }
-    if (scratch_bytes < P.total) {
-        snprintf(g_msg, sizeof(g_msg), "resample: scratch of %zu bytes < %zu (must3r_hip_image_scratch_bytes)", scratch_bytes, P.total);
-        *err = g_msg;
-        return 1;
-    }
-    if (((uintptr_t)scratch & 255) != 0) { *err = "resample: scratch must be 256-byte aligned"; return 1; }
-    if (stage_upload(scratch, P.host.data(), P.host.size(), s, err)) return 1;
+    if (!descs || !out) return fail("resample: null argument");
+    ResamplePlan P;
+    if (plan_resample(mode, descs, n, out, P)) return 1;
+    if (!scratch) return fail("resample: null scratch");
+    if (scratch_bytes < P.total) return fail("resample: scratch of %zu bytes < %zu (must3r_hip_image_scratch_bytes)", scratch_bytes, P.total);
+    if (((uintptr_t)scratch & 255) != 0) return fail("resample: scratch must be 256-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (stage_upload(scratch, P.host.data(), P.host.size(), s)) return 1;
     unsigned char* base = static_cast<unsigned char*>(scratch);
     const ImgDev* dd = reinterpret_cast<const ImgDev*>(base + P.desc_off);
     const float* tab = reinterpret_cast<const float*>(base);
@@ -536,8 +528,6 @@ int launch_resample(int mode, const must3r_hip_image_desc* descs, int n, float* 
         hipLaunchKernelGGL(resample_h_kernel<false>, gh, dim3(RS_T), 0, s, dd, tab, coef, base);
         hipLaunchKernelGGL(resample_v_kernel<false>, gv, dim3(RS_T), 0, s, dd, tab, coef, base);
     }
-    if (hipGetLastError() != hipSuccess) { *err = "resample: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("resample: launch failed");
     return 0;
 }
-
-}  // namespace m3r

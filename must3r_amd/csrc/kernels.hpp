@@ -1,4 +1,5 @@
-// Host-side launcher declarations for the hand-written gfx950 kernels (one process per GPU, explicit stream).
+// Host-side launcher declarations for the hand-written gfx950 kernels of the model path (one process per GPU, explicit stream); the stateless
+// features declare nothing here: their entry points live beside their kernels (abi.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -211,75 +212,6 @@ int launch_quant8(DType dt, const void* in16, int ld_in, void* out8, int ld_out,
                   size_t rows, int cols, int tail_cols, hipStream_t s, const char** err);
 // pos int64 [V, gh*gw, 2] = (y, x) row-major grid
 int launch_fill_pos(int64_t* pos, int V, int gh, int gw, hipStream_t s, const char** err);
-// pointmaps [npix,7] fp32 -> pts3d [npix,3], pts3d_local [npix,3], conf [npix]; linear: ActivationType.LINEAR instead of NORM_EXP
-int launch_postprocess(const float* pm, int linear, float* pts3d, float* pts3d_local, float* conf, size_t npix, hipStream_t s,
-                       const char** err);
-// retrieval front-end on the encoder tokens (retrieval/model.py:59-101,165-183); retrieval.hip
-int launch_gemmx(int is_double, const float* A, const void* sub, const void* B, int b_transposed, const void* bias, const float* resid,
-                 float* out, int M, int N, int K, hipStream_t s, const char** err);
-int launch_row_norm(const float* x, int M, int C, float* out, hipStream_t s, const char** err);
-int launch_l2_normalize(const float* x, long long outer, int L, long long inner, float* out, hipStream_t s, const char** err);
-int launch_ln_act_f32(const float* x, const float* gamma, const float* beta, float eps, int M, int C, int gelu, float* out, hipStream_t s,
-                      const char** err);
-int launch_topk_gather(const float* feat, const float* attn, int Bn, int N, int C, int k, float* out_feat, float* out_attn,
-                       long long* out_idx, hipStream_t s, const char** err);
-int launch_weighted_spoc(const float* feat, const float* attn, int Bn, int N, int C, float* out, hipStream_t s, const char** err);
-// ASMK back-end of the retrieval mode (demo/inference.py:31-60, retrieval/processor.py:83-96): centroid norms, top-k quantizer on the
-// fp32 MFMA, per-image residual aggregation with sign bits, binary-kernel scores; asmk.hip
-int launch_asmk_sqnorm(const float* C, int K, int D, float* out, hipStream_t s, const char** err);
-size_t asmk_quantize_scratch_bytes(int M, int K, int k);
-int launch_asmk_quantize(const float* X, int M, const float* C, const float* csq, int K, int D, int k, int* ids, void* scratch,
-                         size_t scratch_bytes, hipStream_t s, const char** err);
-int launch_asmk_aggregate(const float* X, const float* C, int K, int D, const int* ids, int k_ids, int k_use, const int* offsets, int n_images,
-                          int max_rows, int* words, unsigned* bits, int* counts, hipStream_t s, const char** err);
-int launch_asmk_scores(const int* wq, const unsigned* bq, const int* cq, const int* oq, int kq, int n_q, const int* wd, const unsigned* bd,
-                       const int* cd, const int* od, int kd, int n_d, int D, float alpha, float tau, int normalize, double* out,
-                       hipStream_t s, const char** err);
-// SLAM keyframe test (slam/nns.py, slam/tools.py:9-31): exact 1-NN distances by brute force, view-direction quadrants; nn.hip
-int launch_nn_query(const float* db, long long n_db, const float* q, long long n_q, float* out_dist, hipStream_t s, const char** err);
-int launch_quadrant_ids(const float* pts, long long n, const float* cam_center_host, int div, int* out, hipStream_t s, const char** err);
-// exact 1-NN index over the same points (radix-sorted Morton order per quadrant, heap of fp32 boxes, stackless query); nn_index.hip
-size_t nn_index_bytes(long long n, int divider);
-size_t nn_index_scratch_bytes(long long n);
-int launch_nn_index_build(const float* xyz, const int* qid, long long n, int divider, void* index, void* scratch, hipStream_t s,
-                          const char** err);
-int launch_nn_index_query(const void* index, const float* q, long long n_q, const float* cam_center_host, int divider, float* out_dist,
-                          hipStream_t s, const char** err);
-
-// image ingestion (demo/inference.py:63-76 load_images, slam/model.py:99-120 preproc_frame): host coefficient builder, scratch plan and the
-// two-pass batched resampler; image.hip
-}  // namespace m3r
-struct must3r_hip_image_desc;
-namespace m3r {
-int image_coeffs(int mode, int in, int out, int* ksize, int32_t* bounds, void* weights, const char** err);
-size_t image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n);
-int launch_resample(int mode, const must3r_hip_image_desc* descs, int n, float* out, void* scratch, size_t scratch_bytes, hipStream_t s,
-                    const char** err);
-// scene export (demo/gradio.py:75-156): ordered compaction of the confident points / surviving triangles for up to 8 thresholds from
-// one count + scan, fp64 affine map with one rounding, written in GLB / PLY layout; export.hip
-}  // namespace m3r
-struct must3r_hip_export_view;
-namespace m3r {
-size_t export_scratch_bytes(const must3r_hip_export_view* views, int n_views, int n_thr, int mesh, const char** err);
-int launch_export_count(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int mesh, void* scratch,
-                        size_t scratch_bytes, long long* totals_host, hipStream_t s, const char** err);
-int launch_export_points(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, int layout, int all,
-                         const void* scratch, void* out_pos, void* out_col, float* minmax, hipStream_t s, const char** err);
-int launch_export_faces(const must3r_hip_export_view* views, int n_views, const float* thr, int n_thr, int k, const void* scratch,
-                        unsigned* out_faces, hipStream_t s, const char** err);
-// checkpoint evaluation (eval.py, must3r/engine/losses.py, tools/geometry.py normalize_pointcloud): fused masked reductions; metrics.hip
-}  // namespace m3r
-struct must3r_hip_metrics_loss_args;
-namespace m3r {
-size_t metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W, const char** err);
-int launch_metrics_loss(const must3r_hip_metrics_loss_args* a, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err);
-size_t metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode, const char** err);
-int launch_metrics_factor(const float* pts, const float* trf, const unsigned char* valid, int n_scenes, int n_views, int H, int W, int mode,
-                          float* factor, float* dist, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err);
-// postprocess(compute_cam=True): activation + focal (Weiszfeld) + weighted rigid registration, cam.hip
-size_t cam_scratch_bytes(int n_views, int H, int W);
-int launch_postprocess_cam(const float* pm, int linear, int n_views, int H, int W, float* pts3d, float* pts3d_local, float* conf,
-                           float* focal, float* c2w, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err);
 // 16-bit weight low part: lo = T(w - float(T(w)))  and hi = T(w), from fp32
 int launch_split16(DType dt, const float* in, void* hi, void* lo, size_t n, hipStream_t s, const char** err);
 // 2:4-sparse copy of the fp16 low part of w fp32 [rows, K] (rows % 32 == 0, K % 64 == 0): vals [K/64][rows][32] fp16, idx [K/64][rows/32][64] dwords (GemmArgs::Wlo_sp)

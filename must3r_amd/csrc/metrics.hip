@@ -16,9 +16,8 @@
 // Nothing here uses floating-point atomics; the histograms use integer ones, whose result does not depend on their order.  The block
 // count of a view (scene) depends on H W (V H W) alone, so a scene's figures do not depend on the rest of the batch.
 #include <cstdint>
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
-#include "../../include/must3r_hip.h"
 
 namespace m3r {
 namespace {
@@ -392,18 +391,14 @@ int blocks_for(long long n, int cap) {
     return (int)(c < cap ? c : cap);
 }
 
-int check_sizes(const char* who, int n_scenes, int n_views, int H, int W, const char** err) {
-    static thread_local char msg[128];
+int check_sizes(const char* who, int n_scenes, int n_views, int H, int W) {
     const char* what = nullptr;
     if (n_scenes <= 0) what = "n_scenes must be positive";
     else if (n_views <= 0) what = "n_views must be positive";
     else if (H <= 0 || W <= 0) what = "H and W must be positive";
     else if ((long long)n_views * H * W >= (1LL << 31)) what = "a scene has 2^31 or more pixels";
     else if ((long long)n_scenes * n_views > 65535) what = "more than 65535 views in a batch";
-    if (!what) return 0;
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    *err = msg;
-    return 1;
+    return what ? fail("%s: %s", who, what) : 0;
 }
 
 struct FactorPlan { int n_blocks; size_t off_hist, off_state, bytes; };
@@ -419,64 +414,64 @@ void factor_plan(int n_scenes, int n_views, int H, int W, FactorPlan* p) {
 }
 
 }  // namespace
+}  // namespace m3r
+using namespace m3r;
 
-size_t metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W, const char** err) {
-    if (check_sizes("metrics_loss", n_scenes, n_views, H, W, err)) return 0;
+extern "C" size_t must3r_hip_metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W) {
+    if (check_sizes("metrics_loss", n_scenes, n_views, H, W)) return 0;
     return align256((size_t)n_scenes * n_views * blocks_for((long long)H * W, MET_VIEW_BLOCKS) * 6 * sizeof(double));
 }
 
-int launch_metrics_loss(const must3r_hip_metrics_loss_args* a, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err) {
-    if (!a) { *err = "metrics_loss: null argument block"; return 1; }
-    if (check_sizes("metrics_loss", a->n_scenes, a->n_views, a->H, a->W, err)) return 1;
-    if (!a->gt_pts || !a->in_camera0 || !a->pr_pts || !a->valid || !a->counts || !a->sums || !scratch) {
-        *err = "metrics_loss: null argument"; return 1;
-    }
-    if (a->pr_local && !a->w2c) { *err = "metrics_loss: the local term needs w2c"; return 1; }
-    if (a->loss_in_log < 0 || a->loss_in_log > 2) { *err = "metrics_loss: loss_in_log must be 0, 1 or 2"; return 1; }
+extern "C" int must3r_hip_metrics_loss(const must3r_hip_metrics_loss_args* a, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!a) return fail("metrics_loss: null argument block");
+    if (check_sizes("metrics_loss", a->n_scenes, a->n_views, a->H, a->W)) return 1;
+    if (!a->gt_pts || !a->in_camera0 || !a->pr_pts || !a->valid || !a->counts || !a->sums || !scratch) return fail("metrics_loss: null argument");
+    if (a->pr_local && !a->w2c) return fail("metrics_loss: the local term needs w2c");
+    if (a->loss_in_log < 0 || a->loss_in_log > 2) return fail("metrics_loss: loss_in_log must be 0, 1 or 2");
     const int n_pix_out = (a->pix_g != nullptr) + (a->pix_l != nullptr) + (a->msk_g != nullptr) + (a->msk_l != nullptr);
-    if (n_pix_out != 0 && n_pix_out != 4) { *err = "metrics_loss: the per-pixel outputs come all four or not at all"; return 1; }
-    if (scratch_bytes < metrics_loss_scratch_bytes(a->n_scenes, a->n_views, a->H, a->W, err)) {
-        *err = "metrics_loss: scratch too small"; return 1;
-    }
+    if (n_pix_out != 0 && n_pix_out != 4) return fail("metrics_loss: the per-pixel outputs come all four or not at all");
+    if (scratch_bytes < must3r_hip_metrics_loss_scratch_bytes(a->n_scenes, a->n_views, a->H, a->W)) return fail("metrics_loss: scratch too small");
     LossDev p;
     p.a = *a;
     p.n_pix = (unsigned)((long long)a->H * a->W);
     const int n_bv = a->n_scenes * a->n_views, nb = blocks_for(p.n_pix, MET_VIEW_BLOCKS);
     double* slab = reinterpret_cast<double*>(scratch);
     const dim3 g((unsigned)nb, (unsigned)n_bv), t(MET_T);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (n_pix_out) hipLaunchKernelGGL(metrics_loss_kernel<true>, g, t, 0, s, p, slab);
     else hipLaunchKernelGGL(metrics_loss_kernel<false>, g, t, 0, s, p, slab);
     hipLaunchKernelGGL(metrics_loss_final_kernel, dim3((unsigned)((n_bv + 63) / 64)), dim3(64), 0, s, slab, n_bv, nb,
                        reinterpret_cast<long long*>(a->counts), a->sums);
-    if (hipGetLastError() != hipSuccess) { *err = "metrics_loss: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("metrics_loss: launch failed");
     return 0;
 }
 
-size_t metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode, const char** err) {
-    if (check_sizes("metrics_factor", n_scenes, n_views, H, W, err)) return 0;
-    if (mode < MUST3R_NORM_AVG_DIS || mode > MUST3R_NORM_MEDIAN_DIS) { *err = "metrics_factor: unknown mode"; return 0; }
+extern "C" size_t must3r_hip_metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode) {
+    if (check_sizes("metrics_factor", n_scenes, n_views, H, W)) return 0;
+    if (mode < MUST3R_NORM_AVG_DIS || mode > MUST3R_NORM_MEDIAN_DIS) { fail("metrics_factor: unknown mode"); return 0; }
     FactorPlan p;
     factor_plan(n_scenes, n_views, H, W, &p);
     return p.bytes;
 }
 
-int launch_metrics_factor(const float* pts, const float* trf, const unsigned char* valid, int n_scenes, int n_views, int H, int W, int mode,
-                          float* factor, float* dist, void* scratch, size_t scratch_bytes, hipStream_t s, const char** err) {
-    if (check_sizes("metrics_factor", n_scenes, n_views, H, W, err)) return 1;
-    if (mode < MUST3R_NORM_AVG_DIS || mode > MUST3R_NORM_MEDIAN_DIS) { *err = "metrics_factor: unknown mode"; return 1; }
-    if (!pts || !valid || !factor || !scratch) { *err = "metrics_factor: null argument"; return 1; }
-    if (mode == MUST3R_NORM_MEDIAN_DIS && !dist) { *err = "metrics_factor: median_dis needs the distance buffer"; return 1; }
+extern "C" int must3r_hip_metrics_factor(const float* pts, const float* trf, const uint8_t* valid, int n_scenes, int n_views, int H, int W, int mode,
+                                         float* factor, float* dist, void* scratch, size_t scratch_bytes, void* stream) {
+    if (check_sizes("metrics_factor", n_scenes, n_views, H, W)) return 1;
+    if (mode < MUST3R_NORM_AVG_DIS || mode > MUST3R_NORM_MEDIAN_DIS) return fail("metrics_factor: unknown mode");
+    if (!pts || !valid || !factor || !scratch) return fail("metrics_factor: null argument");
+    if (mode == MUST3R_NORM_MEDIAN_DIS && !dist) return fail("metrics_factor: median_dis needs the distance buffer");
     FactorPlan p;
     factor_plan(n_scenes, n_views, H, W, &p);
-    if (scratch_bytes < p.bytes) { *err = "metrics_factor: scratch too small"; return 1; }
+    if (scratch_bytes < p.bytes) return fail("metrics_factor: scratch too small");
     char* sc = reinterpret_cast<char*>(scratch);
     double* slab = reinterpret_cast<double*>(sc);
     unsigned* hist = reinterpret_cast<unsigned*>(sc + p.off_hist);
     SelState* state = reinterpret_cast<SelState*>(sc + p.off_state);
     const unsigned n = (unsigned)((long long)n_views * H * W);
     const dim3 g((unsigned)p.n_blocks, (unsigned)n_scenes), t(MET_T);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (mode == MUST3R_NORM_MEDIAN_DIS) {
-        if (hipMemsetAsync(sc + p.off_hist, 0, p.bytes - p.off_hist, s) != hipSuccess) { *err = "metrics_factor: clearing the bins failed"; return 1; }
+        if (hipMemsetAsync(sc + p.off_hist, 0, p.bytes - p.off_hist, s) != hipSuccess) return fail("metrics_factor: clearing the bins failed");
         hipLaunchKernelGGL(metrics_factor_kernel<MUST3R_NORM_MEDIAN_DIS>, g, t, 0, s, pts, trf, valid, n, dist, slab, hist);
         hipLaunchKernelGGL(metrics_select_kernel, dim3((unsigned)n_scenes), t, 0, s, hist, state, 11, 1);
         hipLaunchKernelGGL(metrics_hist_kernel, g, t, 0, s, dist, n, state, 10, 11, hist);
@@ -492,8 +487,6 @@ int launch_metrics_factor(const float* pts, const float* trf, const unsigned cha
     }
     hipLaunchKernelGGL(metrics_factor_final_kernel, dim3((unsigned)((n_scenes + 63) / 64)), dim3(64), 0, s, slab, state, n_scenes, p.n_blocks, mode,
                        factor);
-    if (hipGetLastError() != hipSuccess) { *err = "metrics_factor: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("metrics_factor: launch failed");
     return 0;
 }
-
-}  // namespace m3r

@@ -1,6 +1,7 @@
 // HBM-bound row / elementwise kernels: LayerNorm (wave per row, fp32 statistics, 16-bit and/or fp32 output),
 // patch im2col, casts, position grid, pointmap activation.  All vectorised to 16 B per lane where the
 // layout allows; no LDS needed (wave shuffles only).
+#include "abi.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 #include "options.hpp"
@@ -476,14 +477,21 @@ __global__ void postprocess_kernel(const float* __restrict__ pm, float* __restri
     }
 }
 
-int launch_postprocess(const float* pm, int linear, float* pts3d, float* pts3d_local, float* conf, size_t npix, hipStream_t s,
-                       const char** err) {
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" int must3r_hip_postprocess_act(const float* pm, int activation, float* pts3d, float* pts3d_local, float* conf, size_t npix, void* stream) {
+    if (!pm || !pts3d || !pts3d_local || !conf) return fail("postprocess: null argument");
+    if (activation != MUST3R_ACT_NORM_EXP && activation != MUST3R_ACT_LINEAR) return fail("postprocess: unknown activation %d", activation);
     if (!npix) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int grid = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
-    if (linear) hipLaunchKernelGGL(postprocess_kernel<true>, dim3(grid), dim3(256), 0, s, pm, pts3d, pts3d_local, conf, npix);
+    if (activation == MUST3R_ACT_LINEAR) hipLaunchKernelGGL(postprocess_kernel<true>, dim3(grid), dim3(256), 0, s, pm, pts3d, pts3d_local, conf, npix);
     else hipLaunchKernelGGL(postprocess_kernel<false>, dim3(grid), dim3(256), 0, s, pm, pts3d, pts3d_local, conf, npix);
-    if (hipGetLastError() != hipSuccess) { *err = "postprocess: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("postprocess: launch failed");
     return 0;
 }
 
-}  // namespace m3r
+extern "C" int must3r_hip_postprocess(const float* pm, float* pts3d, float* pts3d_local, float* conf, size_t npix, void* stream) {
+    return must3r_hip_postprocess_act(pm, MUST3R_ACT_NORM_EXP, pts3d, pts3d_local, conf, npix, stream);
+}

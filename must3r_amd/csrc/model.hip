@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/must3r_hip.h"
+#include "abi.hpp"
 #include "kernels.hpp"
 #include "options.hpp"
 
@@ -24,7 +24,7 @@ using namespace m3r;
 // error plumbing
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static int fail(const char* fmt, ...) {
+int m3r::fail(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -1435,277 +1435,8 @@ extern "C" int must3r_hip_decode(must3r_hip_ctx* c, const must3r_hip_decode_args
 }
 
 // ------------------------------------------------------------------------------------------------
-// postprocess + operator-level entry points + profiling
+// operator-level entry points + profiling
 // ------------------------------------------------------------------------------------------------
-extern "C" int must3r_hip_postprocess_act(const float* pm, int activation, float* p3, float* pl, float* cf, size_t npix, void* stream) {
-    const char* err = "";
-    if (!pm || !p3 || !pl || !cf) return fail("postprocess: null argument");
-    if (activation != MUST3R_ACT_NORM_EXP && activation != MUST3R_ACT_LINEAR) return fail("postprocess: unknown activation %d", activation);
-    if (launch_postprocess(pm, activation == MUST3R_ACT_LINEAR, p3, pl, cf, npix, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-extern "C" int must3r_hip_postprocess(const float* pm, float* p3, float* pl, float* cf, size_t npix, void* stream) {
-    return must3r_hip_postprocess_act(pm, MUST3R_ACT_NORM_EXP, p3, pl, cf, npix, stream);
-}
-
-extern "C" int must3r_hip_affine(int is_double, const float* A, const void* sub, const void* B, int b_transposed, const void* bias,
-                                 const float* resid, float* out, int M, int N, int K, void* stream) {
-    if (M < 0 || N < 0 || K < 0) return fail("affine: negative size");
-    if (M == 0 || N == 0) return 0;
-    if (!A || !B || !out) return fail("affine: null argument");
-    const char* err = nullptr;
-    if (launch_gemmx(is_double, A, sub, B, b_transposed, bias, resid, out, M, N, K, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_row_norm(const float* x, int M, int C, float* out, void* stream) {
-    if (M < 0 || C <= 0) return fail("row_norm: bad shape");
-    if (M == 0) return 0;
-    if (!x || !out) return fail("row_norm: null argument");
-    const char* err = nullptr;
-    if (launch_row_norm(x, M, C, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_l2_normalize(const float* x, int64_t outer, int L, int64_t inner, float* out, void* stream) {
-    if (outer < 0 || inner < 0 || L < 0) return fail("l2_normalize: negative size");
-    if (outer == 0 || inner == 0 || L == 0) return 0;
-    if (!x || !out) return fail("l2_normalize: null argument");
-    if (outer * inner > (int64_t)0x7fffffff * 4) return fail("l2_normalize: too many vectors");
-    const char* err = nullptr;
-    if (launch_l2_normalize(x, outer, L, inner, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_layernorm_act_f32(const float* x, const float* gamma, const float* beta, float eps, int M, int C, int gelu,
-                                            float* out, void* stream) {
-    if (M < 0 || C <= 0) return fail("layernorm_act_f32: bad shape");
-    if (M == 0) return 0;
-    if (!x || !out) return fail("layernorm_act_f32: null argument");
-    const char* err = nullptr;
-    if (launch_ln_act_f32(x, gamma, beta, eps, M, C, gelu, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_topk_gather(const float* feat, const float* attn, int n_images, int N, int C, int k, float* out_feat,
-                                      float* out_attn, int64_t* out_idx, void* stream) {
-    if (n_images < 0 || N < 0 || C <= 0 || k < 0) return fail("topk_gather: bad shape");
-    if (n_images == 0 || k == 0) return 0;
-    if (!feat || !attn || !out_feat || !out_attn || !out_idx) return fail("topk_gather: null argument");
-    const char* err = nullptr;
-    if (launch_topk_gather(feat, attn, n_images, N, C, k, out_feat, out_attn, reinterpret_cast<long long*>(out_idx),
-                           reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_weighted_spoc(const float* feat, const float* attn, int n_images, int N, int C, float* out, void* stream) {
-    if (n_images < 0 || N < 0 || C <= 0) return fail("weighted_spoc: bad shape");
-    if (n_images == 0) return 0;
-    if (!feat || !attn || !out) return fail("weighted_spoc: null argument");
-    const char* err = nullptr;
-    if (launch_weighted_spoc(feat, attn, n_images, N, C, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_asmk_centroid_sqnorm(const float* centroids, int K, int D, float* out, void* stream) {
-    if (K < 0 || D <= 0) return fail("asmk_centroid_sqnorm: bad shape");
-    if (K == 0) return 0;
-    if (!centroids || !out) return fail("asmk_centroid_sqnorm: null argument");
-    const char* err = nullptr;
-    if (launch_asmk_sqnorm(centroids, K, D, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" size_t must3r_hip_asmk_quantize_scratch_bytes(int M, int K, int k) { return asmk_quantize_scratch_bytes(M, K, k); }
-
-extern "C" int must3r_hip_asmk_quantize(const float* feat, int M, const float* centroids, const float* c_sqnorm, int K, int D, int k, int32_t* ids,
-                                        void* scratch, size_t scratch_bytes, void* stream) {
-    if (M < 0 || K <= 0 || D <= 0) return fail("asmk_quantize: bad shape");
-    if (M == 0) return 0;
-    if (!feat || !centroids || !c_sqnorm || !ids) return fail("asmk_quantize: null argument");
-    const char* err = nullptr;
-    if (launch_asmk_quantize(feat, M, centroids, c_sqnorm, K, D, k, ids, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), &err))
-        return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_asmk_aggregate(const float* feat, const float* centroids, int K, int D, const int32_t* ids, int k_ids, int k_use,
-                                         const int32_t* offsets_dev, int n_images, int max_rows, int32_t* words, uint32_t* bits, int32_t* counts,
-                                         void* stream) {
-    if (n_images < 0 || K <= 0 || D <= 0) return fail("asmk_aggregate: bad shape");
-    if (n_images == 0) return 0;
-    if (!feat || !centroids || !ids || !offsets_dev || !words || !bits || !counts) return fail("asmk_aggregate: null argument");
-    const char* err = nullptr;
-    if (launch_asmk_aggregate(feat, centroids, K, D, ids, k_ids, k_use, offsets_dev, n_images, max_rows, words, bits, counts,
-                              reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_asmk_scores(const int32_t* words_q, const uint32_t* bits_q, const int32_t* counts_q, const int32_t* offsets_q, int k_q,
-                                      int n_q, const int32_t* words_d, const uint32_t* bits_d, const int32_t* counts_d, const int32_t* offsets_d,
-                                      int k_d, int n_d, int D, float alpha, float threshold, int normalize, double* out, void* stream) {
-    if (n_q < 0 || n_d < 0 || D <= 0 || k_q < 1 || k_d < 1) return fail("asmk_scores: bad shape");
-    if (n_q == 0 || n_d == 0) return 0;
-    if (!words_q || !bits_q || !counts_q || !offsets_q || !words_d || !bits_d || !counts_d || !offsets_d || !out)
-        return fail("asmk_scores: null argument");
-    const char* err = nullptr;
-    if (launch_asmk_scores(words_q, bits_q, counts_q, offsets_q, k_q, n_q, words_d, bits_d, counts_d, offsets_d, k_d, n_d, D, alpha, threshold,
-                           normalize, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_nn_query(const float* db, int64_t n_db, const float* q, int64_t n_q, float* out, void* stream) {
-    if (n_db < 0 || n_q < 0) return fail("nn_query: negative count");
-    if (n_q == 0) return 0;
-    if (!q || !out || (n_db > 0 && !db)) return fail("nn_query: null argument");
-    const char* err = nullptr;
-    if (launch_nn_query(db, n_db, q, n_q, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_quadrant_ids(const float* pts, int64_t n, const float* cam_center, int divider, int32_t* out, void* stream) {
-    if (n < 0) return fail("quadrant_ids: negative count");
-    if (n == 0) return 0;
-    if (!pts || !cam_center || !out) return fail("quadrant_ids: null argument");
-    const char* err = nullptr;
-    if (launch_quadrant_ids(pts, n, cam_center, divider, out, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" size_t must3r_hip_nn_index_bytes(int64_t n, int divider) { return nn_index_bytes(n, divider); }
-extern "C" size_t must3r_hip_nn_index_scratch_bytes(int64_t n) { return nn_index_scratch_bytes(n); }
-
-extern "C" int must3r_hip_nn_index_build(const float* xyz, const int32_t* quadrant_ids, int64_t n, int divider, void* index, void* scratch,
-                                         void* stream) {
-    if (n < 0) return fail("nn_index_build: negative count");
-    if (!index || (n > 0 && (!xyz || !scratch))) return fail("nn_index_build: null argument");
-    const char* err = nullptr;
-    if (launch_nn_index_build(xyz, quadrant_ids, n, divider, index, scratch, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_nn_index_query(const void* index, const float* q_xyz, int64_t n_q, const float* cam_center_host3, int divider,
-                                         float* out_dist, void* stream) {
-    if (n_q < 0) return fail("nn_index_query: negative count");
-    if (n_q == 0) return 0;
-    if (!index || !q_xyz || !out_dist || (divider > 0 && !cam_center_host3)) return fail("nn_index_query: null argument");
-    const char* err = nullptr;
-    if (launch_nn_index_query(index, q_xyz, n_q, cam_center_host3, divider, out_dist, reinterpret_cast<hipStream_t>(stream), &err))
-        return fail("%s", err);
-    return 0;
-}
-
-extern "C" size_t must3r_hip_export_scratch_bytes(const must3r_hip_export_view* views_host, int n_views, int n_thr, int mesh) {
-    const char* err = nullptr;
-    const size_t b = export_scratch_bytes(views_host, n_views, n_thr, mesh, &err);
-    if (!b) fail("%s", err ? err : "export: bad view table");
-    return b;
-}
-
-extern "C" int must3r_hip_export_count(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int mesh,
-                                       void* scratch, size_t scratch_bytes, int64_t* totals_host, void* stream) {
-    if (!totals_host) return fail("export_count: null argument");
-    const char* err = nullptr;
-    long long tot[MUST3R_EXPORT_MAX_THR] = {0};
-    if (launch_export_count(views_host, n_views, thr_host, n_thr, mesh, scratch, scratch_bytes, tot, reinterpret_cast<hipStream_t>(stream), &err))
-        return fail("%s", err);
-    for (int k = 0; k < n_thr; ++k) totals_host[k] = tot[k];
-    return 0;
-}
-
-extern "C" int must3r_hip_export_scatter_points(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int k,
-                                                int layout, const void* scratch, void* out_pos, void* out_col, float* minmax, void* stream) {
-    const char* err = nullptr;
-    if (launch_export_points(views_host, n_views, thr_host, n_thr, k, layout, 0, scratch, out_pos, out_col, minmax,
-                             reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_export_vertices(const must3r_hip_export_view* views_host, int n_views, int n_thr, void* scratch, float* out_pos,
-                                          void* out_col, float* minmax, void* stream) {
-    const char* err = nullptr;
-    if (launch_export_points(views_host, n_views, nullptr, n_thr, 0, MUST3R_EXPORT_GLB, 1, scratch, out_pos, out_col, minmax,
-                             reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_export_scatter_faces(const must3r_hip_export_view* views_host, int n_views, const float* thr_host, int n_thr, int k,
-                                               const void* scratch, uint32_t* out_faces, void* stream) {
-    const char* err = nullptr;
-    if (launch_export_faces(views_host, n_views, thr_host, n_thr, k, scratch, out_faces, reinterpret_cast<hipStream_t>(stream), &err))
-        return fail("%s", err);
-    return 0;
-}
-
-extern "C" size_t must3r_hip_metrics_loss_scratch_bytes(int n_scenes, int n_views, int H, int W) {
-    const char* err = nullptr;
-    const size_t b = metrics_loss_scratch_bytes(n_scenes, n_views, H, W, &err);
-    if (!b) fail("%s", err ? err : "metrics_loss: bad sizes");
-    return b;
-}
-
-extern "C" int must3r_hip_metrics_loss(const must3r_hip_metrics_loss_args* args, void* scratch, size_t scratch_bytes, void* stream) {
-    const char* err = nullptr;
-    if (launch_metrics_loss(args, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" size_t must3r_hip_metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode) {
-    const char* err = nullptr;
-    const size_t b = metrics_factor_scratch_bytes(n_scenes, n_views, H, W, mode, &err);
-    if (!b) fail("%s", err ? err : "metrics_factor: bad sizes");
-    return b;
-}
-
-extern "C" int must3r_hip_metrics_factor(const float* pts, const float* trf, const uint8_t* valid, int n_scenes, int n_views, int H, int W,
-                                         int mode, float* factor, float* dist, void* scratch, size_t scratch_bytes, void* stream) {
-    const char* err = nullptr;
-    if (launch_metrics_factor(pts, trf, valid, n_scenes, n_views, H, W, mode, factor, dist, scratch, scratch_bytes,
-                              reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" int must3r_hip_resample_coeffs(int mode, int in_size, int out_size, int* ksize, int32_t* bounds, void* weights) {
-    const char* err = nullptr;
-    if (image_coeffs(mode, in_size, out_size, ksize, bounds, weights, &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" size_t must3r_hip_image_scratch_bytes(int mode, const must3r_hip_image_desc* descs, int n_images) {
-    return image_scratch_bytes(mode, descs, n_images);
-}
-
-extern "C" int must3r_hip_resample(int mode, const must3r_hip_image_desc* descs, int n_images, float* out, void* scratch, size_t scratch_bytes,
-                                   void* stream) {
-    if (n_images < 0) return fail("resample: negative image count");
-    if (n_images == 0) return 0;
-    if (!descs || !out) return fail("resample: null argument");
-    const char* err = nullptr;
-    if (launch_resample(mode, descs, n_images, out, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-
-extern "C" size_t must3r_hip_postprocess_cam_scratch_bytes(int n_views, int H, int W) {
-    if (n_views <= 0 || H <= 0 || W <= 0) return 0;
-    return cam_scratch_bytes(n_views, H, W);
-}
-
-extern "C" int must3r_hip_postprocess_cam_act(const float* pm, int activation, int n_views, int H, int W, float* p3, float* pl, float* cf,
-                                              float* focal, float* c2w, void* scratch, size_t scratch_bytes, void* stream) {
-    if (n_views < 0 || H <= 0 || W <= 0) return fail("postprocess_cam: bad shape");
-    if (activation != MUST3R_ACT_NORM_EXP && activation != MUST3R_ACT_LINEAR) return fail("postprocess_cam: unknown activation %d", activation);
-    if (n_views == 0) return 0;
-    if (!pm || !p3 || !pl || !cf || !focal || !c2w || !scratch) return fail("postprocess_cam: null argument");
-    const char* err = nullptr;
-    if (launch_postprocess_cam(pm, activation == MUST3R_ACT_LINEAR, n_views, H, W, p3, pl, cf, focal, c2w, scratch, scratch_bytes,
-                               reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
-    return 0;
-}
-extern "C" int must3r_hip_postprocess_cam(const float* pm, int n_views, int H, int W, float* p3, float* pl, float* cf,
-                                          float* focal, float* c2w, void* scratch, size_t scratch_bytes, void* stream) {
-    return must3r_hip_postprocess_cam_act(pm, MUST3R_ACT_NORM_EXP, n_views, H, W, p3, pl, cf, focal, c2w, scratch, scratch_bytes, stream);
-}
-
 extern "C" int must3r_hip_op_gemm(int dtype, int epi, const void* A, const void* W, const float* bias, void* out, int M, int N,
                                   int K, int lda, int ldc, const int64_t* pos, const float* rope_tab, int rope_cols,
                                   int rope_npos, const float* bias2, int row_start2, int accumulate, int ntok, int gw, int H,

@@ -13,8 +13,8 @@
 //   quadrant_id_kernel   nns.py:80-92 / slam/tools.py:9-31: view-direction quadrant of (p - cam_center)
 //
 // VALU-bound (fp32 vector rate 157 TFLOP/s): 8 flops per pair.
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
 
 namespace m3r {
 
@@ -102,9 +102,15 @@ __global__ void quadrant_id_kernel(const float* __restrict__ pts, const long lon
     out[i] = ti + pj * div;
 }
 
-int launch_nn_query(const float* db, long long n_db, const float* q, long long n_q, float* out_dist, hipStream_t s, const char** err) {
-    if (n_q <= 0) return 0;
-    unsigned* bits = reinterpret_cast<unsigned*>(out_dist);
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" int must3r_hip_nn_query(const float* db, int64_t n_db, const float* q, int64_t n_q, float* out, void* stream) {
+    if (n_db < 0 || n_q < 0) return fail("nn_query: negative count");
+    if (n_q == 0) return 0;
+    if (!q || !out || (n_db > 0 && !db)) return fail("nn_query: null argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    unsigned* bits = reinterpret_cast<unsigned*>(out);
     const unsigned gq = (unsigned)((n_q + 255) / 256);
     hipLaunchKernelGGL(nn_fill_kernel, dim3(gq), dim3(256), 0, s, bits, n_q);
     if (n_db > 0) {
@@ -117,21 +123,21 @@ int launch_nn_query(const float* db, long long n_db, const float* q, long long n
         long long chunk = (n_db + splits - 1) / splits;
         chunk = ((chunk + NN_TILE - 1) / NN_TILE) * NN_TILE;
         splits = (n_db + chunk - 1) / chunk;
-        if (qblocks > 0x7fffffffLL) { *err = "nn_query: too many queries"; return 1; }
+        if (qblocks > 0x7fffffffLL) return fail("nn_query: too many queries");
         hipLaunchKernelGGL(nn_query_kernel, dim3((unsigned)qblocks, (unsigned)splits), dim3(NN_T), 0, s, db, n_db, q, n_q, bits, chunk);
     }
-    hipLaunchKernelGGL(nn_finish_kernel, dim3(gq), dim3(256), 0, s, out_dist, n_q);
-    if (hipGetLastError() != hipSuccess) { *err = "nn_query: launch failed"; return 1; }
+    hipLaunchKernelGGL(nn_finish_kernel, dim3(gq), dim3(256), 0, s, out, n_q);
+    if (hipGetLastError() != hipSuccess) return fail("nn_query: launch failed");
     return 0;
 }
 
-int launch_quadrant_ids(const float* pts, long long n, const float* cam_center_host, int div, int* out, hipStream_t s, const char** err) {
-    if (n <= 0) return 0;
-    if (div < 1) { *err = "quadrant_ids: bad divider"; return 1; }
-    hipLaunchKernelGGL(quadrant_id_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pts, n, cam_center_host[0], cam_center_host[1],
-                       cam_center_host[2], div, out);
-    if (hipGetLastError() != hipSuccess) { *err = "quadrant_ids: launch failed"; return 1; }
+extern "C" int must3r_hip_quadrant_ids(const float* pts, int64_t n, const float* cam_center, int divider, int32_t* out, void* stream) {
+    if (n < 0) return fail("quadrant_ids: negative count");
+    if (n == 0) return 0;
+    if (!pts || !cam_center || !out) return fail("quadrant_ids: null argument");
+    if (divider < 1) return fail("quadrant_ids: bad divider");
+    hipLaunchKernelGGL(quadrant_id_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pts, n,
+                       cam_center[0], cam_center[1], cam_center[2], divider, out);
+    if (hipGetLastError() != hipSuccess) return fail("quadrant_ids: launch failed");
     return 0;
 }
-
-}  // namespace m3r

@@ -16,7 +16,7 @@
 //     nn_tree_level_kernel leaf boxes, then the levels above: one launch per tree height over every quadrant's nodes at that height
 //                          (a leaf never straddles two quadrants)
 //   query
-//     quadrant ids of the queries by nn.hip's quadrant_id_kernel (launch_quadrant_ids), written into out_dist and read back by
+//     quadrant ids of the queries by nn.hip's quadrant_id_kernel (must3r_hip_quadrant_ids), written into out_dist and read back by
 //     nn_index_query_kernel<G>: G lanes per query walk its quadrant's heap together, nearer child first, a node pruned when its box
 //     bound is >= the best d2 so far; stackless (the path is the node number, a bit per level says the far sibling was taken):
 //     registers only.  A query with another divider than the build's gets NaN.
@@ -25,8 +25,8 @@
 // the per-axis gaps max(lo - q, q - hi, 0), and fl() is monotone and sign-symmetric, so |fl(q - p)| >= gap for every p in the box and the
 // bound never exceeds the d2 of any of its points: a pruned subtree cannot hold a value below the minimum, the minimum is the brute
 // force's minimum over the same points, and sqrtf of it is bit-identical.  Empty quadrant / non-finite query: +inf as nn.hip gives.
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
 #include "options.hpp"
 
 namespace m3r {
@@ -365,7 +365,7 @@ __global__ void __launch_bounds__(256) nn_index_query_kernel(const char* __restr
     const int i = (int)(t / G), sub = (int)(t % G);   // a group never straddles a wave (G divides 64)
     if (i >= n_q) return;
     const NnIndexHeader* h = reinterpret_cast<const NnIndexHeader*>(index);
-    const int quad = divider > 0 ? reinterpret_cast<const int*>(out)[i] : 0;   // launch_quadrant_ids wrote the id here; read before the write
+    const int quad = divider > 0 ? reinterpret_cast<const int*>(out)[i] : 0;   // must3r_hip_quadrant_ids wrote the id here; read before the write
     const float qx = q[(long long)i * 3 + 0], qy = q[(long long)i * 3 + 1], qz = q[(long long)i * 3 + 2];
     float best = INFINITY;
     const int P = (quad >= 0 && quad < h->n_quads) ? h->pow2[quad] : 0;
@@ -425,23 +425,27 @@ void launch_query_g(const char* index, const float* q, long long n_q, int divide
 }
 
 }  // namespace
+}  // namespace m3r
+using namespace m3r;
 
-size_t nn_index_bytes(long long n, int divider) {
+extern "C" size_t must3r_hip_nn_index_bytes(int64_t n, int divider) {
     if (n < 0 || n > NNI_MAX_N || divider < 0 || n_quads_of(divider) > NNI_MAXQ) return 0;
     const int Q = n_quads_of(divider);
     return NNI_HEADER_BYTES + (size_t)n * 16 + (size_t)node_cap_of(n, Q) * 32;
 }
 
-size_t nn_index_scratch_bytes(long long n) {
+extern "C" size_t must3r_hip_nn_index_scratch_bytes(int64_t n) {
     if (n < 0 || n > NNI_MAX_N) return 0;
     return (size_t)n * 16 + (size_t)rs_blocks_of(n) * 256 * 4 + BB_BLOCKS * 6 * 4 + 256;
 }
 
-int launch_nn_index_build(const float* xyz, const int* qid, long long n, int divider, void* index, void* scratch, hipStream_t s,
-                          const char** err) {
-    if (n < 0 || n > NNI_MAX_N) { *err = "nn_index_build: point count outside [0, 2^30]"; return 1; }
-    if (divider < 0 || n_quads_of(divider) > NNI_MAXQ) { *err = "nn_index_build: divider outside [0, 8]"; return 1; }
-    if (divider > 0 && n > 0 && !qid) { *err = "nn_index_build: quadrant ids are needed when divider > 0"; return 1; }
+extern "C" int must3r_hip_nn_index_build(const float* xyz, const int32_t* qid, int64_t n, int divider, void* index, void* scratch, void* stream) {
+    if (n < 0) return fail("nn_index_build: negative count");
+    if (!index || (n > 0 && (!xyz || !scratch))) return fail("nn_index_build: null argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (n < 0 || n > NNI_MAX_N) return fail("nn_index_build: point count outside [0, 2^30]");
+    if (divider < 0 || n_quads_of(divider) > NNI_MAXQ) return fail("nn_index_build: divider outside [0, 8]");
+    if (divider > 0 && n > 0 && !qid) return fail("nn_index_build: quadrant ids are needed when divider > 0");
     const int Q = n_quads_of(divider);
     const int leaf_log2 = opt(OPT_NN_LEAF_LOG2);
     int qbits = 0;
@@ -452,7 +456,7 @@ int launch_nn_index_build(const float* xyz, const int* qid, long long n, int div
     const long long pts_off = NNI_HEADER_BYTES, nodes_off = pts_off + n * 16;
     char* idx = reinterpret_cast<char*>(index);
     NnIndexHeader* h = reinterpret_cast<NnIndexHeader*>(idx);
-    if (hipMemsetAsync(idx, 0, nn_index_bytes(n, divider), s) != hipSuccess) { *err = "nn_index_build: memset failed"; return 1; }
+    if (hipMemsetAsync(idx, 0, must3r_hip_nn_index_bytes(n, divider), s) != hipSuccess) return fail("nn_index_build: memset failed");
     const int ni = (int)n;
     unsigned* kA = reinterpret_cast<unsigned*>(scratch);
     unsigned* vA = kA + n;
@@ -491,16 +495,19 @@ int launch_nn_index_build(const float* xyz, const int* qid, long long n, int div
             hipLaunchKernelGGL(nn_tree_level_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, s, idx, height);
         }
     }
-    if (hipGetLastError() != hipSuccess) { *err = "nn_index_build: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("nn_index_build: launch failed");
     return 0;
 }
 
-int launch_nn_index_query(const void* index, const float* q, long long n_q, const float* cam_center_host, int divider, float* out_dist,
-                          hipStream_t s, const char** err) {
-    if (n_q <= 0) return 0;
-    if (n_q > NNI_MAX_N) { *err = "nn_index_query: query count above 2^30"; return 1; }
-    if (divider < 0 || n_quads_of(divider) > NNI_MAXQ) { *err = "nn_index_query: divider outside [0, 8]"; return 1; }
-    if (divider > 0 && launch_quadrant_ids(q, n_q, cam_center_host, divider, reinterpret_cast<int*>(out_dist), s, err)) return 1;
+extern "C" int must3r_hip_nn_index_query(const void* index, const float* q, int64_t n_q, const float* cam_center_host, int divider, float* out_dist,
+                                         void* stream) {
+    if (n_q < 0) return fail("nn_index_query: negative count");
+    if (n_q == 0) return 0;
+    if (!index || !q || !out_dist || (divider > 0 && !cam_center_host)) return fail("nn_index_query: null argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (n_q > NNI_MAX_N) return fail("nn_index_query: query count above 2^30");
+    if (divider < 0 || n_quads_of(divider) > NNI_MAXQ) return fail("nn_index_query: divider outside [0, 8]");
+    if (divider > 0 && must3r_hip_quadrant_ids(q, n_q, cam_center_host, divider, reinterpret_cast<int32_t*>(out_dist), stream)) return 1;
     const char* idx = reinterpret_cast<const char*>(index);
     switch (opt(OPT_NN_QUERY_LANES_LOG2)) {
         case 0: launch_query_g<1>(idx, q, n_q, divider, out_dist, s); break;
@@ -509,8 +516,6 @@ int launch_nn_index_query(const void* index, const float* q, long long n_q, cons
         case 3: launch_query_g<8>(idx, q, n_q, divider, out_dist, s); break;
         default: launch_query_g<16>(idx, q, n_q, divider, out_dist, s); break;
     }
-    if (hipGetLastError() != hipSuccess) { *err = "nn_index_query: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("nn_index_query: launch failed");
     return 0;
 }
-
-}  // namespace m3r

@@ -13,8 +13,8 @@
 //   ln_act_f32_kernel    fp32 LayerNorm + erf GELU: the hidden layers of a multi-layer projector
 //   spoc_kernel          per image: out = normalize(sum_n attn[n] feat[n,:])  (fp32 sums in token order, F.normalize eps 1e-12)
 // Small problems (768 tokens x 1024 features per image): latency matters more than rate; fp64 MFMA peak is 78.6 TFLOP/s.
+#include "abi.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
 
 namespace m3r {
 
@@ -241,56 +241,74 @@ __global__ void __launch_bounds__(256) ln_act_f32_kernel(const float* __restrict
     }
 }
 
-int launch_l2_normalize(const float* x, long long outer, int L, long long inner, float* out, hipStream_t s, const char** err) {
-    if (outer <= 0 || inner <= 0 || L <= 0) return 0;
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" int must3r_hip_l2_normalize(const float* x, int64_t outer, int L, int64_t inner, float* out, void* stream) {
+    if (outer < 0 || inner < 0 || L < 0) return fail("l2_normalize: negative size");
+    if (outer == 0 || inner == 0 || L == 0) return 0;
+    if (!x || !out) return fail("l2_normalize: null argument");
+    if (outer * inner > (int64_t)0x7fffffff * 4) return fail("l2_normalize: too many vectors");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (inner == 1) hipLaunchKernelGGL(l2_normalize_rows_copy_kernel, dim3((unsigned)((outer + 3) / 4)), dim3(256), 0, s, x, outer, L, out);
     else hipLaunchKernelGGL(l2_normalize_strided_kernel, dim3((unsigned)((outer * inner + 255) / 256)), dim3(256), 0, s, x, outer, L, inner, out);
-    if (hipGetLastError() != hipSuccess) { *err = "l2_normalize: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("l2_normalize: launch failed");
     return 0;
 }
 
-int launch_ln_act_f32(const float* x, const float* gamma, const float* beta, float eps, int M, int C, int gelu, float* out, hipStream_t s,
-                      const char** err) {
-    if (M <= 0) return 0;
-    hipLaunchKernelGGL(ln_act_f32_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, gamma, beta, eps, M, C, gelu, out);
-    if (hipGetLastError() != hipSuccess) { *err = "ln_act: launch failed"; return 1; }
+extern "C" int must3r_hip_layernorm_act_f32(const float* x, const float* gamma, const float* beta, float eps, int M, int C, int gelu,
+                                            float* out, void* stream) {
+    if (M < 0 || C <= 0) return fail("layernorm_act_f32: bad shape");
+    if (M == 0) return 0;
+    if (!x || !out) return fail("layernorm_act_f32: null argument");
+    hipLaunchKernelGGL(ln_act_f32_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, gamma, beta, eps, M, C, gelu, out);
+    if (hipGetLastError() != hipSuccess) return fail("ln_act: launch failed");
     return 0;
 }
 
-int launch_gemmx(int is_double, const float* A, const void* sub, const void* B, int b_transposed, const void* bias, const float* resid,
-                 float* out, int M, int N, int K, hipStream_t s, const char** err) {
-    if (M <= 0 || N <= 0) return 0;
-    if (K <= 0) { *err = "gemmx: K must be positive"; return 1; }
+extern "C" int must3r_hip_affine(int is_double, const float* A, const void* sub, const void* B, int b_transposed, const void* bias,
+                                 const float* resid, float* out, int M, int N, int K, void* stream) {
+    if (M < 0 || N < 0 || K < 0) return fail("affine: negative size");
+    if (M == 0 || N == 0) return 0;
+    if (!A || !B || !out) return fail("affine: null argument");
+    if (K <= 0) return fail("gemmx: K must be positive");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     GemmxArgs a{A, sub, B, bias, resid, out, M, N, K, b_transposed};
     const dim3 grid((N + 63) / 64, (M + 63) / 64);
     if (is_double) hipLaunchKernelGGL(gemmx_kernel<double>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(gemmx_kernel<float>, grid, dim3(256), 0, s, a);
-    if (hipGetLastError() != hipSuccess) { *err = "gemmx: launch failed"; return 1; }
+    if (hipGetLastError() != hipSuccess) return fail("gemmx: launch failed");
     return 0;
 }
 
-int launch_row_norm(const float* x, int M, int C, float* out, hipStream_t s, const char** err) {
-    if (M <= 0) return 0;
-    hipLaunchKernelGGL(row_norm_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, M, C, out);
-    if (hipGetLastError() != hipSuccess) { *err = "row_norm: launch failed"; return 1; }
+extern "C" int must3r_hip_row_norm(const float* x, int M, int C, float* out, void* stream) {
+    if (M < 0 || C <= 0) return fail("row_norm: bad shape");
+    if (M == 0) return 0;
+    if (!x || !out) return fail("row_norm: null argument");
+    hipLaunchKernelGGL(row_norm_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, M, C, out);
+    if (hipGetLastError() != hipSuccess) return fail("row_norm: launch failed");
     return 0;
 }
 
-int launch_topk_gather(const float* feat, const float* attn, int Bn, int N, int C, int k, float* out_feat, float* out_attn,
-                       long long* out_idx, hipStream_t s, const char** err) {
-    if (Bn <= 0 || k <= 0) return 0;
-    if (N > 4096 || k > N || (C % 4)) { *err = "topk: needs k <= N <= 4096 and C % 4 == 0"; return 1; }
-    hipLaunchKernelGGL(topk_kernel, dim3(Bn), dim3(1024), 0, s, feat, attn, N, C, k, out_feat, out_attn, out_idx);
-    if (hipGetLastError() != hipSuccess) { *err = "topk: launch failed"; return 1; }
+extern "C" int must3r_hip_topk_gather(const float* feat, const float* attn, int n_images, int N, int C, int k, float* out_feat,
+                                      float* out_attn, int64_t* out_idx, void* stream) {
+    if (n_images < 0 || N < 0 || C <= 0 || k < 0) return fail("topk_gather: bad shape");
+    if (n_images == 0 || k == 0) return 0;
+    if (!feat || !attn || !out_feat || !out_attn || !out_idx) return fail("topk_gather: null argument");
+    if (N > 4096 || k > N || (C % 4)) return fail("topk: needs k <= N <= 4096 and C %% 4 == 0");
+    hipLaunchKernelGGL(topk_kernel, dim3(n_images), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), feat, attn, N, C, k, out_feat, out_attn,
+                       reinterpret_cast<long long*>(out_idx));
+    if (hipGetLastError() != hipSuccess) return fail("topk: launch failed");
     return 0;
 }
 
-int launch_weighted_spoc(const float* feat, const float* attn, int Bn, int N, int C, float* out, hipStream_t s, const char** err) {
-    if (Bn <= 0) return 0;
-    hipLaunchKernelGGL(spoc_sum_kernel, dim3((C + 255) / 256, Bn), dim3(256), 0, s, feat, attn, N, C, out);
-    hipLaunchKernelGGL(l2_normalize_rows_kernel, dim3((Bn + 3) / 4), dim3(256), 0, s, out, Bn, C);
-    if (hipGetLastError() != hipSuccess) { *err = "weighted_spoc: launch failed"; return 1; }
+extern "C" int must3r_hip_weighted_spoc(const float* feat, const float* attn, int n_images, int N, int C, float* out, void* stream) {
+    if (n_images < 0 || N < 0 || C <= 0) return fail("weighted_spoc: bad shape");
+    if (n_images == 0) return 0;
+    if (!feat || !attn || !out) return fail("weighted_spoc: null argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(spoc_sum_kernel, dim3((C + 255) / 256, n_images), dim3(256), 0, s, feat, attn, N, C, out);
+    hipLaunchKernelGGL(l2_normalize_rows_kernel, dim3((n_images + 3) / 4), dim3(256), 0, s, out, n_images, C);
+    if (hipGetLastError() != hipSuccess) return fail("weighted_spoc: launch failed");
     return 0;
 }
-
-}  // namespace m3r

@@ -35,7 +35,7 @@ def postprocess(pointmaps, pointmaps_activation=ActivationType.NORM_EXP, compute
     pl = torch.empty((*lead, 3), dtype=torch.float32, device=pm.device)
     cf = torch.empty(lead, dtype=torch.float32, device=pm.device)
     lib = _lib.load()
-    stream = torch.cuda.current_stream(pm.device).cuda_stream
+    stream = _lib.stream_ptr(pm.device)
     out = {"pts3d": p3, "pts3d_local": pl, "conf": cf}
     if not compute_cam:
         with torch.cuda.device(pm.device):   # launch from the tensor's device whatever the caller's current device is

@@ -234,7 +234,7 @@ class SceneExporter:
         self._minmax = torch.empty(6, dtype=torch.float32, device=self.device)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return C.c_void_p(_lib.stream_ptr(self.device))
 
     def _buffers(self, nbytes):
         nbytes = max(int(nbytes), 16)

@@ -122,7 +122,7 @@ def _resample(mode, descs, out, keep):
     with torch.cuda.device(out.device):
         scratch = torch.empty((nbytes,), dtype=torch.uint8, device=out.device)
         _lib.check(lib.must3r_hip_resample(mode, arr, len(descs), out.data_ptr(), scratch.data_ptr(), nbytes,
-                                           torch.cuda.current_stream(out.device).cuda_stream))
+                                           _lib.stream_ptr(out.device)))
     del keep
     return out
 

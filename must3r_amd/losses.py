@@ -52,10 +52,6 @@ def _no_grad_input(pred):
                                       "(forward values only; training is out of scope)")
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def loss_pass(gt_pts, in_camera0, pr_pts, valid, w2c=None, pr_local=None, conf=None, sky=None, gt_scale=None, pr_scale=None,
               pr_warp=None, gt_warp=False, dist_clip=None, loss_in_log=False, sky_loss_value=0.0, alpha=0.0, per_pixel=False):
     """One fused pass (``must3r_hip_metrics_loss``).  ``gt_pts`` [B,V,H,W,3] world points, ``in_camera0`` [B,4,4], ``pr_pts`` [B,V,H,W,3],
@@ -107,7 +103,7 @@ def loss_pass(gt_pts, in_camera0, pr_pts, valid, w2c=None, pr_local=None, conf=N
         raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.must3r_hip_metrics_loss(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
+        _lib.check(lib.must3r_hip_metrics_loss(C.byref(a), _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(dev))))
     return (counts, sums) + ((pix,) if per_pixel else ())
 
 
@@ -140,7 +136,7 @@ def norm_factor(pts, valid, norm_mode='avg_dis', trf=None, return_dist=False):
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.must3r_hip_metrics_factor(_ptr(pts), _ptr(trf), _ptr(valid), B, 1, 1, N, mode, _ptr(factor), _ptr(dist),
-                                                 _ptr(scratch), nbytes, _stream(dev)))
+                                                 _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(dev))))
     return (factor, dist) if return_dist else factor
 
 

@@ -184,10 +184,6 @@ class HipModule(nn.Module):
         return self._ctx
 
     @staticmethod
-    def _stream(dev):
-        return torch.cuda.current_stream(dev).cuda_stream
-
-    @staticmethod
     def _check_input(t, name, dtype=None):
         if not t.is_cuda:
             raise RuntimeError(f"must3r_amd: `{name}` is on {t.device}; the HIP path has no CPU fallback")

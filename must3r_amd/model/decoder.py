@@ -325,7 +325,7 @@ class MUSt3R(HipModule):
                                1 if render else 0, 1 if current_mem is None else 0,
                                len(xs), groups, Nm, ptrs, feats_buf.data_ptr() if return_feats else None,
                                cap, B, stride, C.pointer(cp_struct) if cp_struct is not None else None, 1 if self._causal else 0)
-        rc = ctx.lib.must3r_hip_decode(ctx.handle, C.byref(args), self._stream(dev))
+        rc = ctx.lib.must3r_hip_decode(ctx.handle, C.byref(args), _lib.stream_ptr(dev))
         if cp is not None and rc != 0:
             cp.reraise()          # an exception raised inside the exchange callback (ctypes cannot propagate it) comes out here
         _lib.check(rc)

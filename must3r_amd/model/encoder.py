@@ -77,7 +77,7 @@ class Dust3rEncoder(HipModule):
         pos = torch.empty((B, N, 2), dtype=torch.int64, device=img.device)
         code = operand_dtype(self.precision) | (_lib.ATTN_FP8 if self.attention_fp8 else 0)
         _lib.check(ctx.lib.must3r_hip_encode(ctx.handle, code, img.data_ptr(), B, H, W,
-                                             x.data_ptr(), pos.data_ptr(), self._stream(dev)))
+                                             x.data_ptr(), pos.data_ptr(), _lib.stream_ptr(dev)))
         return x, pos
 
     def from_dust3r(self, state_dict, verbose=True):  # encoder.py:54-61

@@ -23,10 +23,6 @@ import torch.nn as nn
 from . import _lib
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _tokens(x, what):
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise RuntimeError(f"must3r_amd.retrieval: {what} must be a CUDA tensor; the HIP path has no CPU fallback")
@@ -49,7 +45,7 @@ def affine(x, sub, B, b_transposed, bias=None, resid=None, double=False):
     with torch.cuda.device(dev):
         _lib.check(_lib.load().must3r_hip_affine(1 if double else 0, x.data_ptr(), None if subd is None else subd.data_ptr(), Bd.data_ptr(),
                                                  1 if b_transposed else 0, None if biasd is None else biasd.data_ptr(),
-                                                 None if residd is None else residd.data_ptr(), out.data_ptr(), M, N, K, _stream(x)))
+                                                 None if residd is None else residd.data_ptr(), out.data_ptr(), M, N, K, _lib.stream_ptr(x.device)))
     return out
 
 
@@ -81,7 +77,7 @@ def l2_normalize(x, dim):
     for d in x.shape[dim + 1:]:
         inner *= d
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().must3r_hip_l2_normalize(x.data_ptr(), outer, x.shape[dim], inner, x.data_ptr(), _stream(x)))
+        _lib.check(_lib.load().must3r_hip_l2_normalize(x.data_ptr(), outer, x.shape[dim], inner, x.data_ptr(), _lib.stream_ptr(x.device)))
     return x
 
 
@@ -97,7 +93,7 @@ def layernorm_act(x, ln, gelu):
     out = torch.empty_like(x)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().must3r_hip_layernorm_act_f32(x.data_ptr(), None if w is None else w.data_ptr(), None if b is None else b.data_ptr(),
-                                                            float(ln.eps), x.numel() // Cd, Cd, 1 if gelu else 0, out.data_ptr(), _stream(x)))
+                                                            float(ln.eps), x.numel() // Cd, Cd, 1 if gelu else 0, out.data_ptr(), _lib.stream_ptr(x.device)))
     return out
 
 
@@ -107,7 +103,7 @@ def weighted_spoc(feat, attn):
     Bn, N, Cd = feat.shape
     out = torch.empty((Bn, Cd), dtype=torch.float32, device=feat.device)
     with torch.cuda.device(feat.device):
-        _lib.check(_lib.load().must3r_hip_weighted_spoc(feat.data_ptr(), attn.data_ptr(), Bn, N, Cd, out.data_ptr(), _stream(feat)))
+        _lib.check(_lib.load().must3r_hip_weighted_spoc(feat.data_ptr(), attn.data_ptr(), Bn, N, Cd, out.data_ptr(), _lib.stream_ptr(feat.device)))
     return out
 
 
@@ -126,7 +122,7 @@ def how_select_local(feat, attn, nfeat):
     oi = torch.empty((Bn, k), dtype=torch.int64, device=feat.device)
     with torch.cuda.device(feat.device):
         _lib.check(_lib.load().must3r_hip_topk_gather(feat.data_ptr(), attn.data_ptr(), Bn, N, Cd, k, of.data_ptr(), oa.data_ptr(), oi.data_ptr(),
-                                                      _stream(feat)))
+                                                      _lib.stream_ptr(feat.device)))
     return of, oa, oi
 
 
@@ -195,7 +191,7 @@ class RetrievalModel(nn.Module):
         Bn, N, Cd = proj.shape
         attention = torch.empty((Bn, N), dtype=torch.float32, device=proj.device)
         with torch.cuda.device(proj.device):
-            _lib.check(_lib.load().must3r_hip_row_norm(proj.data_ptr(), Bn * N, Cd, attention.data_ptr(), _stream(proj)))
+            _lib.check(_lib.load().must3r_hip_row_norm(proj.data_ptr(), Bn * N, Cd, attention.data_ptr(), _lib.stream_ptr(proj.device)))
         post = proj if isinstance(self.postwhiten, nn.Identity) else self.postwhiten(proj)
         return post, attention
 

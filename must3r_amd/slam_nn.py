@@ -23,17 +23,13 @@ def _check_pts(pts):
     return pts.reshape(-1, 3).float().contiguous()
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def nn_distances(db, q):
     """Exact 1-NN Euclidean distances of q [n,3] to db [m,3] (cuda fp32) -> cuda fp32 [n]; +inf if db is empty."""
     q = _check_pts(q)
     out = torch.empty((q.shape[0],), dtype=torch.float32, device=q.device)
     n_db = 0 if db is None else int(db.shape[0])
     with torch.cuda.device(q.device):
-        _lib.check(_lib.load().must3r_hip_nn_query(db.data_ptr() if n_db else None, n_db, q.data_ptr(), q.shape[0], out.data_ptr(), _stream(q)))
+        _lib.check(_lib.load().must3r_hip_nn_query(db.data_ptr() if n_db else None, n_db, q.data_ptr(), q.shape[0], out.data_ptr(), _lib.stream_ptr(q.device)))
     return out
 
 
@@ -43,7 +39,7 @@ def quadrant_ids(pts, cam_center, quadrant_divider):
     out = torch.empty((pts.shape[0],), dtype=torch.int32, device=pts.device)
     cc = (C.c_float * 3)(*[float(v) for v in torch.as_tensor(cam_center).reshape(3).tolist()])
     with torch.cuda.device(pts.device):
-        _lib.check(_lib.load().must3r_hip_quadrant_ids(pts.data_ptr(), pts.shape[0], cc, int(quadrant_divider), out.data_ptr(), _stream(pts)))
+        _lib.check(_lib.load().must3r_hip_quadrant_ids(pts.data_ptr(), pts.shape[0], cc, int(quadrant_divider), out.data_ptr(), _lib.stream_ptr(pts.device)))
     return out
 
 
@@ -166,7 +162,7 @@ class BVH_hip(Base_NN):
         pts, qid = (self.all_points.data_ptr(), self.quadrants.data_ptr()) if self.n else (None, None)   # an empty map: an empty index
         with torch.cuda.device(dev):
             _lib.check(lib.must3r_hip_nn_index_build(pts, qid, self.n, self.quadrant_divider, self.index.data_ptr(), scratch.data_ptr(),
-                                                     torch.cuda.current_stream(dev).cuda_stream))
+                                                     _lib.stream_ptr(dev)))
         self.dirty = False
 
     def query_device(self, pts, cam_center=None, **kw):
@@ -181,7 +177,7 @@ class BVH_hip(Base_NN):
             cc = (C.c_float * 3)(*[float(v) for v in torch.as_tensor(cam_center).reshape(3).tolist()])
         with torch.cuda.device(pts.device):
             _lib.check(_lib.load().must3r_hip_nn_index_query(self.index.data_ptr(), pts.data_ptr(), pts.shape[0], cc, self.quadrant_divider,
-                                                             out.data_ptr(), _stream(pts)))
+                                                             out.data_ptr(), _lib.stream_ptr(pts.device)))
         return out
 
     def query(self, pts, cam_center=None, **kw):
