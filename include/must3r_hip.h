@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 14
+#define MUST3R_HIP_ABI_VERSION 15
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -516,6 +516,27 @@ int must3r_hip_op_attention_ex(const must3r_hip_attn_op* d, void* stream);
 int must3r_hip_op_layernorm(int dtype, const float* x, const float* add, const float* w, const float* b,
                             void* out16, void* out16_lo, float* out32, float* copy32, int M, int C, float eps,
                             void* stream);
+/* ABI 15.  Every LayerNorm launch form the model uses, reachable one by one (tests): the fields of the launch descriptor one for one.  Forwards to the
+ * launcher must3r_hip_decode uses; the kernel is chosen as there (one row per wave below 65536 rows or with LN_ROWS = 0, row-walking waves otherwise)
+ * and reported through `picked` (optional): "ln", "ln_rows/3" (C <= 768), "ln_rows/4".  Nothing here changes what must3r_hip_op_layernorm does.
+ *   input: exactly one of x (fp32) / x16 (16-bit) [M][C]; add (optional, fp32) is added before the statistics
+ *   outputs, all optional: out16 / out16_lo (= T(y - float(T(y)))) / out16_dup (= out16) with row stride ld16 (0 = C); out32; copy32 = x + add (fp32);
+ *     raw16 = T(x + add), fp16 saturated at +-65504.  The three out16* need out16.
+ *   rows_per_group > 0: row r is of group g = r / rows_per_group and uses w + g C, b + g C; add is [rows_per_group][C] and applied to groups < add_groups.
+ * Refused with an error: both or neither of x / x16, null w / b, ld16 non-zero and < C or not a multiple of 4, negative add_groups / rows_per_group,
+ * C > 1024 or not a multiple of 4. */
+typedef struct must3r_hip_ln_op {
+    int32_t dtype;                     /* MUST3R_BF16 / MUST3R_F16 */
+    const float* x; const void* x16; const float* add; const float* w; const float* b;
+    void* out16; void* out16_lo; void* out16_dup;
+    int32_t ld16;
+    float* out32; float* copy32; void* raw16;
+    int32_t M, C;
+    float eps;
+    int32_t rows_per_group, add_groups;
+    const char** picked;
+} must3r_hip_ln_op;
+int must3r_hip_op_layernorm_ex(const must3r_hip_ln_op* d, void* stream);
 int must3r_hip_op_im2col(int dtype, const float* img, void* out16, int n_views, int H, int W, void* stream);
 int must3r_hip_op_cast(int dtype, const float* in, void* out16, void* out16_lo, size_t n, void* stream);
 

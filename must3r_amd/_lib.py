@@ -15,7 +15,7 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 14
+ABI_VERSION = 15
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
@@ -71,6 +71,14 @@ class AttnOp(C.Structure):
                 ("nsplit", C.c_int32), ("scratch", C.c_void_p), ("total_q_rows", C.c_int32), ("dense_rows", C.c_int32),
                 ("stage", C.c_int32), ("slot_o", C.c_void_p), ("slot_ml", C.c_void_p), ("p16", C.c_int32), ("nslots", C.c_int32),
                 ("stride_o", C.c_int64), ("stride_ml", C.c_int64), ("picked", C.POINTER(C.c_char_p))]
+
+
+class LnOp(C.Structure):
+    """must3r_hip_ln_op: one LayerNorm launch, every field of the kernels' descriptor (include/must3r_hip.h, ABI 15)."""
+    _fields_ = [("dtype", C.c_int32), ("x", C.c_void_p), ("x16", C.c_void_p), ("add", C.c_void_p), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("out16", C.c_void_p), ("out16_lo", C.c_void_p), ("out16_dup", C.c_void_p), ("ld16", C.c_int32),
+                ("out32", C.c_void_p), ("copy32", C.c_void_p), ("raw16", C.c_void_p), ("M", C.c_int32), ("C", C.c_int32), ("eps", C.c_float),
+                ("rows_per_group", C.c_int32), ("add_groups", C.c_int32), ("picked", C.POINTER(C.c_char_p))]
 
 
 class ExportView(C.Structure):
@@ -152,6 +160,7 @@ PROTOTYPES = {
     "must3r_hip_op_attention": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, i32, vp]),
     "must3r_hip_op_attention_ex": (i32, [P(AttnOp), vp]),
     "must3r_hip_op_layernorm": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, fp, vp]),
+    "must3r_hip_op_layernorm_ex": (i32, [P(LnOp), vp]),
     "must3r_hip_op_im2col": (i32, [i32, vp, vp, i32, i32, i32, vp]),
     "must3r_hip_op_cast": (i32, [i32, vp, vp, vp, sz, vp]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),

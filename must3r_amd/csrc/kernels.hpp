@@ -183,7 +183,7 @@ const char* attention_last_kernel();   // main kernel of the calling thread's la
 struct LnArgs {
     const float* x;      // [M,C] fp32 input, or nullptr to read x16 instead
     const void* x16;     // optional 16-bit input [M,C] (memory_mode 'raw': LayerNorm of stored 16-bit tokens)
-    void* raw16;         // optional 16-bit copy of x (+add) before normalisation (memory_mode 'raw' rows)
+    void* raw16;         // optional 16-bit copy of x (+add) before normalisation (memory_mode 'raw' rows); fp16: saturated at +-65504 (cvt4_sat)
     const float* add;    // optional [M,C] added to x before the statistics (feedback offset)
     const float* w; const float* b;
     void* out16;         // optional 16-bit [M,C]
@@ -200,6 +200,7 @@ struct LnArgs {
     int add_groups;
 };
 int launch_layernorm(DType dt, const LnArgs& a, hipStream_t s, const char** err);
+const char* layernorm_last_kernel();   // kernel of the calling thread's last launch_layernorm: "ln", "ln_rows/3", "ln_rows/4"
 
 // img fp32 [V,3,H,W] -> patches 16-bit [V*gh*gw, 3*16*16]; column = c*256 + i*16 + j
 int launch_im2col(DType dt, const float* img, void* out16, int V, int H, int W, hipStream_t s, const char** err);

@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(256) ln_kernel(const LnArgs p) {
             else v[i] = __builtin_convertvector(*reinterpret_cast<const v4*>(reinterpret_cast<const T*>(p.x16) + (size_t)row * p.C + c), f32x4);
             if (addp) v[i] += *reinterpret_cast<const f32x4*>(addp + c);
             if (p.copy32) *reinterpret_cast<f32x4*>(p.copy32 + (size_t)row * p.C + c) = v[i];
-            if (p.raw16) *reinterpret_cast<v4*>(reinterpret_cast<T*>(p.raw16) + (size_t)row * p.C + c) = cvt4<T>(v[i]);
+            if (p.raw16) *reinterpret_cast<v4*>(reinterpret_cast<T*>(p.raw16) + (size_t)row * p.C + c) = cvt4_sat<T>(v[i]);
             s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
         }
     }
@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(256) ln_rows_kernel(const LnArgs p) {
             if (act[i]) {
                 if (addp) v[i] += *reinterpret_cast<const f32x4*>(addp + c);
                 if (p.copy32) *reinterpret_cast<f32x4*>(p.copy32 + (size_t)row * p.C + c) = v[i];
-                if (p.raw16) *reinterpret_cast<v4*>(reinterpret_cast<T*>(p.raw16) + (size_t)row * p.C + c) = cvt4<T>(v[i]);
+                if (p.raw16) *reinterpret_cast<v4*>(reinterpret_cast<T*>(p.raw16) + (size_t)row * p.C + c) = cvt4_sat<T>(v[i]);
                 s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
             }
         }
@@ -223,6 +223,8 @@ __global__ void __launch_bounds__(256) ln_rows_kernel(const LnArgs p) {
 
 // M3R_LN_ROWS (A/B instrument): 0 = one row per wave (ln_kernel, r01-r03), 1 = row-walking waves with the next row in flight (default)
 static int ln_rows_mode() { return opt(OPT_LN_ROWS); }
+static thread_local const char* g_ln_pick = "";
+const char* layernorm_last_kernel() { return g_ln_pick; }
 template <class T>
 static void launch_ln_t(const LnArgs& a, hipStream_t s) {
     // Measured (profiles/r04_ln_rows_ab.txt, same bits): the walk wins where the rows stream from HBM -- the render batch, 307200 x 768:
@@ -231,10 +233,12 @@ static void launch_ln_t(const LnArgs& a, hipStream_t s) {
     // Hence: only launches whose rows cannot be MALL-resident (> 64 k rows = 300+ MB).
     const int grid_one = (a.M + 3) / 4;
     if (ln_rows_mode() == 0 || a.M < 65536) {
+        g_ln_pick = "ln";
         hipLaunchKernelGGL(ln_kernel<T>, dim3(grid_one), dim3(256), 0, s, a);
         return;
     }
     const int grid = 256 * 8;   // 8 resident blocks per CU (32 waves): every wave slot of the chip holds one walker
+    g_ln_pick = a.C <= 768 ? "ln_rows/3" : "ln_rows/4";
     if (a.C <= 768) hipLaunchKernelGGL((ln_rows_kernel<T, 3>), dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((ln_rows_kernel<T, 4>), dim3(grid), dim3(256), 0, s, a);
 }
@@ -479,6 +483,27 @@ __global__ void postprocess_kernel(const float* __restrict__ pm, float* __restri
 
 }  // namespace m3r
 using namespace m3r;
+
+// ABI 15 (tests): every field of LnArgs, one launch through launch_layernorm; the kernel is the one the product's rule picks (M, LN_ROWS)
+extern "C" int must3r_hip_op_layernorm_ex(const must3r_hip_ln_op* d, void* stream) {
+    if (!d) return fail("op_layernorm_ex: null descriptor");
+    if (d->dtype != MUST3R_BF16 && d->dtype != MUST3R_F16) return fail("op_layernorm_ex: bad dtype");
+    if ((d->x != nullptr) == (d->x16 != nullptr)) return fail("op_layernorm_ex: exactly one of x / x16 is needed");
+    if (!d->w || !d->b) return fail("op_layernorm_ex: w and b are needed");
+    if (d->M < 0 || d->C <= 0) return fail("op_layernorm_ex: M >= 0 and C > 0 are needed");
+    if (d->ld16 != 0 && (d->ld16 < d->C || d->ld16 % 4)) return fail("op_layernorm_ex: ld16 = %d must be 0 or a multiple of 4 that is >= C = %d", d->ld16, d->C);
+    if (d->add_groups < 0) return fail("op_layernorm_ex: add_groups = %d is negative", d->add_groups);
+    if (d->rows_per_group < 0) return fail("op_layernorm_ex: rows_per_group = %d is negative", d->rows_per_group);
+    LnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = d->x; a.x16 = d->x16; a.raw16 = d->raw16; a.add = d->add; a.w = d->w; a.b = d->b;
+    a.out16 = d->out16; a.out16_lo = d->out16_lo; a.out16_dup = d->out16_dup; a.ld16 = d->ld16; a.out32 = d->out32; a.copy32 = d->copy32;
+    a.M = d->M; a.C = d->C; a.eps = d->eps; a.rows_per_group = d->rows_per_group; a.add_groups = d->add_groups;
+    const char* err = "";
+    if (launch_layernorm((DType)d->dtype, a, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    if (d->picked && d->M > 0) *d->picked = layernorm_last_kernel();
+    return 0;
+}
 
 extern "C" int must3r_hip_postprocess_act(const float* pm, int activation, float* pts3d, float* pts3d_local, float* conf, size_t npix, void* stream) {
     if (!pm || !pts3d || !pts3d_local || !conf) return fail("postprocess: null argument");

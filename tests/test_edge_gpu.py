@@ -180,3 +180,30 @@ def test_fp16_overflow_saturates_and_bf16_is_the_fallback():
     record("fp16_overflow", fp16w2=errs16, bf16=errsb)
     assert torch.isfinite(out16["x"]).all() and torch.isfinite(out16["render"]).all() and torch.isfinite(out16["update"]).all()
     assert max(errsb.values()) < TOL["bf16"], errsb
+
+
+def test_fp16_overflow_saturates_in_the_raw_token_memory():
+    """memory_mode 'raw' stores the decoder's 16-bit tokens themselves: a residual channel beyond the fp16 range (block 0's MLP bias at 1e5, so every later
+    layer's input carries it) is stored as +-65504 like every other 16-bit copy of the residual stream, not as inf.  With inf in the memory the caller holds,
+    the LayerNorm that reads the stored tokens back makes every K|V row NaN; the pointmaps stay finite even then (the attention drops such keys), so the
+    memory itself is what is asserted.  bf16 keeps the value (its range is fp32's)."""
+    cfg = SMALL
+    sde = S.make_encoder_state_dict(cfg, 0)
+    sdd = {k: v.clone() for k, v in S.make_decoder_state_dict(cfg, 0).items()}
+    sdd["blocks_dec.0.mlp.fc2.bias"][[3, 90]] = 1.0e5
+    imgs, ts = S.make_images(3, 224, 224, 4)
+    from must3r_amd.engine import run_scene
+    seen = {}
+    for precision in ("fp16w2", "fp16", "bf16"):
+        enc, dec = _modules(cfg, sde, sdd, precision)
+        dec.change_memory_mode("raw")
+        out = run_scene(enc, dec, imgs.cuda(), ts.cuda(), mem_batches=[2, 1])
+        torch.cuda.synchronize()
+        mem = [m.float() for m in out["mem"][0]]
+        seen[precision] = dict(mem_finite=[bool(torch.isfinite(m).all()) for m in mem], mem_absmax=[float(m.abs().max()) for m in mem],
+                               out_finite=bool(torch.isfinite(out["render"]).all() and torch.isfinite(out["update"]).all()))
+    record("fp16_overflow_raw_memory", **seen)
+    for precision, r in seen.items():
+        assert all(r["mem_finite"]) and r["out_finite"], (precision, r)
+        lo, hi = (9.9e4, 1.01e5) if precision == "bf16" else (65504.0, 65504.0)
+        assert r["mem_absmax"][0] < 100.0 and all(lo <= a <= hi for a in r["mem_absmax"][1:]), (precision, r)

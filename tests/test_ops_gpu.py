@@ -613,6 +613,42 @@ def test_im2col_cast_postprocess(lib, dt):
         assert torch.allclose(o[k].cpu(), r[k], rtol=1e-5, atol=1e-6), k
 
 
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+def test_im2col_cast_beyond_one_grid_sweep(lib, dt):
+    """im2col_kernel and cast_kernel are grid-stride loops whose grids are capped (4096 / 8192 blocks of 256); the shapes above fit in one sweep.  Bit for bit
+    against torch where a thread takes several elements: the encoder chunk the bench launches (40 views of 384 x 512: 11520 blocks' worth of work), portrait
+    512 x 384 views, and a cast of more than 8192 * 256 float4 whose count is no multiple of 256, with and without the low part.  Canary tails: nothing
+    behind the last element is written."""
+    tdt = DT[dt][1]
+    L = lib.load()
+    g = torch.Generator(device="cuda").manual_seed(17)
+    for (V, H, W) in ((40, 384, 512), (7, 512, 384)):
+        ntok = V * (H // 16) * (W // 16)
+        assert V != 40 or (ntok * 96 + 255) // 256 > 2 * 4096
+        img = torch.randn((V, 3, H, W), device="cuda", generator=g)
+        out = torch.full((ntok + 2, 768), 0x7E55, dtype=torch.int16, device="cuda")
+        lib.check(L.must3r_hip_op_im2col(DT[dt][0], P(img), P(out), V, H, W, stream()))
+        torch.cuda.synchronize()
+        ref = torch.nn.functional.unfold(img, kernel_size=16, stride=16).transpose(1, 2).reshape(ntok, 768)
+        assert torch.equal(out[:ntok], ref.to(tdt).view(torch.int16)), (V, H, W)
+        assert (out[ntok:] == 0x7E55).all()
+        del img, out, ref
+    n4 = 2 * 8192 * 256 + 1000 + 3
+    assert n4 > 8192 * 256 and n4 % 256
+    n = 4 * n4
+    x = torch.randn((n,), device="cuda", generator=g) * 10
+    for with_lo in (True, False):
+        hi = torch.full((n + 64,), 0x7E55, dtype=torch.int16, device="cuda")
+        lo = torch.full((n + 64,), 0x7E55, dtype=torch.int16, device="cuda")
+        lib.check(L.must3r_hip_op_cast(DT[dt][0], P(x), P(hi), P(lo) if with_lo else None, n, stream()))
+        torch.cuda.synchronize()
+        assert torch.equal(hi[:n], x.to(tdt).view(torch.int16)) and (hi[n:] == 0x7E55).all()
+        if with_lo:
+            assert torch.equal(lo[:n], (x - x.to(tdt).float()).to(tdt).view(torch.int16)) and (lo[n:] == 0x7E55).all()
+        else:
+            assert (lo == 0x7E55).all()
+
+
 @pytest.mark.parametrize("M", [768, 196])
 def test_gemm_ln_fold(lib, M):
     """LN fold of the one-view memory update (must3r_hip_op_gemm_lnfold): a residual GEMM leaves the new rows rounded to fp16 plus per
