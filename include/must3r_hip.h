@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 15
+#define MUST3R_HIP_ABI_VERSION 16
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -188,6 +188,12 @@ int must3r_hip_postprocess(const float* pointmaps, float* pts3d, float* pts3d_lo
 enum { MUST3R_ACT_NORM_EXP = 0, MUST3R_ACT_LINEAR = 1 };
 int must3r_hip_postprocess_act(const float* pointmaps, int activation, float* pts3d, float* pts3d_local, float* conf, size_t npix,
                                void* stream);
+/* backward of the activation (ABI 16): grad_raw fp32 [npix,7] from raw [npix,7] and the gradients at pts3d [npix,3], pts3d_local
+ * [npix,3] and conf [npix] (any of the three may be NULL = zero).  Nothing is saved by the forward: d = |x| and x^ = x / d are recomputed.
+ * NORM_EXP, y = x / max(d, 1e-8) * expm1(d):  grad_x = (expm1(d) / d) (g - <x^, g> x^) + e^d <x^, g> x^ for d >= 1e-8, the derivative of
+ * the clipped expression below that, 0 at d = 0.  LINEAR: the gradients pass through.  Channel 6: g * exp(raw[6]) in both. */
+int must3r_hip_postprocess_act_grad(const float* pointmaps, int activation, const float* grad_pts3d, const float* grad_pts3d_local,
+                                    const float* grad_conf, float* grad_pointmaps, size_t npix, void* stream);
 
 /* postprocess(..., compute_cam=True) (engine/inference.py:16-48), SURVEY.md section 8f rank 1: the activation above
  * plus, per view, focal = dust3r estimate_focal_knowing_depth(pts3d_local, pp=(W/2,H/2), 'weiszfeld')
@@ -370,6 +376,49 @@ int must3r_hip_metrics_loss(const must3r_hip_metrics_loss_args* args, void* scra
 size_t must3r_hip_metrics_factor_scratch_bytes(int n_scenes, int n_views, int H, int W, int mode);
 int must3r_hip_metrics_factor(const float* pts, const float* trf, const uint8_t* valid, int n_scenes, int n_views, int H, int W, int mode,
                               float* factor, float* dist, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- ABI 16: the backward pass of must3r_hip_metrics_loss -- the gradient of the Regr3D / ConfLoss figures at pr_pts, pr_local and conf;
+ * metrics.hip ----
+ * must3r_hip_metrics_loss_grad takes the argument block of the forward call (its outputs counts / sums / pix_* / msk_* are not used) and
+ * the block below.  The selections valid_g / valid_l / sky_g / sky_l and the chain x -> warp -> / pr_scale -> log map -> |. - target| are
+ * recomputed per pixel exactly as the forward computes them; ground truth is read only under valid.  With u = r / |r| (0 where r = 0) and
+ * J(x) = (log1p(d) / d)(I - x^ x^T) + x^ x^T / (1 + d) the (symmetric) Jacobian of the log map and of the warp (0 at d = 0):
+ *   direct term  grad_pts(p) = J_warp(x) J_log(y) (omega_g(p) u_g) / pr_scale[b] on valid_g pixels, grad_local likewise on valid_l pixels
+ *                (no warp; log map as the forward applies it); sky pixels and unselected pixels get exactly 0
+ *   weighting    MUST3R_LOSS_W_SCALAR  omega = w (reduction 'sum')            MUST3R_LOSS_W_MEAN  omega = w / N (reduction 'mean')
+ *                MUST3R_LOSS_W_CONF    omega = w conf / N, and grad_conf = w_g [sel_g](l_g - alpha / conf) / N_g + w_l [sel_l](...) / N_l
+ *                MUST3R_LOSS_W_PIXEL   omega = w[p], w_g / w_l fp32 [B][V][H][W] (reduction 'none')
+ *                In the first three w_g / w_l point to one device scalar each; N_g / N_l are the batch totals of counts (the forward's
+ *                output, read on the device); a term with N = 0 contributes nothing.  The scalar weights are applied last, so the
+ *                gradients are linear in them to the rounding of that one product (equal w_g and w_l are factored out).
+ *   scale path   for the scenes with own_factor[b] != 0 (pr_scale[b] was computed from pr_pts with factor_mode): with
+ *                S_b = -(1 / pr_scale[b]) sum <g_y(p), y(p)> over the valid_g pixels of the global and the valid_l pixels of the local
+ *                term (g_y the gradient at y = warp(x) / pr_scale), every valid pixel gets grad_pts(p) += S_b dps/dx(p):
+ *                AVG_DIS x^ / (n_b + 1e-8), AVG_LOG1P x^ / ((1 + d)(n_b + 1e-8)), SQRT_DIS sqrt(pr_scale) x^ / (sqrt(d) n_b), 0 at d = 0,
+ *                n_b = n_valid[b] the valid pixels of the scene.  A factor at the 1e-8 clip and MEDIAN_DIS (detached in the reference)
+ *                have no scale path: pass n_own = 0 or own_factor = 0 for them.  n_own (host): the number of scenes with own_factor set;
+ *                0 skips the reduction launches.
+ * Every element of grad_pts, grad_local (iff pr_local) and grad_conf (optional; required by W_CONF) is written exactly once, zeros
+ * included; nothing is accumulated across launches and no floating-point atomics are used: the sums of S_b are fp64 in lane / wave /
+ * block / slab order, so the gradients are bit-identical from run to run. */
+enum { MUST3R_LOSS_W_SCALAR = 0, MUST3R_LOSS_W_MEAN = 1, MUST3R_LOSS_W_CONF = 2, MUST3R_LOSS_W_PIXEL = 3 };
+typedef struct must3r_hip_metrics_loss_grad_args {
+    const float* w_g;             /* one device scalar, or [B][V][H][W] with W_PIXEL */
+    const float* w_l;             /* likewise; required with pr_local */
+    int32_t weighting;            /* MUST3R_LOSS_W_* */
+    int32_t factor_mode;          /* MUST3R_NORM_* of the scale path; read only when n_own > 0 */
+    int32_t n_own;                /* scenes with own_factor set (host copy of the count) */
+    int32_t reserved;
+    const int64_t* counts;        /* [B][V][2], the forward's output; required by W_MEAN / W_CONF */
+    const uint8_t* own_factor;    /* [B]; required when n_own > 0 */
+    const int64_t* n_valid;       /* [B]; required when n_own > 0 */
+    float* grad_pts;              /* [B][V][H][W][3] */
+    float* grad_local;            /* [B][V][H][W][3], required iff pr_local */
+    float* grad_conf;             /* [B][V][H][W] or NULL */
+} must3r_hip_metrics_loss_grad_args;
+size_t must3r_hip_metrics_loss_grad_scratch_bytes(int n_scenes, int n_views, int H, int W);
+int must3r_hip_metrics_loss_grad(const must3r_hip_metrics_loss_args* args, const must3r_hip_metrics_loss_grad_args* grad, void* scratch,
+                                 size_t scratch_bytes, void* stream);
 
 /* ---- ABI 9: image ingestion -- the reference's three image loaders in front of the forwards ----
  * must3r/demo/inference.py:63-76 load_images: ImgNorm (ToTensor, Normalize(0.5, 0.5)), then get_resize_function

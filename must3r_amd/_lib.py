@@ -15,10 +15,11 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 15
+ABI_VERSION = 16
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
+LOSS_W_SCALAR, LOSS_W_MEAN, LOSS_W_CONF, LOSS_W_PIXEL = range(4)
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
 
@@ -97,6 +98,13 @@ class MetricsLossArgs(C.Structure):
                 ("pix_g", C.c_void_p), ("pix_l", C.c_void_p), ("msk_g", C.c_void_p), ("msk_l", C.c_void_p)]
 
 
+class MetricsLossGradArgs(C.Structure):
+    """must3r_hip_metrics_loss_grad_args: weights, counts, scale path and outputs of the loss backward (include/must3r_hip.h, ABI 16)."""
+    _fields_ = [("w_g", C.c_void_p), ("w_l", C.c_void_p), ("weighting", C.c_int32), ("factor_mode", C.c_int32), ("n_own", C.c_int32),
+                ("reserved", C.c_int32), ("counts", C.c_void_p), ("own_factor", C.c_void_p), ("n_valid", C.c_void_p),
+                ("grad_pts", C.c_void_p), ("grad_local", C.c_void_p), ("grad_conf", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -118,6 +126,7 @@ PROTOTYPES = {
     "must3r_hip_decode": (i32, [vp, P(DecodeArgs), vp]),
     "must3r_hip_postprocess": (i32, [vp, vp, vp, vp, sz, vp]),
     "must3r_hip_postprocess_act": (i32, [vp, i32, vp, vp, vp, sz, vp]),
+    "must3r_hip_postprocess_act_grad": (i32, [vp, i32, vp, vp, vp, vp, sz, vp]),
     "must3r_hip_postprocess_cam_scratch_bytes": (sz, [i32, i32, i32]),
     "must3r_hip_postprocess_cam": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "must3r_hip_postprocess_cam_act": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
@@ -147,6 +156,8 @@ PROTOTYPES = {
     "must3r_hip_metrics_loss": (i32, [P(MetricsLossArgs), vp, sz, vp]),
     "must3r_hip_metrics_factor_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
     "must3r_hip_metrics_factor": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "must3r_hip_metrics_loss_grad_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_metrics_loss_grad": (i32, [P(MetricsLossArgs), P(MetricsLossGradArgs), vp, sz, vp]),
     "must3r_hip_resample_coeffs": (i32, [i32, i32, i32, P(i32), vp, vp]),
     "must3r_hip_image_scratch_bytes": (sz, [i32, P(ImageDesc), i32]),
     "must3r_hip_resample": (i32, [i32, P(ImageDesc), i32, vp, vp, sz, vp]),

@@ -481,6 +481,45 @@ __global__ void postprocess_kernel(const float* __restrict__ pm, float* __restri
     }
 }
 
+// backward of norm_exp3: o = J(v)^T g, J = (expm1(d) / d)(I - v^ v^T) + e^d v^ v^T (symmetric); below the clip of d the derivative of the
+// clipped expression, 0 at d = 0.  Recomputed from v: the forward saves nothing.
+__device__ __forceinline__ void norm_exp3_grad(const float* v, const float* g, float* o) {
+    const float d = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (d == 0.f) { o[0] = o[1] = o[2] = 0.f; return; }
+    const float c = fmaxf(d, 1e-8f);
+    const float h = expm1f(d) / c;
+    const float b = d >= 1e-8f ? expf(d) - h : expf(d) * d / c;
+    const float s = (v[0] * g[0] + v[1] * g[1] + v[2] * g[2]) / d * b;
+    o[0] = h * g[0] + s * (v[0] / d);
+    o[1] = h * g[1] + s * (v[1] / d);
+    o[2] = h * g[2] + s * (v[2] / d);
+}
+
+template <bool LINEAR>
+__global__ void postprocess_grad_kernel(const float* __restrict__ pm, const float* __restrict__ g3, const float* __restrict__ gl,
+                                        const float* __restrict__ gc, float* __restrict__ out, size_t npix) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+        float v[7], ga[3], gb[3], o[7];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) v[k] = pm[i * 7 + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            ga[k] = g3 ? g3[i * 3 + k] : 0.f;
+            gb[k] = gl ? gl[i * 3 + k] : 0.f;
+        }
+        if constexpr (LINEAR) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { o[k] = ga[k]; o[3 + k] = gb[k]; }
+        } else {
+            norm_exp3_grad(v, ga, o);
+            norm_exp3_grad(v + 3, gb, o + 3);
+        }
+        o[6] = gc ? gc[i] * expf(v[6]) : 0.f;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) out[i * 7 + k] = o[k];
+    }
+}
+
 }  // namespace m3r
 using namespace m3r;
 
@@ -514,6 +553,21 @@ extern "C" int must3r_hip_postprocess_act(const float* pm, int activation, float
     if (activation == MUST3R_ACT_LINEAR) hipLaunchKernelGGL(postprocess_kernel<true>, dim3(grid), dim3(256), 0, s, pm, pts3d, pts3d_local, conf, npix);
     else hipLaunchKernelGGL(postprocess_kernel<false>, dim3(grid), dim3(256), 0, s, pm, pts3d, pts3d_local, conf, npix);
     if (hipGetLastError() != hipSuccess) return fail("postprocess: launch failed");
+    return 0;
+}
+
+extern "C" int must3r_hip_postprocess_act_grad(const float* pm, int activation, const float* grad_pts3d, const float* grad_pts3d_local,
+                                               const float* grad_conf, float* grad_pm, size_t npix, void* stream) {
+    if (!pm || !grad_pm) return fail("postprocess_act_grad: null argument");
+    if (activation != MUST3R_ACT_NORM_EXP && activation != MUST3R_ACT_LINEAR) return fail("postprocess_act_grad: unknown activation %d", activation);
+    if (!npix) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int grid = (int)((npix + 255) / 256 < 8192 ? (npix + 255) / 256 : 8192);
+    if (activation == MUST3R_ACT_LINEAR)
+        hipLaunchKernelGGL(postprocess_grad_kernel<true>, dim3(grid), dim3(256), 0, s, pm, grad_pts3d, grad_pts3d_local, grad_conf, grad_pm, npix);
+    else
+        hipLaunchKernelGGL(postprocess_grad_kernel<false>, dim3(grid), dim3(256), 0, s, pm, grad_pts3d, grad_pts3d_local, grad_conf, grad_pm, npix);
+    if (hipGetLastError() != hipSuccess) return fail("postprocess_act_grad: launch failed");
     return 0;
 }
 

@@ -8,7 +8,7 @@ this module's namespace::
 Every scalar (``ConfLoss``'s loss and ``details``, ``Regr3D``'s ``details``, ``L21``'s mean, ``eval_metric``) comes out of the fused passes
 of csrc/metrics.hip: one read of the inputs, rigid transforms and scales applied per pixel, fp64 sums per (scene, view) combined in a
 fixed order.  Per-pixel tensors exist only where a caller asks for them (``reduction='none'``, ``get_all_pts3d``).  Forward only: a
-``pred`` that requires grad raises.  As everywhere in the package, CPU tensors raise; there is no fallback.
+``pred`` that requires grad raises (``must3r_amd.train_losses`` subclasses these criteria with a backward pass).  As everywhere in the package, CPU tensors raise; there is no fallback.
 
 An empty selection has count 0 and mean NaN (``torch.mean`` of nothing); ``ConfLoss`` turns that into 0 as the reference does.
 """
@@ -52,18 +52,16 @@ def _no_grad_input(pred):
                                       "(forward values only; training is out of scope)")
 
 
-def loss_pass(gt_pts, in_camera0, pr_pts, valid, w2c=None, pr_local=None, conf=None, sky=None, gt_scale=None, pr_scale=None,
-              pr_warp=None, gt_warp=False, dist_clip=None, loss_in_log=False, sky_loss_value=0.0, alpha=0.0, per_pixel=False):
-    """One fused pass (``must3r_hip_metrics_loss``).  ``gt_pts`` [B,V,H,W,3] world points, ``in_camera0`` [B,4,4], ``pr_pts`` [B,V,H,W,3],
-    ``valid`` [B,V,H,W].  Returns ``(counts int64 [B,V,2], sums fp64 [B,V,4])`` on the device -- (global, local) and (l global, l local,
-    conf-weighted global, conf-weighted local) -- plus ``(pix_g, pix_l, msk_g, msk_l)`` with ``per_pixel``."""
-    lib = _lib.load()
+def loss_args(gt_pts, in_camera0, pr_pts, valid, w2c=None, pr_local=None, conf=None, sky=None, gt_scale=None, pr_scale=None,
+              pr_warp=None, gt_warp=False, dist_clip=None, loss_in_log=False, sky_loss_value=0.0, alpha=0.0):
+    """The argument block of ``must3r_hip_metrics_loss`` (and of its backward) without outputs: ``(block, keep, (B, V, H, W), device)``;
+    ``keep`` holds the converted tensors, which must outlive the launch: only their addresses go into the block."""
     gt_pts, pr_pts = _f32(gt_pts, "gt_pts"), _f32(pr_pts, "pr_pts")
     if gt_pts.ndim != 5 or gt_pts.shape[-1] != 3 or pr_pts.shape != gt_pts.shape:
         raise ValueError(f"loss_pass: gt_pts {tuple(gt_pts.shape)} and pr_pts {tuple(pr_pts.shape)} must both be [B,V,H,W,3]")
     B, V, H, W, _ = gt_pts.shape
     dev = gt_pts.device
-    keep = [gt_pts, pr_pts]                     # converted copies must outlive the launch: only their addresses go into the argument block
+    keep = [gt_pts, pr_pts]
 
     def opt(t, conv, what, shape):
         if t is None:
@@ -90,6 +88,16 @@ def loss_pass(gt_pts, in_camera0, pr_pts, valid, w2c=None, pr_local=None, conf=N
     a.dist_clip = 0.0 if dist_clip is None else float(dist_clip)
     a.loss_in_log = 2 if loss_in_log == 'before' else (1 if loss_in_log else 0)
     a.sky_loss_value, a.alpha = float(sky_loss_value), float(alpha)
+    return a, keep, (B, V, H, W), dev
+
+
+def loss_pass(gt_pts, in_camera0, pr_pts, valid, per_pixel=False, **kw):
+    """One fused pass (``must3r_hip_metrics_loss``).  ``gt_pts`` [B,V,H,W,3] world points, ``in_camera0`` [B,4,4], ``pr_pts`` [B,V,H,W,3],
+    ``valid`` [B,V,H,W]; the optional inputs as ``loss_args`` names them.  Returns ``(counts int64 [B,V,2], sums fp64 [B,V,4])`` on the
+    device -- (global, local) and (l global, l local, conf-weighted global, conf-weighted local) -- plus ``(pix_g, pix_l, msk_g, msk_l)``
+    with ``per_pixel``."""
+    lib = _lib.load()
+    a, keep, (B, V, H, W), dev = loss_args(gt_pts, in_camera0, pr_pts, valid, **kw)
     counts = torch.empty((B, V, 2), dtype=torch.int64, device=dev)
     sums = torch.empty((B, V, 4), dtype=torch.float64, device=dev)
     a.counts, a.sums = _ptr(counts), _ptr(sums)
@@ -254,11 +262,21 @@ class L21Loss(BaseCriterion):
         if n == 0:
             empty = a.new_zeros(a.shape[:-1], dtype=torch.float32)
             return empty if self.reduction == 'none' else (empty.sum() if self.reduction == 'sum' else empty.mean())
+        out = loss_pass(*self.pass_inputs(a, b), per_pixel=self.reduction == 'none')
+        return self.pick(out, a.shape[:-1])
+
+    @staticmethod
+    def pass_inputs(a, b):
+        """``a``, ``b`` [..., 3] as one view of one scene under the identity: the positional inputs of ``loss_pass``."""
+        n = a.numel() // 3
         eye = torch.eye(4, dtype=torch.float32, device=a.device)[None]
         valid = torch.ones((1, 1, 1, n), dtype=torch.uint8, device=a.device)
-        out = loss_pass(b.reshape(1, 1, 1, n, 3), eye, a.reshape(1, 1, 1, n, 3), valid, per_pixel=self.reduction == 'none')
+        return b.reshape(1, 1, 1, n, 3), eye, a.reshape(1, 1, 1, n, 3), valid
+
+    def pick(self, out, shape):
+        n = torch.Size(shape).numel()
         if self.reduction == 'none':
-            return out[2][0].reshape(a.shape[:-1])
+            return out[2][0].reshape(shape)
         s = out[1][0, 0, 0]
         return (s if self.reduction == 'sum' else s / n).to(torch.float32)
 
@@ -370,6 +388,11 @@ class Regr3D(Criterion, MultiLoss):
 
     def fused(self, gt, pred, dist_clip=None, alpha=0.0, per_pixel=False):
         """The device passes behind ``compute_loss``: ``(counts [B,V,2], sums [B,V,4][, pixels])`` of ``loss_pass``."""
+        args, kw, _ = self.fused_inputs(gt, pred, dist_clip=dist_clip, alpha=alpha)
+        return loss_pass(*args, per_pixel=per_pixel, **kw)
+
+    def fused_inputs(self, gt, pred, dist_clip=None, alpha=0.0):
+        """``(args, kw, mask_host)``: the inputs of ``loss_pass`` for this criterion, and the scenes normalised by their own factor."""
         device, gt_w2c, gt_pts3d, valid, sky, mask_host = self._inputs(gt, pred)
         in_camera0 = gt_w2c[:, 0].contiguous()
         pr_pts = _f32(pred['pts3d'], "pred['pts3d']").reshape(gt_pts3d.shape)
@@ -378,10 +401,10 @@ class Regr3D(Criterion, MultiLoss):
         conf = pred.get('conf')
         conf = None if conf is None else _f32(conf, "pred['conf']").reshape(gt_pts3d.shape[:-1])
         gt_scale, pr_scale, pr_warp, gt_warp = self._scales(gt_pts3d, in_camera0, pr_pts, valid, mask_host)
-        return loss_pass(gt_pts3d, in_camera0, pr_pts, valid, w2c=gt_w2c, pr_local=pr_local, conf=conf,
-                         sky=sky if self.sky_loss_value > 0 else None, gt_scale=gt_scale, pr_scale=pr_scale, pr_warp=pr_warp,
-                         gt_warp=gt_warp, dist_clip=dist_clip, loss_in_log=self.loss_in_log, sky_loss_value=self.sky_loss_value,
-                         alpha=alpha, per_pixel=per_pixel)
+        kw = dict(w2c=gt_w2c, pr_local=pr_local, conf=conf, sky=sky if self.sky_loss_value > 0 else None, gt_scale=gt_scale,
+                  pr_scale=pr_scale, pr_warp=pr_warp, gt_warp=gt_warp, dist_clip=dist_clip, loss_in_log=self.loss_in_log,
+                  sky_loss_value=self.sky_loss_value, alpha=alpha)
+        return (gt_pts3d, in_camera0, pr_pts, valid), kw, (mask_host if self.norm_mode else None)
 
     def get_all_pts3d(self, gt, pred, dist_clip=None):
         """losses.py:22-84, materialised: everything normalised w.r.t. the camera of view 1."""
@@ -417,24 +440,33 @@ class Regr3D(Criterion, MultiLoss):
         has_local = 'pts3d_local' in pred
         none = self.criterion.reduction == 'none'
         out = self.fused(gt, pred, per_pixel=none, **kw)
-        counts, sums = out[0].sum(dim=(0, 1)), out[1].sum(dim=(0, 1))
-        means = _ratio(sums[:2], counts).to(torch.float32)
-        host = means.tolist()                    # the one device->host read
+        figures = self.figures(out[0], out[1])
+        return self.assemble(figures, out[2] if none else None, has_local), self.details(figures, has_local)
+
+    @staticmethod
+    def figures(counts, sums):
+        """fp32 [4]: the means of the global and of the local term, then their sums."""
+        counts, sums = counts.sum(dim=(0, 1)), sums.sum(dim=(0, 1))
+        return torch.cat((_ratio(sums[:2], counts).to(torch.float32), sums[:2].to(torch.float32)))
+
+    def details(self, figures, has_local):
+        host = figures.tolist()                  # the one device->host read
         self_name = type(self).__name__
         details = {self_name + '_pts3d': host[0]}
         if has_local:
             details[self_name + '_pts3d_local'] = host[1]
-        if none:
-            pix_g, pix_l, msk_g, msk_l = out[2]
+        return details
+
+    def assemble(self, figures, pix, has_local):
+        if pix is not None:
+            pix_g, pix_l, msk_g, msk_l = pix
             msk_g, msk_l = msk_g.bool(), msk_l.bool()
             l1, l2 = pix_g[msk_g], (pix_l[msk_l] if has_local else None)
         else:
             msk_g = msk_l = None
-            if self.criterion.reduction == 'sum':
-                l1, l2 = sums[0].to(torch.float32), (sums[1].to(torch.float32) if has_local else None)
-            else:
-                l1, l2 = means[0], (means[1] if has_local else None)
-        return Sum((l1, msk_g), (l2, msk_l)), details
+            k = 2 if self.criterion.reduction == 'sum' else 0
+            l1, l2 = figures[k], (figures[k + 1] if has_local else None)
+        return Sum((l1, msk_g), (l2, msk_l))
 
 
 class ConfLoss(MultiLoss):
@@ -453,11 +485,18 @@ class ConfLoss(MultiLoss):
     def compute_loss(self, gt, pred, **kw):
         has_local, has_conf = 'pts3d_local' in pred, 'conf' in pred
         counts, sums = self.pixel_loss.fused(gt, pred, alpha=self.alpha, **kw)
+        return self.result(self.figures(counts, sums, has_conf), has_local)
+
+    @staticmethod
+    def figures(counts, sums, has_conf):
+        """fp32 [4]: the plain means of the global and of the local term, then the confidence-weighted ones (the loss's two terms)."""
         counts, sums = counts.sum(dim=(0, 1)), sums.sum(dim=(0, 1))
         plain = _ratio(sums[:2], counts)
         weighted = _ratio(sums[2:], counts) if has_conf else plain
         weighted = torch.where(counts > 0, weighted, torch.zeros_like(weighted))      # nan protection (no selected pixel at all)
-        host = torch.cat((plain, weighted)).to(torch.float32)
+        return torch.cat((plain, weighted)).to(torch.float32)
+
+    def result(self, host, has_local):
         values = host.tolist()                   # the one device->host read
         name = type(self.pixel_loss).__name__
         details = dict(conf_loss_g=values[2])
