@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 16
+#define MUST3R_HIP_ABI_VERSION 17
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -68,7 +68,8 @@ typedef struct must3r_hip_config {
 int must3r_hip_abi_version(void);
 const char* must3r_hip_last_error(void);
 /* ABI 8.  Process-wide A/B switches of the library (measuring instruments, not model semantics: DESIGN.md section 10 lists them -- "PERSIST", "GEMM256",
- * "G256K", "G256P", "G256P_SPLIT", "SPARSE_256", "SPARSE_LO", "BK128", "LN_ROWS", "LNFOLD", "ENC_CHUNK_ROWS", "ATTN_LZ").  Each has a default and an allowed
+ * "G256K", "G256P", "G256P_SPLIT", "SPARSE_256", "SPARSE_LO", "BK128", "LN_ROWS", "LNFOLD", "ENC_CHUNK_ROWS", "ATTN_LZ", "LNFOLD256", "G256_GM",
+ * "NN_LEAF_LOG2", "NN_QUERY_LANES_LOG2").  Each has a default and an allowed
  * range; an unknown name or a value outside the range is refused (status 1, must3r_hip_last_error() says why).  Without a call a switch takes its value from the
  * environment variable M3R_<NAME> (validated alike; a bad value is reported on stderr and ignored).  No counterpart in the reference: its only back-end
  * switch is toggle_memory_efficient_attention (must3r/model/blocks/attention.py:18-27). */
@@ -516,6 +517,45 @@ int must3r_hip_op_gemm_fold256(int epi, int wsplit, const void* A, const void* W
                                int M, int N, int K, int lda, int ldc, void* x16_out, float* copy32_out, float* stats_out, const float* ln_stats,
                                const float* ln_s, float ln_eps, float* ln_shift, const int64_t* pos, const float* rope_tab, int rope_cols, int rope_npos,
                                float out_scale, int scale_cols, void* stream);
+/* ABI 17.  Every argument form in which the model launches its GEMMs, reachable one by one (tests): the grouped and per-scene fields of the launch descriptor that
+ * must3r_hip_op_gemm / _op_gemm_sp do not carry.  Forwards to the launcher must3r_hip_decode uses; the kernel is the one the default dispatch picks for the shape and
+ * is reported through `picked` (optional): "<family>/e<epilogue>/w<1 plain | 2 split | 3 sparse low part>/n<tile width>".  Nothing here changes what
+ * must3r_hip_op_gemm does; the LN-fold fields keep their own entry points.
+ *   weights: wsplit = 2: W is [N, 2K] = [W_hi | W_lo] (fp16); Wlo_sp / Widx_sp (optional, both or neither, wsplit = 2 only): the packed 2:4-sparse low part of a
+ *     parameter of wsp_rows rows (must3r_hip_op_sparse24_pack)
+ *   out_scale != 0: columns < scale_cols (a multiple of 64) of a 16-bit store are multiplied by it before rounding (after RoPE)
+ *   batch > 1: problem g reads A + g strideA, W + w strideW, bias + w strideB with w = g / wdiv (wdiv > 1) or g, and writes to out_table[g] (DEVICE array of `batch`
+ *     pointers; `out` is not used); strides in elements.  The sparse low part of weight group w starts at row w * (strideW / 2K) of the packed parameter.
+ *   EPI_F32: bias2 is added on rows m >= row_start2, with row_period2 > 0 on rows (m % row_period2) >= row_start2; accumulate: out += product, no bias
+ *   EPI_HEAD: rows are views of ntok tokens on a grid gw wide, written pixel-shuffled into [view][H][Wimg][7]; head_views > 0: the views belong to scenes of
+ *     head_views views whose blocks lie head_scene_skip floats further apart than contiguous
+ * Refused with an error: out_scale on another epilogue than STORE16 / QKV_ROPE or with scale_cols no multiple of 64; batch > 1 without out_table; wdiv > 1 that does not divide batch (or without batch > 1); row_period2 > 0 without bias2, negative row_start2 /
+ * row_period2; head_views / head_scene_skip on another epilogue than EPI_HEAD, negative, or head_scene_skip % 4 != 0; one of Wlo_sp / Widx_sp alone, or without wsplit = 2;
+ * wsp_rows smaller than the rows the weight groups index or not a multiple of 32; negative batch, wdiv or strides; and whatever must3r_hip_op_gemm refuses. */
+typedef struct must3r_hip_gemm_op {
+    int32_t dtype;                     /* MUST3R_BF16 / MUST3R_F16 */
+    int32_t epi;                       /* MUST3R_EPI_* */
+    const void* A; const void* W; const float* bias; void* out;
+    int32_t M, N, K, lda, ldc;
+    int32_t wsplit;                    /* 2: split weights, else 0 */
+    const void* Wlo_sp; const void* Widx_sp;
+    int32_t wsp_rows;
+    float out_scale;
+    int32_t scale_cols;
+    int32_t batch;                     /* 0 / 1: one problem */
+    int64_t strideA, strideW, strideB;
+    void* const* out_table;
+    int32_t wdiv;
+    const int64_t* pos; const float* rope_tab;
+    int32_t rope_cols, rope_npos;
+    const float* bias2;
+    int32_t row_start2, row_period2, accumulate;
+    int32_t ntok, gw, H, Wimg;
+    int32_t head_views;
+    int64_t head_scene_skip;
+    const char** picked;
+} must3r_hip_gemm_op;
+int must3r_hip_op_gemm_ex(const must3r_hip_gemm_op* d, void* stream);
 /* cos/sin table fp32 [npos][16][2] for RoPE2D(freq, F0) with head dim 64 (host pointer) */
 int must3r_hip_rope_table(float freq, float f0, int npos, float* out_host);
 

@@ -1502,6 +1502,45 @@ extern "C" int must3r_hip_op_gemm_lnfold(int dtype, int epi, const void* A, cons
     return 0;
 }
 
+// ABI 17 (tests): the grouped and per-scene fields of GemmArgs, one launch through launch_gemm under the default dispatch; what the kernels would misread is refused
+extern "C" int must3r_hip_op_gemm_ex(const must3r_hip_gemm_op* d, void* stream) {
+    if (!d) return fail("op_gemm_ex: null descriptor");
+    if (d->dtype != MUST3R_BF16 && d->dtype != MUST3R_F16) return fail("op_gemm_ex: bad dtype");
+    if (d->epi < 0 || d->epi >= EPI_COUNT) return fail("op_gemm_ex: bad epilogue");
+    if (!d->A || !d->W) return fail("op_gemm_ex: A and W are needed");
+    if (d->M < 0 || d->N <= 0 || d->K <= 0) return fail("op_gemm_ex: M >= 0, N > 0 and K > 0 are needed");
+    if (d->batch < 0 || d->wdiv < 0 || d->strideA < 0 || d->strideW < 0 || d->strideB < 0) return fail("op_gemm_ex: batch, wdiv and the strides must not be negative");
+    if (d->batch > 1 && !d->out_table) return fail("op_gemm_ex: batch = %d needs out_table", d->batch);
+    if (d->batch <= 1 && !d->out) return fail("op_gemm_ex: out is needed");
+    if (d->wdiv > 1 && (d->batch <= 1 || d->batch % d->wdiv != 0)) return fail("op_gemm_ex: wdiv = %d must divide batch = %d", d->wdiv, d->batch);
+    if (d->out_scale != 0.f && d->epi != EPI_STORE16 && d->epi != EPI_QKV_ROPE) return fail("op_gemm_ex: out_scale belongs to the STORE16 / QKV_ROPE epilogues");
+    if (d->out_scale != 0.f && (d->scale_cols < 0 || d->scale_cols % 64 != 0)) return fail("op_gemm_ex: scale_cols = %d must be a multiple of 64", d->scale_cols);
+    if (d->row_start2 < 0 || d->row_period2 < 0) return fail("op_gemm_ex: row_start2 and row_period2 must not be negative");
+    if (d->row_period2 > 0 && !d->bias2) return fail("op_gemm_ex: row_period2 = %d needs bias2", d->row_period2);
+    if ((d->head_views != 0 || d->head_scene_skip != 0) && d->epi != EPI_HEAD) return fail("op_gemm_ex: head_views / head_scene_skip belong to EPI_HEAD");
+    if (d->head_views < 0 || d->head_scene_skip < 0) return fail("op_gemm_ex: head_views and head_scene_skip must not be negative");
+    if (d->head_scene_skip % 4 != 0) return fail("op_gemm_ex: head_scene_skip = %lld must be a multiple of 4 floats", (long long)d->head_scene_skip);
+    if ((d->Wlo_sp != nullptr) != (d->Widx_sp != nullptr)) return fail("op_gemm_ex: Wlo_sp and Widx_sp come together");
+    if (d->Wlo_sp) {
+        if (d->wsplit != 2 || d->dtype != MUST3R_F16) return fail("op_gemm_ex: the sparse low part belongs to fp16 split weights (wsplit = 2)");
+        const long long ngroups = d->batch > 1 ? (d->wdiv > 1 ? d->batch / d->wdiv : d->batch) : 1;
+        const long long need = (ngroups - 1) * (d->strideW / (2 * (long long)d->K)) + d->N;
+        if (d->wsp_rows < need || d->wsp_rows % 32 != 0)
+            return fail("op_gemm_ex: wsp_rows = %d, but the %lld weight groups index %lld rows of the packed low part (a multiple of 32)", d->wsp_rows, ngroups, need);
+    }
+    GemmArgs a = gargs(d->A, d->W, d->bias, d->out, d->M, d->N, d->K, d->lda, d->ldc);
+    a.wsplit = d->wsplit == 2 ? 2 : 0; a.Wlo_sp = d->Wlo_sp; a.Widx_sp = d->Widx_sp; a.wsp_rows = d->wsp_rows;
+    a.out_scale = d->out_scale; a.scale_cols = d->scale_cols;
+    a.batch = d->batch; a.strideA = d->strideA; a.strideW = d->strideW; a.strideB = d->strideB; a.out_table = d->out_table; a.wdiv = d->wdiv;
+    a.pos = d->pos; a.rope_tab = d->rope_tab; a.rope_cols = d->rope_cols; a.rope_npos = d->rope_npos;
+    a.bias2 = d->bias2; a.row_start2 = d->row_start2; a.row_period2 = d->row_period2; a.accumulate = d->accumulate;
+    a.ntok = d->ntok; a.gw = d->gw; a.H = d->H; a.Wimg = d->Wimg; a.head_views = d->head_views; a.head_scene_skip = d->head_scene_skip;
+    const char* err = "";
+    if (launch_gemm((DType)d->dtype, (Epi)d->epi, a, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    if (d->picked && d->M > 0) *d->picked = gemm_last_kernel();
+    return 0;
+}
+
 extern "C" size_t must3r_hip_attention_scratch_bytes(int nsplit, int total_q_rows, int heads) {
     return attention_split_scratch_bytes(nsplit, total_q_rows, heads);
 }

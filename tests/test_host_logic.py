@@ -380,16 +380,19 @@ def test_set_option_is_validated(monkeypatch):
     error string; a refused call leaves the switch as it was.  (No GPU needed: nothing is launched.)"""
     from must3r_amd import _lib
     L = _lib.load()
-    assert L.must3r_hip_set_option(b"PERSIST", 1) == 0
-    for name, bad in ((b"PERSIST", 2), (b"PERSIST", -1), (b"GEMM256", 3), (b"ENC_CHUNK_ROWS", 0), (b"ENC_CHUNK_ROWS", 1 << 40), (b"NOPE", 1), (b"", 0)):
-        assert L.must3r_hip_set_option(name, bad) == 1, (name, bad)
-        msg = L.must3r_hip_last_error().decode()
-        assert "set_option" in msg and (name.decode() in msg or not name), msg
-    with pytest.raises(_lib.HipError):
-        _lib.set_option("SPARSE_LO", 7)
-    for name, ok in (("PERSIST", 0), ("PERSIST", 1), ("GEMM256", 2), ("GEMM256", 1), ("ENC_CHUNK_ROWS", 32768), ("ATTN_LZ", 1), ("LNFOLD", 1), ("SPARSE_LO", 1)):
-        _lib.set_option(name, ok)
-
+    try:
+        assert L.must3r_hip_set_option(b"PERSIST", 1) == 0
+        for name, bad in ((b"PERSIST", 2), (b"PERSIST", -1), (b"GEMM256", 3), (b"ENC_CHUNK_ROWS", 0), (b"ENC_CHUNK_ROWS", 1 << 40), (b"NOPE", 1), (b"", 0)):
+            assert L.must3r_hip_set_option(name, bad) == 1, (name, bad)
+            msg = L.must3r_hip_last_error().decode()
+            assert "set_option" in msg and (name.decode() in msg or not name), msg
+        with pytest.raises(_lib.HipError):
+            _lib.set_option("SPARSE_LO", 7)
+        for name, ok in (("PERSIST", 0), ("PERSIST", 1), ("GEMM256", 2), ("GEMM256", 1), ("ENC_CHUNK_ROWS", 32768), ("ATTN_LZ", 1), ("LNFOLD", 1), ("SPARSE_LO", 1)):
+            _lib.set_option(name, ok)
+    finally:   # the switches are process-wide: every one touched here goes back to its table default (csrc/misc.hip kOpts), so that later tests run the default kernels
+        for name, default in (("PERSIST", 0), ("GEMM256", 1), ("ENC_CHUNK_ROWS", 32768), ("ATTN_LZ", 1), ("LNFOLD", 1), ("SPARSE_LO", 1)):
+            _lib.set_option(name, default)
 
 
 def test_causal_module_constructor_and_memory_tail():

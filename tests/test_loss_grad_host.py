@@ -110,7 +110,7 @@ def _refused(lib, a, g, scratch, nbytes, words):
 
 def test_loss_grad_entry_point_refuses_bad_arguments():
     lib = _lib.load()
-    assert lib.must3r_hip_abi_version() == _lib.ABI_VERSION == 16
+    assert lib.must3r_hip_abi_version() == _lib.ABI_VERSION >= 16
     need = lib.must3r_hip_metrics_loss_grad_scratch_bytes(2, 3, 7, 13)
     assert need > 0 and need % 256 == 0
     assert lib.must3r_hip_metrics_loss_grad_scratch_bytes(0, 3, 7, 13) == 0 and "n_scenes" in lib.must3r_hip_last_error().decode()

@@ -218,6 +218,59 @@ def test_decode_refuses_a_call_that_would_overrun_the_memory_buffers():
     assert all(float(b.abs().sum()) == 0.0 for b in bufs)    # nothing was written
 
 
+def test_pointmaps_scene_stride_moves_the_scenes_apart_and_nothing_else():
+    """must3r_hip_group::pointmaps_scene_stride (the head epilogue's head_views / head_scene_skip): a batched render call whose scenes' pointmaps lie a scene + a
+    multiple of 4 floats apart writes the bits of the contiguous call and leaves what lies between, in front and behind alone; a stride that is no multiple of 4
+    floats, or smaller than a scene, is refused by the library with the field's name, before anything is written."""
+    from must3r_amd import _lib
+    cfg = TINY
+    enc, dec = build(cfg, "fp16w2")
+    B, n, H, W = 3, 3, 48, 64
+    imgs, ts = S.make_images(B * n, H, W, 21)
+    x, pos = enc(imgs.cuda(), ts.cuda())
+    x, pos, t = x.view(B, n, *x.shape[1:]), pos.view(B, n, *pos.shape[1:]), ts.cuda().view(B, n, 2)
+    mem, _ = dec(*_c(x[:, :2], pos[:, :2], t[:, :2]), None)
+    _, want = dec(x, pos, t, mem, render=True)
+    inner, lead = n * H * W * 7, 64
+    for extra in (4, 7 * 64, 1000):
+        stride = inner + extra
+        buf = torch.full((lead + B * stride,), float("nan"), device="cuda")
+        pm = torch.as_strided(buf, (B, n, H, W, 7), (stride, H * W * 7, W * 7, 7, 1), lead)
+        _, got = dec(x, pos, t, mem, render=True, pointmaps_out=pm)
+        torch.cuda.synchronize()
+        assert got.data_ptr() == pm.data_ptr() and got.stride(0) == stride
+        assert torch.equal(got, want), extra
+        assert bool(torch.isnan(buf[:lead]).all())
+        for b in range(B):
+            assert bool(torch.isnan(buf[lead + b * stride + inner:lead + (b + 1) * stride]).all()), (extra, b)
+    # the library's own refusals (the Python wrapper checks its tensor first, so through the C ABI): an update call of 2 scenes x 2 views
+    ctx = dec._context()
+    N, D = x.shape[2], cfg.dec_dim
+    xs, ps = x[:2, :2].contiguous(), pos[:2, :2].contiguous()
+    inner2 = 2 * H * W * 7
+    bufs = [torch.zeros((2, 2 * N, 2 * D), dtype=torch.float16, device="cuda") for _ in range(cfg.dec_depth)]
+    ptrs = (C.c_void_p * cfg.dec_depth)(*[b.data_ptr() for b in bufs])
+    stream = torch.cuda.current_stream().cuda_stream
+    for stride in (inner2 + 2, inner2 + 7, inner2 - 4, 4):
+        pm = torch.full((2 * max(stride, inner2) + 8,), float("nan"), device="cuda")
+        groups = (_lib.Group * 1)(_lib.Group(xs.data_ptr(), ps.data_ptr(), 2, N, H, W, pm.data_ptr(), stride))
+        args = _lib.DecodeArgs(_lib.F16_W2, _lib.MEM_KV, 0, 1, 1, groups, 0, ptrs, None, 2 * N, 2, 2 * N)
+        assert ctx.lib.must3r_hip_decode(ctx.handle, C.byref(args), stream) != 0, stride
+        assert "pointmaps_scene_stride" in ctx.lib.must3r_hip_last_error().decode(), stride
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(pm).all()) and all(float(b.abs().sum()) == 0.0 for b in bufs)
+    # and the same call with a stride the head can serve goes through, scene 1 behind the gap
+    stride = inner2 + 8
+    pm = torch.full((2 * stride,), float("nan"), device="cuda")
+    groups = (_lib.Group * 1)(_lib.Group(xs.data_ptr(), ps.data_ptr(), 2, N, H, W, pm.data_ptr(), stride))
+    args = _lib.DecodeArgs(_lib.F16_W2, _lib.MEM_KV, 0, 1, 1, groups, 0, ptrs, None, 2 * N, 2, 2 * N)
+    _lib.check(ctx.lib.must3r_hip_decode(ctx.handle, C.byref(args), stream))
+    torch.cuda.synchronize()
+    _, upd = dec(xs, ps, t[:2, :2].contiguous(), None)
+    assert torch.equal(pm.view(2, stride)[:, :inner2].reshape(2, 2, H, W, 7), upd)
+    assert bool(torch.isnan(pm.view(2, stride)[:, inner2:]).all())
+
+
 def test_full_size_scenes_in_flight_properties():
     """BASELINE geometry (384x512, ViT-L / ViT-B): 2 scenes x 4 views in flight against the same scenes run alone -- the batched
     calls take other tile shapes and, for the one-view updates, another algorithm (no LN fold), so the comparison is the mode's
