@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 17
+#define MUST3R_HIP_ABI_VERSION 18
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -508,6 +508,33 @@ int must3r_hip_op_gemm_lnfold(int dtype, int epi, const void* A, const void* W2,
                               int lda, int ldc, void* x16_out, float* copy32_out, float* stats_out, const float* ln_stats,
                               const float* ln_s, float ln_eps, float* ln_shift, int ln_shift_init, const int64_t* pos,
                               const float* rope_tab, int rope_cols, int rope_npos, float out_scale, int scale_cols, void* stream);
+/* ABI 18.  Every launch form of the LN fold of a one-view update, reachable one by one (tests): the arguments of must3r_hip_op_gemm_lnfold plus what it does not
+ * carry -- plain fp16 weights (wsplit = 0: the fc1 consumer, the fc2 and embed producers of MUST3R_F16_WA mode) and bias2 / row_start2 (the embed producer).  Forwards
+ * to the launcher must3r_hip_decode uses and adds no arithmetic; `picked` (optional) reports the kernel as must3r_hip_gemm_op does.  must3r_hip_op_gemm_lnfold is unchanged.
+ * Refused with an error: another dtype than MUST3R_F16; a wsplit other than 0 / 2; null A, W or out; M < 0; ln_stats (consumer) together with x16_out / copy32_out /
+ * stats_out (producer); a consumer without ln_s, bias or ln_shift, on another epilogue than STORE16 / STORE16_GELU / QKV_ROPE, or with K != 768; producer outputs on
+ * another epilogue than RESID_F32 / F32; stats_out without x16_out or with N != 768; producer outputs with ldc != N (x16_out, copy32_out and the fragment sums are
+ * addressed with out's stride); bias2 on another epilogue than F32, negative row_start2; out_scale on another epilogue than STORE16 / QKV_ROPE or with scale_cols no
+ * multiple of 64; and whatever must3r_hip_op_gemm refuses. */
+typedef struct must3r_hip_lnfold_op {
+    int32_t dtype;                     /* MUST3R_F16 */
+    int32_t epi;                       /* MUST3R_EPI_* */
+    const void* A; const void* W; const float* bias; void* out;
+    int32_t M, N, K, lda, ldc;
+    int32_t wsplit;                    /* 2: W is [N, 2K] = [W_hi | W_lo]; 0: plain [N, K] */
+    void* x16_out; float* copy32_out; float* stats_out;          /* producer */
+    const float* ln_stats; const float* ln_s; float ln_eps;      /* consumer */
+    float* ln_shift;
+    int32_t ln_shift_init;
+    const int64_t* pos; const float* rope_tab;
+    int32_t rope_cols, rope_npos;
+    float out_scale;
+    int32_t scale_cols;
+    const float* bias2;
+    int32_t row_start2;
+    const char** picked;
+} must3r_hip_lnfold_op;
+int must3r_hip_op_gemm_lnfold_ex(const must3r_hip_lnfold_op* d, void* stream);
 /* ABI 8 (r06).  The same fold on the chip-filling 256 x 256 tiles (batched decoder calls, encoder chunks; fp16; the library uses it by itself in MUST3R_F16_WA mode,
  * M3R_LNFOLD256=0: never).  wsplit = 2: W = [N, 2K] split rows + the packed sparse low part (must3r_hip_op_sparse24_pack), epi STORE16 / QKV_ROPE (consumer) or
  * RESID_F32 (producer); wsplit = 0: plain fp16 W [N, K], epi STORE16_GELU (consumer) or RESID_F32 (producer).  N % 256 == 0.
@@ -611,6 +638,7 @@ int must3r_hip_op_layernorm(int dtype, const float* x, const float* add, const f
  *   input: exactly one of x (fp32) / x16 (16-bit) [M][C]; add (optional, fp32) is added before the statistics
  *   outputs, all optional: out16 / out16_lo (= T(y - float(T(y)))) / out16_dup (= out16) with row stride ld16 (0 = C); out32; copy32 = x + add (fp32);
  *     raw16 = T(x + add), fp16 saturated at +-65504.  The three out16* need out16.
+ *     mean_out [M] (ABI 18): the row means of x + add the statistics used (the LN fold's first shift); such a launch always runs the one-row-per-wave kernel.
  *   rows_per_group > 0: row r is of group g = r / rows_per_group and uses w + g C, b + g C; add is [rows_per_group][C] and applied to groups < add_groups.
  * Refused with an error: both or neither of x / x16, null w / b, ld16 non-zero and < C or not a multiple of 4, negative add_groups / rows_per_group,
  * C > 1024 or not a multiple of 4. */
@@ -624,6 +652,7 @@ typedef struct must3r_hip_ln_op {
     float eps;
     int32_t rows_per_group, add_groups;
     const char** picked;
+    float* mean_out;                   /* ABI 18 */
 } must3r_hip_ln_op;
 int must3r_hip_op_layernorm_ex(const must3r_hip_ln_op* d, void* stream);
 int must3r_hip_op_im2col(int dtype, const float* img, void* out16, int n_views, int H, int W, void* stream);

@@ -15,7 +15,7 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 17
+ABI_VERSION = 18
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
@@ -79,7 +79,7 @@ class LnOp(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("x", C.c_void_p), ("x16", C.c_void_p), ("add", C.c_void_p), ("w", C.c_void_p), ("b", C.c_void_p),
                 ("out16", C.c_void_p), ("out16_lo", C.c_void_p), ("out16_dup", C.c_void_p), ("ld16", C.c_int32),
                 ("out32", C.c_void_p), ("copy32", C.c_void_p), ("raw16", C.c_void_p), ("M", C.c_int32), ("C", C.c_int32), ("eps", C.c_float),
-                ("rows_per_group", C.c_int32), ("add_groups", C.c_int32), ("picked", C.POINTER(C.c_char_p))]
+                ("rows_per_group", C.c_int32), ("add_groups", C.c_int32), ("picked", C.POINTER(C.c_char_p)), ("mean_out", C.c_void_p)]
 
 
 class GemmOp(C.Structure):
@@ -91,6 +91,17 @@ class GemmOp(C.Structure):
                 ("pos", C.c_void_p), ("rope_tab", C.c_void_p), ("rope_cols", C.c_int32), ("rope_npos", C.c_int32),
                 ("bias2", C.c_void_p), ("row_start2", C.c_int32), ("row_period2", C.c_int32), ("accumulate", C.c_int32),
                 ("ntok", C.c_int32), ("gw", C.c_int32), ("H", C.c_int32), ("Wimg", C.c_int32), ("head_views", C.c_int32), ("head_scene_skip", C.c_int64),
+                ("picked", C.POINTER(C.c_char_p))]
+
+
+class LnFoldOp(C.Structure):
+    """must3r_hip_lnfold_op: one LN-fold GEMM launch of a one-view update, plain or split weights (include/must3r_hip.h, ABI 18)."""
+    _fields_ = [("dtype", C.c_int32), ("epi", C.c_int32), ("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("lda", C.c_int32), ("ldc", C.c_int32), ("wsplit", C.c_int32),
+                ("x16_out", C.c_void_p), ("copy32_out", C.c_void_p), ("stats_out", C.c_void_p),
+                ("ln_stats", C.c_void_p), ("ln_s", C.c_void_p), ("ln_eps", C.c_float), ("ln_shift", C.c_void_p), ("ln_shift_init", C.c_int32),
+                ("pos", C.c_void_p), ("rope_tab", C.c_void_p), ("rope_cols", C.c_int32), ("rope_npos", C.c_int32),
+                ("out_scale", C.c_float), ("scale_cols", C.c_int32), ("bias2", C.c_void_p), ("row_start2", C.c_int32),
                 ("picked", C.POINTER(C.c_char_p))]
 
 
@@ -177,6 +188,7 @@ PROTOTYPES = {
     "must3r_hip_op_sparse24_pack": (i32, [vp, i32, i32, vp, vp, vp]),
     "must3r_hip_op_gemm_sp": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
     "must3r_hip_op_gemm_lnfold": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, fp, vp, i32, vp, vp, i32, i32, fp, i32, vp]),
+    "must3r_hip_op_gemm_lnfold_ex": (i32, [P(LnFoldOp), vp]),
     "must3r_hip_op_gemm_fold256": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, fp, vp, vp, vp, i32, i32, fp, i32, vp]),
     "must3r_hip_op_gemm_ex": (i32, [P(GemmOp), vp]),
     "must3r_hip_rope_table": (i32, [fp, fp, i32, vp]),

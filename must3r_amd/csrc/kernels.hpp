@@ -192,6 +192,7 @@ struct LnArgs {
     int ld16;            // row stride (elements) of out16 / out16_lo / out16_dup; 0 = C
     float* out32;        // optional fp32 [M,C]
     float* copy32;       // optional raw copy of x (+add) (memorised layer input, decoder.py:304-305)
+    float* mean_out;     // optional [M]: the row means the statistics used (LN fold: the shift of the rows' next producer, GemmArgs::ln_shift); always the one-row-per-wave kernel
     int M, C;
     float eps;
     // grouped rows: row r belongs to group g = r / rows_per_group: affine parameters w + g*C, b + g*C; `add` (shape

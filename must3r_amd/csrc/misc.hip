@@ -17,7 +17,7 @@ namespace {
 struct OptRow { const char* name; long long def, lo, hi; };
 const OptRow kOpts[OPT_COUNT] = {
     {"PERSIST", 0, 0, 1}, {"GEMM256", 1, 0, 2}, {"G256K", 1, 0, 2}, {"G256P", 1, 0, 1}, {"G256P_SPLIT", 1, 0, 2}, {"SPARSE_256", 1, 0, 1},
-    {"SPARSE_LO", 1, 0, 1}, {"BK128", 1, 0, 1}, {"LN_ROWS", 1, 0, 1}, {"LNFOLD", 1, 0, 1}, {"ENC_CHUNK_ROWS", 32768, 256, 1 << 22}, {"ATTN_LZ", 1, 0, 2},
+    {"SPARSE_LO", 1, 0, 1}, {"BK128", 1, 0, 1}, {"LN_ROWS", 1, 0, 1}, {"LNFOLD", 1, 0, 2}, {"ENC_CHUNK_ROWS", 32768, 256, 1 << 22}, {"ATTN_LZ", 1, 0, 2},
     {"LNFOLD256", 0, 0, 1}, {"G256_GM", 4, 1, 64}, {"NN_LEAF_LOG2", 5, 4, 6}, {"NN_QUERY_LANES_LOG2", 3, 0, 4},
 };
 long long g_opt_val[OPT_COUNT];
@@ -65,7 +65,8 @@ int opt_set(const char* name, long long value, const char** err) {
 // ------------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, C <= 1024, C % 4 == 0.  Two-pass statistics in registers.
 // ------------------------------------------------------------------------------------------------
-template <class T>
+// MEAN: the row means go to p.mean_out as well (LnArgs::mean_out; a form of its own, so that the other launches keep their code)
+template <class T, bool MEAN = false>
 __global__ void __launch_bounds__(256) ln_kernel(const LnArgs p) {
     typedef typename Vec<T>::v4 v4;
     const int lane = threadIdx.x & 63;
@@ -96,6 +97,9 @@ __global__ void __launch_bounds__(256) ln_kernel(const LnArgs p) {
         }
     }
     const float mean = wave_sum_dpp(s) / (float)p.C;
+    if constexpr (MEAN) {
+        if (lane == 0) p.mean_out[row] = mean;
+    }
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -232,6 +236,11 @@ static void launch_ln_t(const LnArgs& a, hipStream_t s) {
     // 32.4 -> 39.2 us (5.8 -> 4.8 TB/s: 194 VGPRs = 2 walkers per SIMD cannot keep as many lines in flight as 8 one-row waves can).
     // Hence: only launches whose rows cannot be MALL-resident (> 64 k rows = 300+ MB).
     const int grid_one = (a.M + 3) / 4;
+    if (a.mean_out != nullptr) {   // (a one-view update's block 0: a few hundred rows; the walker does not carry the output)
+        g_ln_pick = "ln";
+        hipLaunchKernelGGL((ln_kernel<T, true>), dim3(grid_one), dim3(256), 0, s, a);
+        return;
+    }
     if (ln_rows_mode() == 0 || a.M < 65536) {
         g_ln_pick = "ln";
         hipLaunchKernelGGL(ln_kernel<T>, dim3(grid_one), dim3(256), 0, s, a);
@@ -536,7 +545,7 @@ extern "C" int must3r_hip_op_layernorm_ex(const must3r_hip_ln_op* d, void* strea
     LnArgs a;
     memset(&a, 0, sizeof(a));
     a.x = d->x; a.x16 = d->x16; a.raw16 = d->raw16; a.add = d->add; a.w = d->w; a.b = d->b;
-    a.out16 = d->out16; a.out16_lo = d->out16_lo; a.out16_dup = d->out16_dup; a.ld16 = d->ld16; a.out32 = d->out32; a.copy32 = d->copy32;
+    a.out16 = d->out16; a.out16_lo = d->out16_lo; a.out16_dup = d->out16_dup; a.ld16 = d->ld16; a.out32 = d->out32; a.copy32 = d->copy32; a.mean_out = d->mean_out;
     a.M = d->M; a.C = d->C; a.eps = d->eps; a.rows_per_group = d->rows_per_group; a.add_groups = d->add_groups;
     const char* err = "";
     if (launch_layernorm((DType)d->dtype, a, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);

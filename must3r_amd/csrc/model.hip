@@ -900,8 +900,12 @@ static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void*
         need = ws_need(need, (size_t)R * D, 4);       // feedback offset
         need = ws_need(need, (size_t)L * R * D, 2);   // norm_y of all layers (grouped K|V projection)
     }
-    // LN fold (one-view update calls, fp16 + split weights): none of the 36 LayerNorm launches of the blocks is issued; the residual GEMMs
+    // LN fold (one-view update calls, fp16 + split weights): the LayerNorm launches of the blocks are not issued; the residual GEMMs
     // leave 16-bit rows + per-fragment sums, the Linears that follow normalise after their product (kernels.hpp GemmArgs "LN fold").
+    // Block 0's norm1 keeps its kernel (35 of the 36 launches go): a consumer multiplies the fp16 copy of x - shift, so its error grows with
+    // |mean - shift| / sigma of the row, and the embedded tokens come with no estimate of their mean -- a common offset of 40 sigma in the embed
+    // bias took the update pointmaps of a 48 x 64 scene from 4.9e-4 to 1.4e-3 (tests/test_lnfold_model_gpu.py; the bound per launch form:
+    // tests/lnfold_forms.py).  The LayerNorm launch pays nothing for an offset and leaves the row means as the shift of block 0's first producer.  M3R_LNFOLD=2 (A/B instrument): block 0's norm1 folded too.
     const bool lnf_on = opt(OPT_LNFOLD) != 0;
     // (S > 1: the consumers of the fold only exist on the small-M tile shapes; a batched call is past the launch floor the fold removes)
     const bool lnf = lnf_on && update && !need_pre_kv && c->wsplit == 2 && dt == DT_F16 && !a8 && !A->feats && A->n_groups == 1 &&
@@ -911,6 +915,7 @@ static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void*
     const bool f256 = !lnf && opt(OPT_LNFOLD256) != 0 && c->wsplit == 2 && c->mlp_plain && dt == DT_F16 && !a8 && !A->feats && !A->cp && (D == 768 || D == 1024) &&
                       gemm_fold256_shape_ok(R, 3 * D, D, true) && gemm_fold256_shape_ok(R, D, D, true) &&
                       gemm_fold256_shape_ok(R, F, D, false) && gemm_fold256_shape_ok(R, D, F, false);
+    const bool lnf_all = lnf && opt(OPT_LNFOLD) == 2;   // block 0's norm1 folded as well: its consumer reads unshifted rows
     const bool lnF = lnf || f256;
     need = ws_need(need, lnF ? (size_t)R * D : 0, 2);                 // x16: the residual stream rounded to fp16
     need = ws_need(need, lnF ? (size_t)R * (D / 16) * 2 : 0, 4);      // per row and 16-column fragment (f256: 64-column wave tile) (sum, sum of squares)
@@ -1034,7 +1039,7 @@ static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void*
         ga.bias2 = p32(c, "decoder.image2_embed");
         ga.row_start2 = A->first_call ? A->groups[0].n_tokens : 0;  // reference view (group 0, view 0) of every scene gets no embed
         ga.row_period2 = S > 1 ? Rs : 0;
-        if (lnf) { ga.x16_out = x16; ga.stats_out = lnstats; ga.copy32_out = newmem; }   // block 0's norm1 input (+ its memorised copy)
+        if (lnf_all) { ga.x16_out = x16; ga.stats_out = lnstats; ga.copy32_out = newmem; }   // block 0's norm1 input (+ its memorised copy)
         M3R_OK(gemm(c, dt, EPI_F32, ga, s));
     }
     // several aspect ratios: gather the positions of all rows into one [R,2] array.  t16 is dead after the
@@ -1116,10 +1121,12 @@ static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void*
         auto fold_out = [&](GemmArgs& g_, float* copy) {
             g_.x16_out = x16; g_.stats_out = lnstats; g_.copy32_out = copy; g_.ln_shift = lnshift; g_.fold256 = f256 ? 1 : 0;
         };
-        const bool fq = lnf || (f256 && l > 0);   // is this block's norm1 folded?
-        if (!fq)
-            M3R_OK(layernorm_a(c, dt, lnargs(x, nullptr, LP[LF_N1W]->d, LP[LF_N1B]->d, h16, nullptr, nullptr,
-                                            update ? newmem + (size_t)l * R * D : nullptr, R, D, 1e-6f), s));
+        const bool fq = lnf_all || ((lnf || f256) && l > 0);   // is this block's norm1 folded?
+        if (!fq) {
+            LnArgs la = lnargs(x, nullptr, LP[LF_N1W]->d, LP[LF_N1B]->d, h16, nullptr, nullptr, update ? newmem + (size_t)l * R * D : nullptr, R, D, 1e-6f);
+            if (lnf) { la.mean_out = lnshift; lnshift_fresh = false; }   // the row means: the shift of this block's proj producer
+            M3R_OK(layernorm_a(c, dt, la, s));
+        }
         M3R_OK(w16p(c, *LP[fq ? LF_QKVLN_W : LF_QKVW], dt, &w, s));
         GemmArgs ga = gargs(h16, w, LP[LF_QKVB]->d, qkv, R, 3 * D, D, D, 3 * D);
         if (fq) fold_in(ga, LF_QKVLN_S);
@@ -1499,6 +1506,44 @@ extern "C" int must3r_hip_op_gemm_lnfold(int dtype, int epi, const void* A, cons
     a.out_scale = out_scale; a.scale_cols = scale_cols;
     const char* err = "";
     if (launch_gemm(DT_F16, (Epi)epi, a, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    return 0;
+}
+
+// ABI 18 (tests): every launch form of the one-view LN fold -- plain or split weights, bias2 -- one launch through launch_gemm; what the kernels would misread is refused
+extern "C" int must3r_hip_op_gemm_lnfold_ex(const must3r_hip_lnfold_op* d, void* stream) {
+    if (!d) return fail("op_gemm_lnfold_ex: null descriptor");
+    if (d->dtype != MUST3R_F16) return fail("op_gemm_lnfold_ex: the fold is built for fp16 operands (dtype)");
+    if (d->epi < 0 || d->epi >= EPI_COUNT) return fail("op_gemm_lnfold_ex: bad epilogue");
+    if (d->wsplit != 0 && d->wsplit != 2) return fail("op_gemm_lnfold_ex: wsplit = %d (0: plain weights, 2: split weights)", d->wsplit);
+    if (!d->A || !d->W || !d->out) return fail("op_gemm_lnfold_ex: A, W and out are needed");
+    if (d->M < 0 || d->N <= 0 || d->K <= 0) return fail("op_gemm_lnfold_ex: M >= 0, N > 0 and K > 0 are needed");
+    const bool cons = d->ln_stats != nullptr, prod = d->x16_out || d->copy32_out || d->stats_out;
+    if (cons && prod) return fail("op_gemm_lnfold_ex: ln_stats (consumer) and x16_out / copy32_out / stats_out (producer) exclude each other");
+    if (cons) {
+        if (d->epi != EPI_STORE16 && d->epi != EPI_STORE16_GELU && d->epi != EPI_QKV_ROPE) return fail("op_gemm_lnfold_ex: a consumer has a 16-bit-store epilogue");
+        if (!d->ln_s || !d->bias || !d->ln_shift) return fail("op_gemm_lnfold_ex: a consumer needs ln_s, bias and ln_shift");
+        if (d->K != 768) return fail("op_gemm_lnfold_ex: a consumer reads 48 fragment sums per row (K = 768), not K = %d", d->K);
+    }
+    if (prod) {
+        if (d->epi != EPI_RESID_F32 && d->epi != EPI_F32) return fail("op_gemm_lnfold_ex: producer outputs belong to the RESID_F32 / F32 epilogues");
+        if (d->stats_out && !d->x16_out) return fail("op_gemm_lnfold_ex: stats_out comes with x16_out");
+        if (d->stats_out && d->N != 768) return fail("op_gemm_lnfold_ex: stats_out needs N = 768, not N = %d", d->N);
+        if (d->ldc != d->N) return fail("op_gemm_lnfold_ex: producer outputs are addressed with out's stride: ldc = %d must equal N = %d", d->ldc, d->N);
+    }
+    if (d->bias2 && d->epi != EPI_F32) return fail("op_gemm_lnfold_ex: bias2 belongs to EPI_F32");
+    if (d->row_start2 < 0) return fail("op_gemm_lnfold_ex: row_start2 must not be negative");
+    if (d->out_scale != 0.f && d->epi != EPI_STORE16 && d->epi != EPI_QKV_ROPE) return fail("op_gemm_lnfold_ex: out_scale belongs to the STORE16 / QKV_ROPE epilogues");
+    if (d->out_scale != 0.f && (d->scale_cols < 0 || d->scale_cols % 64 != 0)) return fail("op_gemm_lnfold_ex: scale_cols = %d must be a multiple of 64", d->scale_cols);
+    GemmArgs a = gargs(d->A, d->W, d->bias, d->out, d->M, d->N, d->K, d->lda, d->ldc);
+    a.wsplit = d->wsplit;
+    a.x16_out = d->x16_out; a.copy32_out = d->copy32_out; a.stats_out = d->stats_out;
+    a.ln_stats = d->ln_stats; a.ln_s = d->ln_s; a.ln_eps = d->ln_eps; a.ln_shift = d->ln_shift; a.ln_shift_init = d->ln_shift_init;
+    a.pos = d->pos; a.rope_tab = d->rope_tab; a.rope_cols = d->rope_cols; a.rope_npos = d->rope_npos;
+    a.out_scale = d->out_scale; a.scale_cols = d->scale_cols;
+    a.bias2 = d->bias2; a.row_start2 = d->row_start2;
+    const char* err = "";
+    if (launch_gemm(DT_F16, (Epi)d->epi, a, reinterpret_cast<hipStream_t>(stream), &err)) return fail("%s", err);
+    if (d->picked && d->M > 0) *d->picked = gemm_last_kernel();
     return 0;
 }
 

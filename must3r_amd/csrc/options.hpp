@@ -18,7 +18,7 @@ enum Opt {
     OPT_SPARSE_LO,         // pack and use the 2:4-sparse low part of the split weights (read when a split weight is first packed): 0 dense two-pass kernels everywhere
     OPT_BK128,             // 128-deep K-tiles in gemm48_kernel: 0 the 64-deep form
     OPT_LN_ROWS,           // row-walking LayerNorm for launches of more than 64 k rows: 0 one row per wave everywhere
-    OPT_LNFOLD,            // LN fold in one-view update calls: 0 LayerNorm kernels
+    OPT_LNFOLD,            // LN fold in one-view update calls: 0 LayerNorm kernels, 1 every norm but block 0's norm1 folded, 2 that one too (A/B: unshifted first consumer)
     OPT_ENC_CHUNK_ROWS,    // token rows per encoder chunk
     OPT_ATTN_LZ,           // attn3_kernel: softmax references move on the tile's row sums (1) or on the per-lane score maxima (0); 2: experiment builds only
     OPT_LNFOLD256,         // r06: LN fold in the chip-filling launches (batched decoder calls, encoder chunks; MUST3R_F16_WA): 0 (default) LayerNorm kernels.

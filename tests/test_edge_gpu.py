@@ -139,8 +139,9 @@ def test_token_constant_massive_activations_stay_inside_the_target(precision):
     every token (here: 3e3 from a bias of block 0's MLP output, encoder and decoder, ~1e3 x the other channels).  Unlike the adversarial
     case above (token-DEPENDENT outliers, 1.0-1.6e-2) the 16-bit operands keep the 1e-3 parity: the outlier channels are constant
     after the LayerNorm too, their 2^-11 rounding is a constant offset of every GEMM output (emulation: 3e-6, scripts/emul/gemm_precision.py
-    model with a constant bias).  Exercises the LN-fold path of the one-view update as well (its fp16 copy of the raw residual rows holds
-    the outliers at an ulp of 2)."""
+    model with a constant bias).  The LN fold of the one-view update does not run here (it needs dec_dim = 768, SMALL has 128):
+    tests/test_lnfold_model_gpu.py runs these weights on a 768-wide geometry with the fold on and off (its fp16 copy of the raw residual
+    rows holds the outliers at an ulp of 2)."""
     from oracle import must3r_ref as R
     cfg = SMALL
     sde = {k: v.clone() for k, v in S.make_encoder_state_dict(cfg, 0).items()}

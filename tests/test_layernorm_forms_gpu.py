@@ -192,3 +192,34 @@ def test_raw16_saturates_in_fp16_and_the_stored_rows_normalise(lib, M):
                 F.assert_values(F.value_report(sops, so), (dt, picked, "from_raw of the stored rows"))
             finally:
                 lib.set_option("LN_ROWS", 1)
+
+
+@pytest.mark.parametrize("form,M,Cc", [("add_copy", 1000, 768), ("add_copy", 5, 200), ("add_copy", F.WALK_MIN + 37, 768), ("grouped", 35, 768)])
+def test_mean_out_is_the_row_mean_and_changes_nothing_else(lib, form, M, Cc):
+    """mean_out (ABI 18; the first shift of the LN fold: block 0's norm1 of a one-view update leaves it): row r gets the mean of x + add the statistics used (always by the one-row
+    kernel, also where the launch without it walks rows); nothing in front of or behind the M entries is written; every other output keeps its bits.  Bound: a lane adds its <= 16 values in order, the wave adds
+    the 64 partial sums in 6 pairwise steps, one division: (15 + 6 + 1) 2^-24 mean |x + add| + 2^-24 |mean|."""
+    case = F._case(form, M, Cc, R=7, add_groups=4) if form == "grouped" else F._case(form, M, Cc)
+    ops = F.make_operands(case, "fp16", "cuda")
+    rows = torch.arange(M, device="cuda")
+    xin, add, _, _ = F.resolve(ops, rows)
+    s = xin.double() if add is None else (xin.float() + add.float()).double()      # the kernel adds in fp32 first
+    want = s.mean(1)
+    tol = 22 * 2.0 ** -24 * s.abs().mean(1) + 2.0 ** -24 * want.abs() + 1e-30
+    for ln_rows in (1, 0):
+        try:
+            lib.set_option("LN_ROWS", ln_rows)
+            base, picked = run(lib, ops)
+            outs = F.alloc_outputs(ops, "cuda")
+            mean = torch.full((2 + M + 3,), float("nan"), device="cuda")
+            assert picked == F.kernel_name(M, Cc, ln_rows) and launch(lib, ops, outs, mean_out=mean[2:].data_ptr()) == "ln"   # the one-row kernel carries it
+        finally:
+            lib.set_option("LN_ROWS", 1)
+        assert bool(torch.isnan(mean[:2]).all()) and bool(torch.isnan(mean[2 + M:]).all()), "mean_out written outside its M entries"
+        got = mean[2:2 + M].double()
+        assert bool(torch.isfinite(got).all()), "mean_out not written"
+        r = float(((got - want).abs() / tol).max())
+        print(form, M, Cc, picked, "mean_out against fp64, ratio of the bound:", r)
+        assert r <= 1.0, (picked, r)
+        F.check_canaries(ops, outs)
+        F.outputs_equal(base, outs)
