@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 18
+#define MUST3R_HIP_ABI_VERSION 19
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -657,6 +657,51 @@ typedef struct must3r_hip_ln_op {
 int must3r_hip_op_layernorm_ex(const must3r_hip_ln_op* d, void* stream);
 int must3r_hip_op_im2col(int dtype, const float* img, void* out16, int n_views, int H, int W, void* stream);
 int must3r_hip_op_cast(int dtype, const float* in, void* out16, void* out16_lo, size_t n, void* stream);
+
+/* ABI 19.  Training forward and backward of the prediction head (decoder.py:149-156, blocks/head.py:63-72, tools/image.py:9-14), stateless:
+ *   x fp32 [R][D], R = n_views N, N = (H/16)(Wimg/16);  gamma, beta [D];  W [O][D], b [O], O = 7 * 256 (the reference's row order c 256 + i 16 + j)
+ *   y = (x - mu) rstd gamma + beta;  z = y W^T + b;  pointmaps[v][16 gy + i][16 gx + j][c] = z[v N + gy gw + gx][c 256 + i 16 + j]     fp32 [n_views][H][Wimg][7]
+ * must3r_hip_head_forward runs the two launches must3r_hip_decode runs for its head (split-precision 16-bit operands, fp32-equivalent), on operands packed from
+ * the fp32 parameters on every call (weights change between training steps; nothing is cached).  dtype: MUST3R_BF16 / MUST3R_F16.
+ * must3r_hip_op_head_linear is its Linear stage alone, from the fp32 y (the post-LayerNorm tensor return_feats hands out).
+ *
+ * must3r_hip_head_grad: from G = dL/dpointmaps fp32 [n_views][H][Wimg][7], with dZ[r][c 256 + i 16 + j] = G[v][16 gy + i][16 gx + j][c] (never materialised):
+ *   db[o] = sum_r dZ[r][o]                  dW[o][k] = gamma[k] sum_r dZ[r][o] x^[r][k] + beta[k] db[o]            x^ = (x - mu) rstd
+ *   dY = dZ W                               dgamma[k] = sum_r dY[r][k] x^[r][k]       dbeta[k] = sum_r dY[r][k]
+ *   g^ = dY gamma                           dx = rstd (g^ - mean_k(g^) - x^ mean_k(g^ x^))
+ * fp32 operands on v_mfma_f32_16x16x4_f32 (exact products, k-ordered fmaf chain); (mu, rstd) are recomputed from x, the forward saves nothing.  The weight
+ * gradient splits its sum over the rows across must3r_hip_head_grad_splits(R) blocks -- a function of R alone -- and adds the partials in split order; no atomics
+ * anywhere: repeated calls agree bit for bit, and a row of dx does not depend on which other rows the call holds.
+ * Every output may be NULL and then costs nothing: without dW and db no weight-gradient launch, without dx no data-gradient launch and no LayerNorm backward.
+ * dY lives in the dx buffer, so dgamma / dbeta need dx (refused otherwise).  An output that is not asked for is not written.
+ * Refused with an error: null required pointers, H or Wimg not multiples of 16, D not a multiple of 64 or above 1024, pointers not 16-byte aligned, scratch smaller
+ * than must3r_hip_head_grad_scratch_bytes (row statistics, the permuted W, the split partials, the LayerNorm column partials; returns 0 on a bad shape). */
+typedef struct must3r_hip_head_grad_args {
+    const float* x; const float* gamma; const float* beta; const float* W; const float* G;
+    int32_t n_views, H, Wimg, D;
+    float eps;
+    int32_t reserved;
+    float* dx; float* dgamma; float* dbeta; float* dW; float* db;
+} must3r_hip_head_grad_args;
+int must3r_hip_head_grad_splits(int rows);
+size_t must3r_hip_head_forward_scratch_bytes(int n_views, int H, int Wimg, int D);
+int must3r_hip_head_forward(int dtype, const float* x, const float* gamma, const float* beta, const float* W, const float* b, int n_views, int H, int Wimg, int D,
+                            float eps, float* pointmaps, void* scratch, size_t scratch_bytes, void* stream);
+int must3r_hip_op_head_linear(int dtype, const float* y, const float* W, const float* b, int n_views, int H, int Wimg, int D, float* pointmaps, void* scratch,
+                              size_t scratch_bytes, void* stream);
+size_t must3r_hip_head_grad_scratch_bytes(int n_views, int H, int Wimg, int D);
+int must3r_hip_head_grad(const must3r_hip_head_grad_args* a, void* scratch, size_t scratch_bytes, void* stream);
+/* the backward kernels one by one, in the plain forms a later Linear / LayerNorm backward calls (fp32, row-major):
+ *   linear_dgrad_f32:  out[M][K] = dZ[M][O] (row stride ldz) W[O][K];  O % 16 == 0, K % 4 == 0, ldz % 4 == 0
+ *   linear_wgrad_f32:  dW[O][K] = sum_r dZ[r][o] A[r][k] (row strides ldz, lda), db[O] = sum_r dZ[r][o]; either may be NULL; O, K, ldz, lda multiples of 4
+ *   layernorm_grad:    dx [M][D] (may alias dy), dgamma [D], dbeta [D] of y = LN(x) gamma + beta from dy; each may be NULL; D % 64 == 0, D <= 1024 */
+int must3r_hip_op_linear_dgrad_f32(const float* dZ, int ldz, const float* W, float* out, int M, int O, int K, void* stream);
+size_t must3r_hip_op_linear_wgrad_scratch_bytes(int M, int O, int K);
+int must3r_hip_op_linear_wgrad_f32(const float* dZ, int ldz, const float* A, int lda, float* dW, float* db, int M, int O, int K, void* scratch,
+                                   size_t scratch_bytes, void* stream);
+size_t must3r_hip_op_layernorm_grad_scratch_bytes(int M, int D);
+int must3r_hip_op_layernorm_grad(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int M, int D, float eps,
+                                 void* scratch, size_t scratch_bytes, void* stream);
 
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);

@@ -15,7 +15,7 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 18
+ABI_VERSION = 19
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
@@ -128,6 +128,13 @@ class MetricsLossGradArgs(C.Structure):
                 ("grad_pts", C.c_void_p), ("grad_local", C.c_void_p), ("grad_conf", C.c_void_p)]
 
 
+class HeadGradArgs(C.Structure):
+    """must3r_hip_head_grad_args: inputs and (optional) outputs of the prediction head's backward (include/must3r_hip.h, ABI 19)."""
+    _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("W", C.c_void_p), ("G", C.c_void_p),
+                ("n_views", C.c_int32), ("H", C.c_int32), ("Wimg", C.c_int32), ("D", C.c_int32), ("eps", C.c_float), ("reserved", C.c_int32),
+                ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dW", C.c_void_p), ("db", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -199,6 +206,17 @@ PROTOTYPES = {
     "must3r_hip_op_layernorm_ex": (i32, [P(LnOp), vp]),
     "must3r_hip_op_im2col": (i32, [i32, vp, vp, i32, i32, i32, vp]),
     "must3r_hip_op_cast": (i32, [i32, vp, vp, vp, sz, vp]),
+    "must3r_hip_head_grad_splits": (i32, [i32]),
+    "must3r_hip_head_forward_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_head_forward": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, fp, vp, vp, sz, vp]),
+    "must3r_hip_op_head_linear": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "must3r_hip_head_grad_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_head_grad": (i32, [P(HeadGradArgs), vp, sz, vp]),
+    "must3r_hip_op_linear_dgrad_f32": (i32, [vp, i32, vp, vp, i32, i32, i32, vp]),
+    "must3r_hip_op_linear_wgrad_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_op_linear_wgrad_f32": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "must3r_hip_op_layernorm_grad_scratch_bytes": (sz, [i32, i32]),
+    "must3r_hip_op_layernorm_grad": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, fp, vp, sz, vp]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct must3r_hip_ctx;
+
 namespace m3r {
 
 enum DType { DT_BF16 = 0, DT_F16 = 1 };
@@ -218,6 +220,13 @@ int launch_fill_pos(int64_t* pos, int V, int gh, int gw, hipStream_t s, const ch
 int launch_split16(DType dt, const float* in, void* hi, void* lo, size_t n, hipStream_t s, const char** err);
 // 2:4-sparse copy of the fp16 low part of w fp32 [rows, K] (rows % 32 == 0, K % 64 == 0): vals [K/64][rows][32] fp16, idx [K/64][rows/32][64] dwords (GemmArgs::Wlo_sp)
 int launch_sparse24_pack(const float* w, int rows, int K, void* vals, void* idx, hipStream_t s, const char** err);
+
+// the prediction head's LayerNorm and Linear launches as must3r_hip_decode issues them (model.hip); c may be null (no profiling).
+// hcat: 16-bit [R][3 D] = [y_hi | y_lo | y_hi]; y32 (optional): the fp32 y; wcat: 16-bit [OUT][3 D] = [W_hi | W_hi | W_lo], rows in pixel-shuffle order
+int head_layernorm(must3r_hip_ctx* c, DType dt, const float* x, const float* gamma, const float* beta, void* hcat, float* y32, int R, int D, float eps,
+                   hipStream_t s);
+int head_linear(must3r_hip_ctx* c, DType dt, const void* hcat, const void* wcat, const float* bias_ps, float* pointmaps, int rows, int D, int OUT, int ntok,
+                int gw, int H, int Wimg, int head_views, long long head_scene_skip, hipStream_t s);
 
 // debug: mapping of ds_read_b64_tr_b16 (out: 256 shorts)
 int launch_tr_probe(short* out, hipStream_t s);

@@ -244,6 +244,24 @@ static int layernorm(must3r_hip_ctx* c, DType dt, const float* x, const float* a
                      void* o16, void* o16lo, float* o32, float* copy, int M, int C, float eps, hipStream_t s) {
     return layernorm_a(c, dt, lnargs(x, add, w, b, o16, o16lo, o32, copy, M, C, eps), s);
 }
+// The two launches of the prediction head, shared by must3r_hip_decode and the training forward (train_head.hip; c = nullptr there: no profiling):
+// LayerNorm of the residual stream into the [y_hi | y_lo | y_hi] rows of 3 D (+ the fp32 y of return_feats), then ONE plain GEMM over K = 3 D against the
+// pixel-shuffle-ordered [W_hi | W_hi | W_lo] rows, scattered to [views][H][W][7].
+int m3r::head_layernorm(must3r_hip_ctx* c, DType dt, const float* x, const float* gamma, const float* beta, void* hcat, float* y32, int R, int D, float eps,
+                        hipStream_t s) {
+    uint16_t* h = reinterpret_cast<uint16_t*>(hcat);
+    LnArgs la = lnargs(x, nullptr, gamma, beta, h, h + D, y32, nullptr, R, D, eps);
+    la.out16_dup = h + 2 * D;
+    la.ld16 = 3 * D;
+    return layernorm_a(c, dt, la, s);
+}
+int m3r::head_linear(must3r_hip_ctx* c, DType dt, const void* hcat, const void* wcat, const float* bias_ps, float* pointmaps, int rows, int D, int OUT, int ntok,
+                     int gw, int H, int Wimg, int head_views, long long head_scene_skip, hipStream_t s) {
+    GemmArgs ga = gargs(hcat, wcat, bias_ps, pointmaps, rows, OUT, 3 * D, 3 * D, 0);
+    ga.ntok = ntok; ga.gw = gw; ga.H = H; ga.Wimg = Wimg;
+    ga.head_views = head_views; ga.head_scene_skip = head_scene_skip;
+    return gemm(c, dt, EPI_HEAD, ga, s);
+}
 static int quant8(must3r_hip_ctx* c, DType dt, const void* in16, int ld_in, void* out8, int ld_out, void* const* out_table,
                   int rows_per_group, size_t rows, int cols, int tail_cols, hipStream_t s) {
 #ifdef M3R_ATTN_FP8
@@ -1244,13 +1262,8 @@ static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void*
     {
     // --- prediction head in split precision (fp32-equivalent; decoder.py:149-156 runs it in fp32):
         //     y = LN(x); out = y_hi W_hi + y_lo W_hi + y_hi W_lo + b, pixel-shuffled to [n,H,W,7]
-        {
-            LnArgs la = lnargs(x, nullptr, p32(c, "decoder.norm_dec.weight"), p32(c, "decoder.norm_dec.bias"), hcat, hcat + D,
-                               A->feats ? A->feats + (size_t)(L - 1) * R * D : nullptr, nullptr, R, D, 1e-6f);
-            la.out16_dup = hcat + 2 * D;
-            la.ld16 = 3 * D;
-            M3R_OK(layernorm_a(c, dt, la, hs_));
-        }
+        M3R_OK(head_layernorm(c, dt, x, p32(c, "decoder.norm_dec.weight"), p32(c, "decoder.norm_dec.bias"), hcat,
+                              A->feats ? A->feats + (size_t)(L - 1) * R * D : nullptr, R, D, 1e-6f, hs_));
         const void* wcat;
         M3R_OK(w3(c, "decoder.head_dec.proj_ps.weight", dt, &wcat, hs_));
         for (int b = 0; b < (one_block ? 1 : S); ++b)
@@ -1260,11 +1273,10 @@ static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void*
                 const int Rg = one_block ? S * rg : rg;                      // one group: all scenes in one launch ([S, n, H, W, 7] is contiguous)
                 const size_t scene_elems = (size_t)G.n_views * G.H * G.W * 7;
                 const size_t scene_stride = G.pointmaps_scene_stride > 0 ? (size_t)G.pointmaps_scene_stride : scene_elems;
-                GemmArgs ga = gargs(hcat + ((size_t)b * Rs + grow0[gi]) * 3 * D, wcat, p32(c, "decoder.head_dec.proj_ps.bias"),
-                                    G.pointmaps + (size_t)b * scene_stride, Rg, OUT, 3 * D, 3 * D, 0);
-                ga.ntok = G.n_tokens; ga.gw = G.W / 16; ga.H = G.H; ga.Wimg = G.W;
-                if (one_block && scene_stride != scene_elems) { ga.head_views = G.n_views; ga.head_scene_skip = (long long)(scene_stride - scene_elems); }
-                M3R_OK(gemm(c, dt, EPI_HEAD, ga, hs_));
+                const bool skip = one_block && scene_stride != scene_elems;
+                M3R_OK(head_linear(c, dt, hcat + ((size_t)b * Rs + grow0[gi]) * 3 * D, wcat, p32(c, "decoder.head_dec.proj_ps.bias"),
+                                   G.pointmaps + (size_t)b * scene_stride, Rg, D, OUT, G.n_tokens, G.W / 16, G.H, G.W, skip ? G.n_views : 0,
+                                   skip ? (long long)(scene_stride - scene_elems) : 0, hs_));
             }
     }
     if (update) {

@@ -1,0 +1,581 @@
+// Training forward and backward of the prediction head (decoder.py:149-156, blocks/head.py:63-72, tools/image.py:9-14):
+//   y = LN(x) gamma + beta,  z = y W^T + b,  pointmaps[v, 16 gy + i, 16 gx + j, c] = z[v N + gy gw + gx, c 256 + i 16 + j].
+// The forward is the decoder's own head (kernels.hpp head_layernorm / head_linear) on operands packed from the fp32 parameters of
+// the call.  The backward keeps fp32 operands on v_mfma_f32_16x16x4_f32 (exact products, k-ordered fmaf chain: a result does not
+// depend on how the rows were tiled), recomputes the row statistics from x and saves nothing:
+//
+//   row_stats_kernel      (mu, rstd) per row of x, one wave per row, two passes over the row.
+//   perm_w_kernel         W rows in the order o' = (i 16 + j) 7 + c, in which one token's 1792 upstream values are 16 runs of 112
+//                         consecutive floats of G (448-byte reads); dZ is never materialised.
+//   dgrad_kernel<GATHER>  dY[M, K] = dZ[M, O] W[O, K]: 128 x 128 tiles, 16-deep steps over O through LDS, 4 waves of 64 x 64.  dZ rows are
+//                         read along their fast dimension (LDS rows padded to 20 floats: conflict-free), W rows as they lie.
+//   wgrad_kernel<GATHER>  P_s[O, K] = sum_{r in split s} dZ[r, o] x^[r, k]: both operands have the contraction as their slow dimension, the
+//                         LDS tiles [r][.] feed the MFMA lanes with consecutive addresses.  x^ = (x - mu) rstd is formed on load.  The
+//                         blocks of the first column tile also leave the column sums of their dZ rows (db partials).
+//   wgrad_reduce_kernel   sums the S partials in split order and writes dW[o, k] = gamma[k] sum_s P_s[o', k] + beta[k] db[o] at the
+//                         un-permuted row, db[o] = sum_s of the column-sum partials.
+//   ln_grad_kernel        per row: g^ = dY gamma, dx = rstd (g^ - mean(g^) - x^ mean(g^ x^)), in place over dY; row-walking waves keep
+//                         per-lane column sums of dY x^ and dY, one partial per block.
+//   ln_grad_reduce_kernel sums the block partials in a fixed two-level order (16 interleaved slices, then the slices): dgamma, dbeta.
+// The split count of the weight gradient and the block count of the LayerNorm backward are functions of the row count alone.  No atomics:
+// every output element has one writer and a fixed order of operations.
+#include "abi.hpp"
+#include "common.hpp"
+#include "kernels.hpp"
+
+namespace m3r {
+
+constexpr int HM = 128, HN = 128, HK = 16, HAP = 20, HBP = 144;   // HAP / HBP: LDS row strides (floats) of [128][16] / [16][128] tiles
+constexpr int HEAD_P2 = 256, HEAD_C = 7, HEAD_RUN = 16 * HEAD_C;  // 16 x 16 patch, 7 channels, one pixel row of a patch = 112 floats
+constexpr int WGRAD_MAX_SPLITS = 16, WGRAD_ROWS_PER_SPLIT = 128;
+constexpr int LNG_MAX_BLOCKS = 1024, LNG_MIN_ROWS = 16, LNG_MAX_T = 16;   // LayerNorm backward: D <= 64 * LNG_MAX_T
+
+// where the rows of dZ come from: a plain [M][ld] matrix, or the pixel-unshuffle of G [n_views][H][W][7]
+struct DzSrc {
+    const float* p;
+    long long ld;          // plain: row stride
+    int ntok, gw, H, Wimg; // gather: tokens per view, patches per image row, image size
+};
+template <bool GATHER> __device__ __forceinline__ size_t dz_row(const DzSrc& z, int r) {
+    if constexpr (!GATHER) return (size_t)r * (size_t)z.ld;
+    const int v = r / z.ntok, t = r - v * z.ntok, gy = t / z.gw, gx = t - gy * z.gw;
+    return (((size_t)v * z.H + 16 * gy) * z.Wimg + 16 * gx) * HEAD_C;
+}
+// column o' (a multiple of 4) of a row -> offset from the row's start
+template <bool GATHER> __device__ __forceinline__ size_t dz_col(const DzSrc& z, int o) {
+    if constexpr (!GATHER) return (size_t)o;
+    const int i = o / HEAD_RUN;
+    return (size_t)i * z.Wimg * HEAD_C + (o - i * HEAD_RUN);
+}
+
+__global__ void __launch_bounds__(256) row_stats_kernel(const float* __restrict__ x, int M, int D, float eps, float2* __restrict__ stats) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= M) return;
+    const float* xr = x + (size_t)row * D;
+    float s = 0.f;
+    for (int c = lane; c < D; c += 64) s += xr[c];
+    const float mu = wave_sum_dpp(s) / (float)D;
+    float q = 0.f;
+    for (int c = lane; c < D; c += 64) { const float d = xr[c] - mu; q += d * d; }
+    const float var = wave_sum_dpp(q) / (float)D;
+    if (lane == 0) stats[row] = make_float2(mu, 1.0f / sqrtf(var + eps));
+}
+
+// Wp[(i 16 + j) 7 + c][:] = W[c 256 + i 16 + j][:]
+__global__ void __launch_bounds__(256) perm_w_kernel(const float* __restrict__ W, int D, float* __restrict__ Wp) {
+    const int o = blockIdx.x, src = (o % HEAD_C) * HEAD_P2 + o / HEAD_C;
+    for (int k = threadIdx.x * 4; k < D; k += 1024)
+        *reinterpret_cast<f32x4*>(Wp + (size_t)o * D + k) = *reinterpret_cast<const f32x4*>(W + (size_t)src * D + k);
+}
+
+// forward operands from the fp32 parameters: rows in pixel-shuffle order, [W_hi | W_hi | W_lo] (model.hip w3) and the permuted bias
+template <class T>
+__global__ void __launch_bounds__(256) pack_w3_kernel(const float* __restrict__ W, const float* __restrict__ b, int D, T* __restrict__ wcat,
+                                                      float* __restrict__ bias_ps) {
+    typedef typename Vec<T>::v4 v4;
+    const int o = blockIdx.x, src = (o % HEAD_C) * HEAD_P2 + o / HEAD_C;
+    T* row = wcat + (size_t)o * 3 * D;
+    for (int k = threadIdx.x * 4; k < D; k += 1024) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(W + (size_t)src * D + k);
+        const v4 h = cvt4<T>(w);
+        const f32x4 hf = __builtin_convertvector(h, f32x4);
+        *reinterpret_cast<v4*>(row + k) = h;
+        *reinterpret_cast<v4*>(row + D + k) = h;
+        *reinterpret_cast<v4*>(row + 2 * D + k) = cvt4<T>(w - hf);
+    }
+    if (threadIdx.x == 0) bias_ps[o] = b[src];
+}
+
+// y fp32 [M][D] -> [y_hi | y_lo | y_hi] rows of 3 D, as the head LayerNorm leaves them
+template <class T>
+__global__ void __launch_bounds__(256) split3_kernel(const float* __restrict__ y, int D, T* __restrict__ hcat) {
+    typedef typename Vec<T>::v4 v4;
+    const size_t r = blockIdx.x;
+    T* row = hcat + r * 3 * D;
+    for (int k = threadIdx.x * 4; k < D; k += 1024) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(y + r * D + k);
+        const v4 h = cvt4<T>(v);
+        const f32x4 hf = __builtin_convertvector(h, f32x4);
+        *reinterpret_cast<v4*>(row + k) = h;
+        *reinterpret_cast<v4*>(row + D + k) = cvt4<T>(v - hf);
+        *reinterpret_cast<v4*>(row + 2 * D + k) = h;
+    }
+}
+
+// out[M, K] = dZ[M, O] W[O, K];  O % 16 == 0, K % 4 == 0; tail rows and columns are zero-filled on load and not stored
+template <bool GATHER>
+__global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __restrict__ W, float* __restrict__ out, int M, int O, int K, int n_tiles) {
+    __shared__ __attribute__((aligned(16))) float As[HM * HAP];
+    __shared__ __attribute__((aligned(16))) float Bs[HK * HBP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int fr = lane & 15, fk = lane >> 4;
+    const int m0 = (blockIdx.x / n_tiles) * HM, n0 = (blockIdx.x % n_tiles) * HN;
+    // staging: A 128 rows x 16 floats and B 16 rows x 128 floats, 512 float4 each, two per thread
+    int ar[2], ac[2], br[2], bc[2];
+    size_t abase[2];
+    bool aok[2], bok[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int idx = e * 256 + tid;
+        ar[e] = idx >> 2; ac[e] = (idx & 3) * 4;
+        br[e] = idx >> 5; bc[e] = (idx & 31) * 4;
+        aok[e] = m0 + ar[e] < M;
+        abase[e] = aok[e] ? dz_row<GATHER>(z, m0 + ar[e]) : 0;
+        bok[e] = n0 + bc[e] < K;
+    }
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 ra[2], rb[2];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            ra[e] = aok[e] ? *reinterpret_cast<const f32x4*>(z.p + abase[e] + dz_col<GATHER>(z, k0 + ac[e])) : f32x4{0.f, 0.f, 0.f, 0.f};
+            rb[e] = bok[e] ? *reinterpret_cast<const f32x4*>(W + (size_t)(k0 + br[e]) * K + n0 + bc[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < O; k0 += HK) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            *reinterpret_cast<f32x4*>(As + ar[e] * HAP + ac[e]) = ra[e];
+            *reinterpret_cast<f32x4*>(Bs + br[e] * HBP + bc[e]) = rb[e];
+        }
+        __syncthreads();
+        if (k0 + HK < O) fetch(k0 + HK);
+#pragma unroll
+        for (int ks = 0; ks < HK / 4; ++ks) {
+            float a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[i] = As[(wm * 64 + i * 16 + fr) * HAP + ks * 4 + fk];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = Bs[(ks * 4 + fk) * HBP + wn * 64 + j * 16 + fr];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+    }
+    // C/D map: row 4 (lane / 16) + r, column lane & 15
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + wm * 64 + i * 16 + fk * 4 + r;
+            if (m >= M) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n = n0 + wn * 64 + j * 16 + fr;
+                if (n < K) out[(size_t)m * K + n] = acc[i][j][r];
+            }
+        }
+}
+
+// part[split][O][K] = sum over the split's rows of dZ[r, o] a[r, k], a = (A - mu) rstd with `stats`, A itself without; pdb[split][O] = the
+// column sums of the split's dZ rows (blocks of column tile 0).  want_dw = 0: only the column sums (grid of one column tile).
+template <bool GATHER>
+__global__ void __launch_bounds__(256) wgrad_kernel(DzSrc z, const float* __restrict__ A, int lda, const float2* __restrict__ stats, int M, int O, int K,
+                                                    int rows_per_split, int o_tiles, int n_tiles, int want_dw, float* __restrict__ part,
+                                                    float* __restrict__ pdb) {
+    __shared__ __attribute__((aligned(16))) float As[HK * HBP];
+    __shared__ __attribute__((aligned(16))) float Bs[HK * HBP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int fr = lane & 15, fk = lane >> 4;
+    const int tile = blockIdx.x % (o_tiles * n_tiles), split = blockIdx.x / (o_tiles * n_tiles);
+    const int o0 = (tile / n_tiles) * HM, n0 = (tile % n_tiles) * HN;
+    const int r_lo = split * rows_per_split, r_hi = min(M, r_lo + rows_per_split);
+    int sr[2], sc[2];
+    size_t zcol[2];
+    bool zok[2], bok[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int idx = e * 256 + tid;
+        sr[e] = idx >> 5; sc[e] = (idx & 31) * 4;
+        zok[e] = o0 + sc[e] < O;
+        zcol[e] = zok[e] ? dz_col<GATHER>(z, o0 + sc[e]) : 0;
+        bok[e] = want_dw && n0 + sc[e] < K;
+    }
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 ra[2], rb[2];
+    auto fetch = [&](int r0) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int r = r0 + sr[e];
+            const bool in = r < r_hi;
+            ra[e] = in && zok[e] ? *reinterpret_cast<const f32x4*>(z.p + dz_row<GATHER>(z, r) + zcol[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
+            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (in && bok[e]) {
+                v = *reinterpret_cast<const f32x4*>(A + (size_t)r * lda + n0 + sc[e]);
+                if (stats) { const float2 st = stats[r]; v = (v - st.x) * st.y; }
+            }
+            rb[e] = v;
+        }
+    };
+    const bool sum_cols = n0 == 0 && tid < HM;
+    float colsum = 0.f;
+    fetch(r_lo);
+    for (int r0 = r_lo; r0 < r_hi; r0 += HK) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            *reinterpret_cast<f32x4*>(As + sr[e] * HBP + sc[e]) = ra[e];
+            *reinterpret_cast<f32x4*>(Bs + sr[e] * HBP + sc[e]) = rb[e];
+        }
+        __syncthreads();
+        if (r0 + HK < r_hi) fetch(r0 + HK);
+        if (sum_cols) {
+#pragma unroll
+            for (int rr = 0; rr < HK; ++rr) colsum += As[rr * HBP + tid];
+        }
+        if (want_dw) {
+#pragma unroll
+            for (int ks = 0; ks < HK / 4; ++ks) {
+                float a[4], b[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a[i] = As[(ks * 4 + fk) * HBP + wm * 64 + i * 16 + fr];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) b[j] = Bs[(ks * 4 + fk) * HBP + wn * 64 + j * 16 + fr];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    }
+    if (sum_cols && o0 + tid < O) pdb[(size_t)split * O + o0 + tid] = colsum;
+    if (!want_dw) return;
+    float* P = part + (size_t)split * O * K;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int o = o0 + wm * 64 + i * 16 + fk * 4 + r;
+            if (o >= O) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n = n0 + wn * 64 + j * 16 + fr;
+                if (n < K) P[(size_t)o * K + n] = acc[i][j][r];
+            }
+        }
+}
+
+// one block per row o' of the partials; unperm: the row is written at (o' % 7) 256 + o' / 7.  gamma / beta NULL: dW = sum_s P_s.
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ pdb, int S, int O, int K,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta, int unperm,
+                                                           float* __restrict__ dW, float* __restrict__ db) {
+    const int o = blockIdx.x, dst = unperm ? (o % HEAD_C) * HEAD_P2 + o / HEAD_C : o;
+    float bsum = 0.f;
+    for (int s = 0; s < S; ++s) bsum += pdb[(size_t)s * O + o];
+    if (db && threadIdx.x == 0) db[dst] = bsum;
+    if (!dW) return;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        float v = 0.f;
+        for (int s = 0; s < S; ++s) v += part[((size_t)s * O + o) * K + k];
+        dW[(size_t)dst * K + k] = gamma ? gamma[k] * v + beta[k] * bsum : v;
+    }
+}
+
+// dx may alias dy (each element is read before it is written, by the lane that writes it).  part [blocks][2][D]: column sums of dy x^ and dy.
+__global__ void __launch_bounds__(256) ln_grad_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float2* __restrict__ stats,
+                                                      const float* dy, float* dx, int M, int D, int rows_per_block, float* __restrict__ part) {
+    __shared__ float red[3 * 2 * 64 * LNG_MAX_T];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, T = D / 64;
+    const int r_lo = blockIdx.x * rows_per_block, r_hi = min(M, r_lo + rows_per_block);
+    float g[LNG_MAX_T], ag[LNG_MAX_T], ab[LNG_MAX_T];
+#pragma unroll
+    for (int t = 0; t < LNG_MAX_T; ++t) {
+        g[t] = t < T ? gamma[t * 64 + lane] : 0.f;
+        ag[t] = 0.f; ab[t] = 0.f;
+    }
+    for (int r = r_lo + wave; r < r_hi; r += 4) {
+        const float2 st = stats[r];
+        const size_t o = (size_t)r * D;
+        float xh[LNG_MAX_T], gh[LNG_MAX_T];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int t = 0; t < LNG_MAX_T; ++t)
+            if (t < T) {
+                const float d = dy[o + t * 64 + lane];
+                xh[t] = (x[o + t * 64 + lane] - st.x) * st.y;
+                gh[t] = d * g[t];
+                s1 += gh[t];
+                s2 += gh[t] * xh[t];
+                ag[t] += d * xh[t];
+                ab[t] += d;
+            }
+        const float m1 = wave_sum_dpp(s1) / (float)D, m2 = wave_sum_dpp(s2) / (float)D;
+        if (dx) {
+#pragma unroll
+            for (int t = 0; t < LNG_MAX_T; ++t)
+                if (t < T) dx[o + t * 64 + lane] = st.y * (gh[t] - m1 - xh[t] * m2);
+        }
+    }
+    if (!part) return;
+    // waves 1..3 -> LDS, wave 0 adds them in wave order
+    if (wave > 0) {
+#pragma unroll
+        for (int t = 0; t < LNG_MAX_T; ++t)
+            if (t < T) {
+                red[((wave - 1) * 2 + 0) * 64 * LNG_MAX_T + t * 64 + lane] = ag[t];
+                red[((wave - 1) * 2 + 1) * 64 * LNG_MAX_T + t * 64 + lane] = ab[t];
+            }
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int t = 0; t < LNG_MAX_T; ++t)
+            if (t < T) {
+                float a = ag[t], b = ab[t];
+                for (int w = 0; w < 3; ++w) {
+                    a += red[(w * 2 + 0) * 64 * LNG_MAX_T + t * 64 + lane];
+                    b += red[(w * 2 + 1) * 64 * LNG_MAX_T + t * 64 + lane];
+                }
+                part[((size_t)blockIdx.x * 2 + 0) * D + t * 64 + lane] = a;
+                part[((size_t)blockIdx.x * 2 + 1) * D + t * 64 + lane] = b;
+            }
+    }
+}
+
+// 16 columns per block; slice q of 16 adds the partials of blocks q, q + 16, ... in that order, then one thread per column adds the 16 slices in slice order
+__global__ void __launch_bounds__(256) ln_grad_reduce_kernel(const float* __restrict__ part, int NB, int D, float* __restrict__ dgamma,
+                                                             float* __restrict__ dbeta) {
+    __shared__ float ra[16][17], rb[16][17];
+    const int c = threadIdx.x & 15, q = threadIdx.x >> 4, k = blockIdx.x * 16 + c;
+    float a = 0.f, b = 0.f;
+    for (int i = q; i < NB; i += 16) {
+        a += part[((size_t)i * 2 + 0) * D + k];
+        b += part[((size_t)i * 2 + 1) * D + k];
+    }
+    ra[q][c] = a; rb[q][c] = b;
+    __syncthreads();
+    if (q != 0) return;
+    a = ra[0][c]; b = rb[0][c];
+    for (int j = 1; j < 16; ++j) { a += ra[j][c]; b += rb[j][c]; }
+    if (dgamma) dgamma[k] = a;
+    if (dbeta) dbeta[k] = b;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------------------------
+#define M3R_RUN(expr)                 \
+    do {                              \
+        int rc__ = (expr);            \
+        if (rc__) return rc__;        \
+    } while (0)
+
+static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+static int wgrad_splits(long long R) {
+    const long long s = (R + WGRAD_ROWS_PER_SPLIT - 1) / WGRAD_ROWS_PER_SPLIT;
+    return (int)(s < 1 ? 1 : (s > WGRAD_MAX_SPLITS ? WGRAD_MAX_SPLITS : s));
+}
+static int wgrad_rows_per_split(int R) {   // a multiple of the 16-row step, so that no step straddles two splits
+    const int S = wgrad_splits(R), rows = (R + S - 1) / S;
+    return (rows + HK - 1) / HK * HK;
+}
+static int lng_rows_per_block(int R) {
+    const int rows = (R + LNG_MAX_BLOCKS - 1) / LNG_MAX_BLOCKS;
+    return rows < LNG_MIN_ROWS ? LNG_MIN_ROWS : rows;
+}
+static int lng_blocks(int R) { const int rpb = lng_rows_per_block(R); return (R + rpb - 1) / rpb; }
+
+static size_t wgrad_scratch(int M, int O, int K) { return up256((size_t)wgrad_splits(M) * O * K * 4) + up256((size_t)wgrad_splits(M) * O * 4); }
+static size_t lng_scratch(int M, int D) { return up256((size_t)M * 8) + up256((size_t)lng_blocks(M) * 2 * D * 4); }
+
+static bool misaligned(const void* p) { return ((size_t)p & 15) != 0; }
+
+static int run_dgrad(bool gather, const DzSrc& z, const float* W, float* out, int M, int O, int K, hipStream_t s) {
+    const int n_tiles = (K + HN - 1) / HN;
+    const long long blocks = (long long)((M + HM - 1) / HM) * n_tiles;
+    if (blocks > 0x7fffffffLL) return fail("linear_dgrad: too many rows");
+    if (gather) hipLaunchKernelGGL(dgrad_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles);
+    else hipLaunchKernelGGL(dgrad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles);
+    if (hipGetLastError() != hipSuccess) return fail("linear_dgrad: launch failed");
+    return 0;
+}
+
+// scratch: [partials S O K | column-sum partials S O]
+static int run_wgrad(bool gather, const DzSrc& z, const float* A, int lda, const float2* stats, int M, int O, int K, const float* gamma,
+                     const float* beta, float* dW, float* db, char* scratch, hipStream_t s) {
+    const int S = wgrad_splits(M), rps = wgrad_rows_per_split(M), want_dw = dW ? 1 : 0;
+    const int o_tiles = (O + HM - 1) / HM, n_tiles = want_dw ? (K + HN - 1) / HN : 1;
+    float* part = reinterpret_cast<float*>(scratch);
+    float* pdb = reinterpret_cast<float*>(scratch + up256((size_t)S * O * K * 4));
+    const dim3 grid((unsigned)(o_tiles * n_tiles * S));
+    if (gather) hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
+    else hipLaunchKernelGGL(wgrad_kernel<false>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(O), dim3(256), 0, s, part, pdb, S, O, K, gamma, beta, gather ? 1 : 0, dW, db);
+    if (hipGetLastError() != hipSuccess) return fail("linear_wgrad: launch failed");
+    return 0;
+}
+
+static int run_stats(const float* x, int M, int D, float eps, float2* stats, hipStream_t s) {
+    hipLaunchKernelGGL(row_stats_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, M, D, eps, stats);
+    if (hipGetLastError() != hipSuccess) return fail("head_grad: the statistics launch failed");
+    return 0;
+}
+
+// part: lng_blocks(M) x 2 x D floats, or NULL when neither dgamma nor dbeta is asked for
+static int run_ln_grad(const float* x, const float* gamma, const float2* stats, const float* dy, float* dx, float* dgamma, float* dbeta, int M, int D,
+                       float* part, hipStream_t s) {
+    const int NB = lng_blocks(M), rpb = lng_rows_per_block(M);
+    const bool cols = dgamma || dbeta;
+    hipLaunchKernelGGL(ln_grad_kernel, dim3(NB), dim3(256), 0, s, x, gamma, stats, dy, dx, M, D, rpb, cols ? part : nullptr);
+    if (cols) hipLaunchKernelGGL(ln_grad_reduce_kernel, dim3(D / 16), dim3(256), 0, s, part, NB, D, dgamma, dbeta);
+    if (hipGetLastError() != hipSuccess) return fail("layernorm_grad: launch failed");
+    return 0;
+}
+
+static const char* head_shape_error(int n_views, int H, int Wimg, int D) {
+    if (n_views <= 0 || H <= 0 || Wimg <= 0) return "n_views, H and W must be positive";
+    if (H % 16 || Wimg % 16) return "H and W must be multiples of 16";
+    if (D <= 0 || D % 64) return "D must be a positive multiple of 64";
+    if (D > 64 * LNG_MAX_T) return "D must not exceed 1024";
+    if ((long long)n_views * (H / 16) * (Wimg / 16) > 0x7fffffffLL / 4) return "too many tokens";
+    return nullptr;
+}
+
+static size_t head_forward_scratch(int R, int D) {
+    const size_t O = HEAD_C * HEAD_P2;
+    return up256((size_t)R * 3 * D * 2) + up256(O * 3 * D * 2) + up256(O * 4);
+}
+
+// y fp32 [R][D] given: the Linear stage alone; x given: LayerNorm first
+static int head_forward(int dtype, const float* x, const float* y, const float* gamma, const float* beta, const float* W, const float* b, int n_views,
+                        int H, int Wimg, int D, float eps, float* pointmaps, void* scratch, size_t scratch_bytes, void* stream, const char* who) {
+    if (const char* e = head_shape_error(n_views, H, Wimg, D)) return fail("%s: %s", who, e);
+    if (dtype != MUST3R_BF16 && dtype != MUST3R_F16) return fail("%s: dtype must be MUST3R_BF16 or MUST3R_F16", who);
+    if (!(x || y) || !W || !b || !pointmaps || (x && (!gamma || !beta))) return fail("%s: null argument", who);
+    if (misaligned(x) || misaligned(y) || misaligned(W) || misaligned(pointmaps)) return fail("%s: tensors must be 16-byte aligned", who);
+    const int ntok = (H / 16) * (Wimg / 16), R = n_views * ntok, O = HEAD_C * HEAD_P2;
+    if (!scratch || scratch_bytes < head_forward_scratch(R, D) || misaligned(scratch)) return fail("%s: scratch too small", who);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const DType dt = dtype == MUST3R_BF16 ? DT_BF16 : DT_F16;
+    char* p = reinterpret_cast<char*>(scratch);
+    void* hcat = p;
+    void* wcat = p + up256((size_t)R * 3 * D * 2);
+    float* bias_ps = reinterpret_cast<float*>(p + up256((size_t)R * 3 * D * 2) + up256((size_t)O * 3 * D * 2));
+    if (dt == DT_BF16) hipLaunchKernelGGL(pack_w3_kernel<bf16_t>, dim3(O), dim3(256), 0, s, W, b, D, (bf16_t*)wcat, bias_ps);
+    else hipLaunchKernelGGL(pack_w3_kernel<f16_t>, dim3(O), dim3(256), 0, s, W, b, D, (f16_t*)wcat, bias_ps);
+    if (x) {
+        if (head_layernorm(nullptr, dt, x, gamma, beta, hcat, nullptr, R, D, eps, s)) return 1;
+    } else {
+        if (dt == DT_BF16) hipLaunchKernelGGL(split3_kernel<bf16_t>, dim3(R), dim3(256), 0, s, y, D, (bf16_t*)hcat);
+        else hipLaunchKernelGGL(split3_kernel<f16_t>, dim3(R), dim3(256), 0, s, y, D, (f16_t*)hcat);
+    }
+    if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
+    return head_linear(nullptr, dt, hcat, wcat, bias_ps, pointmaps, R, D, O, ntok, Wimg / 16, H, Wimg, 0, 0, s);
+}
+
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" int must3r_hip_head_grad_splits(int rows) { return rows > 0 ? wgrad_splits(rows) : 0; }
+
+extern "C" size_t must3r_hip_head_forward_scratch_bytes(int n_views, int H, int Wimg, int D) {
+    if (const char* e = head_shape_error(n_views, H, Wimg, D)) { fail("head_forward_scratch_bytes: %s", e); return 0; }
+    return head_forward_scratch(n_views * (H / 16) * (Wimg / 16), D);
+}
+
+extern "C" int must3r_hip_head_forward(int dtype, const float* x, const float* gamma, const float* beta, const float* W, const float* b, int n_views,
+                                       int H, int Wimg, int D, float eps, float* pointmaps, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!x) return fail("head_forward: null argument");
+    return head_forward(dtype, x, nullptr, gamma, beta, W, b, n_views, H, Wimg, D, eps, pointmaps, scratch, scratch_bytes, stream, "head_forward");
+}
+
+extern "C" int must3r_hip_op_head_linear(int dtype, const float* y, const float* W, const float* b, int n_views, int H, int Wimg, int D,
+                                         float* pointmaps, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!y) return fail("op_head_linear: null argument");
+    return head_forward(dtype, nullptr, y, nullptr, nullptr, W, b, n_views, H, Wimg, D, 0.f, pointmaps, scratch, scratch_bytes, stream, "op_head_linear");
+}
+
+// scratch of must3r_hip_head_grad: [statistics R x 2 | permuted W | weight-gradient partials and column sums | LayerNorm column partials]
+extern "C" size_t must3r_hip_head_grad_scratch_bytes(int n_views, int H, int Wimg, int D) {
+    if (const char* e = head_shape_error(n_views, H, Wimg, D)) { fail("head_grad_scratch_bytes: %s", e); return 0; }
+    const int R = n_views * (H / 16) * (Wimg / 16), O = HEAD_C * HEAD_P2;
+    return up256((size_t)R * 8) + up256((size_t)O * D * 4) + wgrad_scratch(R, O, D) + up256((size_t)lng_blocks(R) * 2 * D * 4);
+}
+
+extern "C" int must3r_hip_head_grad(const must3r_hip_head_grad_args* a, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!a) return fail("head_grad: null argument");
+    if (const char* e = head_shape_error(a->n_views, a->H, a->Wimg, a->D)) return fail("head_grad: %s", e);
+    const bool want_w = a->dW || a->db, want_x = a->dx || a->dgamma || a->dbeta;
+    if (!a->G) return fail("head_grad: null argument (G)");
+    if (a->dW && (!a->x || !a->gamma || !a->beta)) return fail("head_grad: null argument (dW needs x, gamma and beta)");
+    if (want_x && (!a->x || !a->gamma || !a->W)) return fail("head_grad: null argument (dx, dgamma and dbeta need x, gamma and W)");
+    if (misaligned(a->x) || misaligned(a->W) || misaligned(a->G) || misaligned(a->dx) || misaligned(a->dW))
+        return fail("head_grad: tensors must be 16-byte aligned");
+    if (!scratch || misaligned(scratch) || scratch_bytes < must3r_hip_head_grad_scratch_bytes(a->n_views, a->H, a->Wimg, a->D))
+        return fail("head_grad: scratch too small");
+    const int D = a->D, ntok = (a->H / 16) * (a->Wimg / 16), R = a->n_views * ntok, O = HEAD_C * HEAD_P2;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    char* p = reinterpret_cast<char*>(scratch);
+    float2* stats = reinterpret_cast<float2*>(p); p += up256((size_t)R * 8);
+    float* Wp = reinterpret_cast<float*>(p); p += up256((size_t)O * D * 4);
+    char* wscr = p; p += wgrad_scratch(R, O, D);
+    float* lpart = reinterpret_cast<float*>(p);
+    const DzSrc z{a->G, 0, ntok, a->Wimg / 16, a->H, a->Wimg};
+    if (a->dW || want_x) M3R_RUN(run_stats(a->x, R, D, a->eps, stats, s));
+    if (want_w) M3R_RUN(run_wgrad(true, z, a->x, D, stats, R, O, D, a->gamma, a->beta, a->dW, a->db, wscr, s));
+    if (want_x) {
+        // dY goes where dx will be; without dx it needs a home of its own, which the caller did not give: the partials' space is free again
+        // only after the reduce above has read it (stream order), and R D floats may not fit there -- so dgamma / dbeta alone still need dx
+        if (!a->dx) return fail("head_grad: dgamma / dbeta without dx is not provided for (dY lives in the dx buffer)");
+        hipLaunchKernelGGL(perm_w_kernel, dim3(O), dim3(256), 0, s, a->W, D, Wp);
+        M3R_RUN(run_dgrad(true, z, Wp, a->dx, R, O, D, s));
+        M3R_RUN(run_ln_grad(a->x, a->gamma, stats, a->dx, a->dx, a->dgamma, a->dbeta, R, D, lpart, s));
+    }
+    return 0;
+}
+
+extern "C" int must3r_hip_op_linear_dgrad_f32(const float* dZ, int ldz, const float* W, float* out, int M, int O, int K, void* stream) {
+    if (M < 0 || O <= 0 || K <= 0) return fail("op_linear_dgrad_f32: bad shape");
+    if (M == 0) return 0;
+    if (!dZ || !W || !out) return fail("op_linear_dgrad_f32: null argument");
+    if (O % 16 || K % 4 || ldz < O || ldz % 4) return fail("op_linear_dgrad_f32: O must be a multiple of 16, K and ldz of 4, ldz >= O");
+    if (misaligned(dZ) || misaligned(W)) return fail("op_linear_dgrad_f32: dZ and W must be 16-byte aligned");
+    const DzSrc z{dZ, ldz, 0, 0, 0, 0};
+    return run_dgrad(false, z, W, out, M, O, K, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t must3r_hip_op_linear_wgrad_scratch_bytes(int M, int O, int K) {
+    if (M <= 0 || O <= 0 || K <= 0) return 0;
+    return wgrad_scratch(M, O, K);
+}
+
+extern "C" int must3r_hip_op_linear_wgrad_f32(const float* dZ, int ldz, const float* A, int lda, float* dW, float* db, int M, int O, int K,
+                                              void* scratch, size_t scratch_bytes, void* stream) {
+    if (M <= 0 || O <= 0 || K <= 0) return fail("op_linear_wgrad_f32: bad shape");
+    if (!dZ || (dW && !A)) return fail("op_linear_wgrad_f32: null argument");
+    if (!dW && !db) return 0;
+    if (O % 4 || K % 4 || ldz < O || ldz % 4 || (dW && (lda < K || lda % 4))) return fail("op_linear_wgrad_f32: O, K, ldz and lda must be multiples of 4, ldz >= O, lda >= K");
+    if (misaligned(dZ) || misaligned(A)) return fail("op_linear_wgrad_f32: dZ and A must be 16-byte aligned");
+    if (!scratch || misaligned(scratch) || scratch_bytes < wgrad_scratch(M, O, K)) return fail("op_linear_wgrad_f32: scratch too small");
+    const DzSrc z{dZ, ldz, 0, 0, 0, 0};
+    return run_wgrad(false, z, A, lda, nullptr, M, O, K, nullptr, nullptr, dW, db, reinterpret_cast<char*>(scratch), reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t must3r_hip_op_layernorm_grad_scratch_bytes(int M, int D) {
+    if (M <= 0 || D <= 0) return 0;
+    return lng_scratch(M, D);
+}
+
+extern "C" int must3r_hip_op_layernorm_grad(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int M, int D,
+                                            float eps, void* scratch, size_t scratch_bytes, void* stream) {
+    if (M <= 0 || D <= 0 || D % 64 || D > 64 * LNG_MAX_T) return fail("op_layernorm_grad: M must be positive, D a multiple of 64 and at most 1024");
+    if (!x || !gamma || !dy) return fail("op_layernorm_grad: null argument");
+    if (!dx && !dgamma && !dbeta) return 0;
+    if (!scratch || misaligned(scratch) || scratch_bytes < lng_scratch(M, D)) return fail("op_layernorm_grad: scratch too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float2* stats = reinterpret_cast<float2*>(scratch);
+    float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + up256((size_t)M * 8));
+    M3R_RUN(run_stats(x, M, D, eps, stats, s));
+    return run_ln_grad(x, gamma, stats, dy, dx, dgamma, dbeta, M, D, part, s);
+}

@@ -1,0 +1,206 @@
+"""The prediction head with a backward pass: ``MUSt3R._compute_prediction_head`` (decoder.py:149-156: ``norm_dec`` LayerNorm, ``head_dec.proj``
+Linear D -> 7 * 16 * 16, pixel shuffle to ``[n, H, W, 7]``; blocks/head.py:63-72, tools/image.py:9-14) under ``torch.autograd``, the link between the
+decoder's last-layer tokens and ``must3r_amd.train_losses``::
+
+    head = PredictionHead.from_decoder(decoder)
+    raw = head(tokens, true_shape)                                    # tokens.requires_grad or not
+    loss, details = criterion(gt, train_losses.postprocess(raw, 'norm_exp'))
+    loss.backward()                                                   # tokens.grad, head.*.grad
+    torch.optim.AdamW(head.parameters()).step()
+
+The forward is the native decoder's own head (the same two launches, ``must3r_hip_head_forward``) on operands packed from the fp32 parameters of the
+call, so that an optimizer step is seen by the next forward.  The backward (``must3r_hip_head_grad``, include/must3r_hip.h ABI 19) runs fp32 operands on
+the fp32 MFMA, recomputes the LayerNorm statistics from the tokens and reads the upstream gradient in place: the forward saves its five inputs and
+nothing else.  Only the gradients that ``needs_input_grad`` asks for are computed.  First order only (``once_differentiable``); gradients come back
+in the shape and dtype of their inputs.  CPU tensors raise.
+"""
+import ctypes as C
+
+import torch
+import torch.nn as nn
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+
+PATCH, CHANNELS = 16, 7
+OUT = CHANNELS * PATCH * PATCH
+WGRAD_MAX_SPLITS, WGRAD_ROWS_PER_SPLIT = 16, 128
+
+
+def wgrad_splits(rows):
+    """Over how many blocks the weight gradient splits its sum over ``rows`` token rows (``must3r_hip_head_grad_splits``): a function of the
+    row count alone, so that the order of the additions, and with it every bit of the result, is fixed by the shapes."""
+    return max(1, min(WGRAD_MAX_SPLITS, -(-int(rows) // WGRAD_ROWS_PER_SPLIT))) if rows > 0 else 0
+
+
+def _dev(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"must3r_amd.train_head: {what} must be a tensor on the GPU (there is no CPU path)")
+    return t
+
+
+def _f32(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _scratch(nbytes, dev):
+    if not nbytes:
+        raise _lib.HipError(_lib.load().must3r_hip_last_error().decode("utf-8", "replace"))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+
+
+def _check_shapes(tokens, img_shape, norm_weight, norm_bias, proj_weight, proj_bias):
+    H, W = int(img_shape[0]), int(img_shape[1])
+    if H <= 0 or W <= 0 or H % PATCH or W % PATCH:
+        raise ValueError(f"prediction_head: the image size {(H, W)} is not a positive multiple of {PATCH}")
+    if tokens.ndim < 2:
+        raise ValueError(f"prediction_head: tokens of shape {tuple(tokens.shape)}, expected [..., N, D]")
+    N, D = int(tokens.shape[-2]), int(tokens.shape[-1])
+    if N != (H // PATCH) * (W // PATCH):
+        raise ValueError(f"prediction_head: {N} tokens per view do not match an image of {H} x {W} ({(H // PATCH) * (W // PATCH)} patches)")
+    if tuple(norm_weight.shape) != (D,) or tuple(norm_bias.shape) != (D,) or tuple(proj_weight.shape) != (OUT, D) or tuple(proj_bias.shape) != (OUT,):
+        raise ValueError(f"prediction_head: parameters of shapes {tuple(norm_weight.shape)}, {tuple(norm_bias.shape)}, {tuple(proj_weight.shape)}, "
+                         f"{tuple(proj_bias.shape)} do not belong to tokens of width {D}")
+    return H, W, N, D
+
+
+def head_forward(x, gamma, beta, W, b, n_views, H, Wimg, eps=1e-6, dtype=_lib.F16):
+    """``must3r_hip_head_forward`` on contiguous fp32 tensors: x [n_views * N, D] -> pointmaps [n_views, H, Wimg, 7]."""
+    lib = _lib.load()
+    D = int(x.shape[-1])
+    out = torch.empty((n_views, H, Wimg, CHANNELS), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        nbytes = lib.must3r_hip_head_forward_scratch_bytes(n_views, H, Wimg, D)
+        scratch = _scratch(nbytes, x.device)
+        _lib.check(lib.must3r_hip_head_forward(dtype, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(b), n_views, H, Wimg, D, eps, _ptr(out),
+                                               _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(x.device))))
+    return out
+
+
+def head_linear(y, W, b, n_views, H, Wimg, dtype=_lib.F16):
+    """The Linear stage of the head alone (``must3r_hip_op_head_linear``): y fp32 [n_views * N, D], already normalised -> [n_views, H, Wimg, 7]."""
+    lib = _lib.load()
+    y, W, b = (_f32(_dev(t, n)) for t, n in ((y, "y"), (W, "W"), (b, "b")))
+    D = int(y.shape[-1])
+    out = torch.empty((n_views, H, Wimg, CHANNELS), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        nbytes = lib.must3r_hip_head_forward_scratch_bytes(n_views, H, Wimg, D)
+        scratch = _scratch(nbytes, y.device)
+        _lib.check(lib.must3r_hip_op_head_linear(dtype, _ptr(y), _ptr(W), _ptr(b), n_views, H, Wimg, D, _ptr(out), _ptr(scratch), nbytes,
+                                                 C.c_void_p(_lib.stream_ptr(y.device))))
+    return out
+
+
+def head_grad(x, gamma, beta, W, G, n_views, H, Wimg, eps=1e-6, want=(True,) * 5):
+    """``must3r_hip_head_grad`` on contiguous fp32 tensors: ``(dx, dgamma, dbeta, dW, db)``, ``None`` where ``want`` says so."""
+    lib = _lib.load()
+    D, dev = int(x.shape[-1]), x.device
+    new = lambda need, *shape: torch.empty(shape, dtype=torch.float32, device=dev) if need else None
+    want_dx, want_dg, want_dbeta, want_dw, want_db = want
+    # dY lives in the dx buffer: the column sums of the LayerNorm backward need one even when the tokens are frozen
+    dx = new(want_dx or want_dg or want_dbeta, *x.shape)
+    dgamma, dbeta, dW, db = new(want_dg, D), new(want_dbeta, D), new(want_dw, OUT, D), new(want_db, OUT)
+    a = _lib.HeadGradArgs()
+    a.x, a.gamma, a.beta, a.W, a.G = _ptr(x), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(G)
+    a.n_views, a.H, a.Wimg, a.D, a.eps = n_views, H, Wimg, D, eps
+    a.dx, a.dgamma, a.dbeta, a.dW, a.db = _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(dW), _ptr(db)
+    with torch.cuda.device(dev):
+        nbytes = lib.must3r_hip_head_grad_scratch_bytes(n_views, H, Wimg, D)
+        scratch = _scratch(nbytes, dev)
+        _lib.check(lib.must3r_hip_head_grad(C.byref(a), _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(dev))))
+    return (dx if want_dx else None), dgamma, dbeta, dW, db
+
+
+class _Head(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tokens, norm_weight, norm_bias, proj_weight, proj_bias, H, W, eps, dtype):
+        D = int(tokens.shape[-1])
+        lead = tuple(tokens.shape[:-2])
+        n_views = tokens.numel() // (int(tokens.shape[-2]) * D)
+        ctx.save_for_backward(tokens, norm_weight, norm_bias, proj_weight, proj_bias)
+        ctx.geom = (n_views, H, W, eps)
+        out = head_forward(_f32(tokens).view(-1, D), _f32(norm_weight), _f32(norm_bias), _f32(proj_weight), _f32(proj_bias), n_views, H, W, eps, dtype)
+        return out.view(*lead, H, W, CHANNELS)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        n_views, H, W, eps = ctx.geom
+        x, gamma, beta, Wt, _ = (_f32(t) for t in saved)
+        grads = head_grad(x.view(-1, x.shape[-1]), gamma, beta, Wt, _f32(grad_out), n_views, H, W, eps, want=tuple(ctx.needs_input_grad[:5]))
+        out = [None if g is None else g.reshape(t.shape).to(t.dtype) for g, t in zip(grads, saved)]
+        return (*out, None, None, None, None)
+
+
+def prediction_head(tokens, img_shape, norm_weight, norm_bias, proj_weight, proj_bias, eps=1e-6, dtype=_lib.F16):
+    """Raw pointmaps ``[..., H, W, 7]`` fp32 from the decoder's last-layer tokens ``[..., N, D]`` (before ``norm_dec``), ``img_shape = (H, W)`` shared
+    by every view; differentiable at the tokens and the four parameters.  ``dtype``: the 16-bit operand type of the forward's split-precision
+    products (``_lib.F16`` / ``_lib.BF16``), as in the native decoder."""
+    H, W, N, D = _check_shapes(tokens, img_shape, norm_weight, norm_bias, proj_weight, proj_bias)
+    for t, what in ((tokens, "tokens"), (norm_weight, "norm_weight"), (norm_bias, "norm_bias"), (proj_weight, "proj_weight"), (proj_bias, "proj_bias")):
+        _dev(t, what)
+    if tokens.numel() == 0:
+        raise ValueError("prediction_head: no tokens")
+    inputs = (tokens, norm_weight, norm_bias, proj_weight, proj_bias)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in inputs):
+        return _Head.apply(*inputs, H, W, float(eps), int(dtype))
+    n_views = tokens.numel() // (N * D)
+    out = head_forward(_f32(tokens).view(-1, D), *(_f32(t) for t in inputs[1:]), n_views, H, W, float(eps), int(dtype))
+    return out.view(*tokens.shape[:-2], H, W, CHANNELS)
+
+
+class _Affine(nn.Module):
+    def __init__(self, dim):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(dim))
+        self.bias = nn.Parameter(torch.zeros(dim))
+
+
+class _Proj(nn.Module):
+    def __init__(self, dim, out):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(out, dim))
+        self.bias = nn.Parameter(torch.zeros(out))
+        nn.init.xavier_uniform_(self.weight)
+
+
+class _HeadDec(nn.Module):
+    def __init__(self, dim, out):
+        super().__init__()
+        self.proj = _Proj(dim, out)
+
+
+class PredictionHead(nn.Module):
+    """``norm_dec`` and ``head_dec`` of the decoder as a trainable module; the parameters live under the reference's state-dict keys
+    (``norm_dec.weight``, ``norm_dec.bias``, ``head_dec.proj.weight``, ``head_dec.proj.bias``) in fp32."""
+
+    def __init__(self, embed_dim=768, eps=1e-6, dtype=_lib.F16):
+        super().__init__()
+        self.embed_dim, self.eps, self.dtype = int(embed_dim), float(eps), int(dtype)
+        self.norm_dec = _Affine(self.embed_dim)
+        self.head_dec = _HeadDec(self.embed_dim, OUT)
+
+    @classmethod
+    def from_decoder(cls, decoder, dtype=_lib.F16):
+        """fp32 copies of a loaded decoder's four head tensors (the decoder itself is left alone)."""
+        w = decoder.norm_dec.weight
+        head = cls(int(w.shape[0]), float(decoder.norm_dec.eps), dtype)
+        with torch.no_grad():
+            for dst, src in ((head.norm_dec.weight, w), (head.norm_dec.bias, decoder.norm_dec.bias),
+                             (head.head_dec.proj.weight, decoder.head_dec.proj.weight), (head.head_dec.proj.bias, decoder.head_dec.proj.bias)):
+                dst.copy_(src.detach().to(torch.float32))
+        return head.to(w.device)
+
+    def forward(self, tokens, true_shape):
+        """tokens ``[B, nimgs, N, D]`` (or ``[nimgs, N, D]``), true_shape ``[B, nimgs, 2]`` of (H, W) rows, all alike -> ``[B, nimgs, H, W, 7]``."""
+        ts = torch.as_tensor(true_shape).reshape(-1, 2).cpu()
+        H, W = int(ts[0, 0]), int(ts[0, 1])
+        if not bool((ts == ts[0]).all()):
+            raise ValueError("PredictionHead: all views of a call must share (H, W)")
+        return prediction_head(tokens, (H, W), self.norm_dec.weight, self.norm_dec.bias, self.head_dec.proj.weight, self.head_dec.proj.bias,
+                               self.eps, self.dtype)
