@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 19
+#define MUST3R_HIP_ABI_VERSION 20
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -702,6 +702,43 @@ int must3r_hip_op_linear_wgrad_f32(const float* dZ, int ldz, const float* A, int
 size_t must3r_hip_op_layernorm_grad_scratch_bytes(int M, int D);
 int must3r_hip_op_layernorm_grad(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int M, int D, float eps,
                                  void* scratch, size_t scratch_bytes, void* stream);
+
+/* ABI 20.  Training forward and backward of the attention core, softmax(Q K^T / 8) V per head of 64 (blocks/attention.py CoreAttention.attention), stateless, fp32
+ * operands on v_mfma_f32_16x16x4_f32.  The views are the table of must3r_hip_op_attention, int32 [n_views][6] = q_row0, nq, kv_row0, nk, skip_lo, skip_hi, but given
+ * as a HOST pointer: the entry points group the views on the host and upload what the kernels read into the scratch buffer.  Per head, s = 1/8, key j of a view
+ * valid when j < nk and j is not in [skip_lo, skip_hi):
+ *   S_ij = s q_i.k_j      lse_i = log sum_valid exp(S_ij)      P_ij = exp(S_ij - lse_i)  (0 where invalid)
+ *   O_i  = sum_j P_ij v_j                 delta_i = dO_i . O_i
+ *   dV_j = sum_i P_ij dO_i                dP_ij = dO_i . v_j            dS_ij = P_ij (dP_ij - delta_i)
+ *   dQ_i = s sum_j dS_ij k_j              dK_j  = s sum_i dS_ij q_i
+ * A query row without a valid key has O = 0 (lse = -inf), gives nothing to dK / dV and has dQ = 0.  q, k, v, dO, O, dQ, dK, dV are fp32 with a row stride in
+ * elements each (at least heads * 64, a multiple of 4), so that q, k and v may be the column blocks of one packed [R][3 D] tensor; lse is [rows][heads].
+ * must3r_hip_attn_forward_f32 writes O (required) and lse (optional).  must3r_hip_attn_grad needs dO and writes whichever of dQ, dK, dV are non-NULL: it runs
+ * the forward kernel once more (row statistics and delta into scratch; O is never stored), then one launch for dK and dV (skipped when neither is asked for) and one
+ * for dQ (skipped without dQ).  An output that is not asked for is not written.
+ * Key groups: dK and dV sum over every view that reads a key row.  The views are partitioned by kv_row0; a group spans rows [kv_row0, kv_row0 + max nk) and one
+ * block per (group, head, 64-row tile) adds the views' contributions in the order of the table -- no atomics, repeated calls agree bit for bit, and a group's
+ * result does not depend on the other groups of the call.  Views that share key rows must therefore share kv_row0 (the decoder's cross attention does, causal
+ * prefixes included: one group per scene); two groups whose spans overlap are refused.  Rows of dK / dV outside every group's span and rows of dQ outside every view
+ * are not written; a key row inside a span that no view attends gets zeros.  must3r_hip_attn_train_groups returns the number of groups of a table, or -1 with an
+ * error where must3r_hip_attn_grad would refuse it (no device needed).
+ * Scratch (must3r_hip_attn_train_scratch_bytes; total_q_rows = max(q_row0 + nq), total_kv_rows = max(kv_row0 + nk); 0 on a bad shape; no device needed):
+ * [views | groups | per-group view lists | lse (log2 domain) rows x heads | delta rows x heads].
+ * Refused with an error: null required pointers, heads <= 0, a leading dimension below heads * 64 or not a multiple of 4, pointers not 16-byte aligned, negative
+ * table entries, skip_lo > skip_hi or skip_hi > nk, more than 65535 views, overlapping groups (attn_grad), scratch too small. */
+typedef struct must3r_hip_attn_train_args {
+    const float* q; const float* k; const float* v; const float* dO;   /* dO: must3r_hip_attn_grad only */
+    int32_t ldq, ldk, ldv, lddo;
+    int32_t heads, n_views;
+    const int32_t* views;              /* HOST int32 [n_views][6] */
+    float* O; float* lse;              /* must3r_hip_attn_forward_f32 */
+    float* dQ; float* dK; float* dV;   /* must3r_hip_attn_grad, each optional */
+    int32_t ldo, lddq, lddk, lddv;
+} must3r_hip_attn_train_args;
+size_t must3r_hip_attn_train_scratch_bytes(int n_views, int total_q_rows, int total_kv_rows, int heads);
+int must3r_hip_attn_train_groups(const int32_t* views_host, int n_views);
+int must3r_hip_attn_forward_f32(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream);
+int must3r_hip_attn_grad(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream);
 
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);

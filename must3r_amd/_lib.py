@@ -15,7 +15,7 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 19
+ABI_VERSION = 20
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
@@ -135,6 +135,14 @@ class HeadGradArgs(C.Structure):
                 ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dW", C.c_void_p), ("db", C.c_void_p)]
 
 
+class AttnTrainArgs(C.Structure):
+    """must3r_hip_attn_train_args: operands, HOST view table and (optional) outputs of the attention training forward / backward (include/must3r_hip.h, ABI 20)."""
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("dO", C.c_void_p),
+                ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("lddo", C.c_int32), ("heads", C.c_int32), ("n_views", C.c_int32),
+                ("views", C.c_void_p), ("O", C.c_void_p), ("lse", C.c_void_p), ("dQ", C.c_void_p), ("dK", C.c_void_p), ("dV", C.c_void_p),
+                ("ldo", C.c_int32), ("lddq", C.c_int32), ("lddk", C.c_int32), ("lddv", C.c_int32)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -217,6 +225,10 @@ PROTOTYPES = {
     "must3r_hip_op_linear_wgrad_f32": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, sz, vp]),
     "must3r_hip_op_layernorm_grad_scratch_bytes": (sz, [i32, i32]),
     "must3r_hip_op_layernorm_grad": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, fp, vp, sz, vp]),
+    "must3r_hip_attn_train_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_attn_train_groups": (i32, [vp, i32]),
+    "must3r_hip_attn_forward_f32": (i32, [P(AttnTrainArgs), vp, sz, vp]),
+    "must3r_hip_attn_grad": (i32, [P(AttnTrainArgs), vp, sz, vp]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -1,0 +1,571 @@
+// Training forward and backward of the attention core (blocks/attention.py CoreAttention.attention): softmax(Q K^T / 8) V per head of 64, driven by the
+// 6-int view table of the inference kernels (kernels.hpp AttnView).  Per head, s = 1/8, query row i of a view, key row j of its key range; j is valid when
+// j < nk and j is not in [skip_lo, skip_hi):
+//
+//   S_ij = s q_i.k_j      lse_i = log sum_valid exp(S_ij)      P_ij = exp(S_ij - lse_i)  (0 where invalid)
+//   O_i  = sum_j P_ij v_j                 delta_i = dO_i . O_i
+//   dV_j = sum_i P_ij dO_i                dP_ij = dO_i . v_j            dS_ij = P_ij (dP_ij - delta_i)
+//   dQ_i = s sum_j dS_ij k_j              dK_j  = s sum_i dS_ij q_i
+//
+// A query row without a valid key has O = 0, contributes nothing to dK / dV and gets dQ = 0 (as the inference kernels define it).
+// fp32 operands on v_mfma_f32_16x16x4_f32 (upstream gradients of a mean-reduced loss are of order 1e-8, below fp16's range); exp2f with log2(e) folded into the
+// scale.  The forward saves nothing but its inputs, the backward recomputes S:
+//
+//   attn_fwd_f32   one block per (view, head, 64-row query tile): online softmax over the view's 64-row key tiles.  Optional outputs O, lse (natural
+//                  log, -inf for a row without keys), lse2 (log2 domain, +inf for such a row: the backward's P is then 0) and delta (needs dO).  The training
+//                  forward (O) and the backward's first launch (lse2 and delta into scratch, O never stored) are this one kernel.
+//   attn_dkv_f32   one block per (key group, head, 64-row key tile): dK and dV of the tile stay in registers while the block walks the group's views in table
+//                  order and each view's query tiles in row order; a (view, key tile) pair at or past the view's nk or wholly inside its skip range is
+//                  skipped.  It computes S^T = K Q^T and dP^T = V dO^T, so that P^T and dS^T come out with the key on the accumulator row.
+//   attn_dq_f32    one block per (view, head, 64-row query tile): walks the view's key tiles in order, recomputes S and dP, writes dQ once.
+//
+// A block is 4 waves, each owning 16 rows of the tile's 64 and all 64 columns (4 accumulators of 16 x 16).  The operand that belongs to the block's own rows (Q and
+// dO, or K and V in attn_dkv_f32) lives in registers as 16-step A fragments read once from global memory; the walked tiles go through LDS ([64][68] floats: rows
+// 16-byte aligned, at most 2-way bank conflicts in either read orientation), each fetched into registers one step ahead, under the products of the tile before it.  P and dS leave the MFMA in the accumulator layout (row 4 (lane / 16) + r, column
+// lane % 16) and are the A operand of the next product: they pass through one LDS tile, each wave its own 16 rows.
+// No atomics: every output element has one writer and a fixed order of additions (views in table order, tiles in row order, k ascending inside a product).
+#include <algorithm>
+#include <string.h>
+#include <vector>
+
+#include "abi.hpp"
+#include "common.hpp"
+#include "kernels.hpp"
+
+namespace m3r {
+
+constexpr int TA_T = 64, TA_LD = 68;             // tile rows / head size, LDS row stride in floats
+constexpr float TA_SCALE = 0.125f;
+constexpr float TA_C = 0.125f * 1.4426950408889634f;   // scale * log2(e)
+constexpr float TA_LN2 = 0.6931471805599453f;
+
+struct TaGroup { int kv_row0, extent, first, count; };   // views list[first .. first + count) read key rows [kv_row0, kv_row0 + extent)
+
+struct TaArgs {
+    const float* Q; const float* K; const float* V; const float* dO;
+    int ldq, ldk, ldv, lddo, heads;
+    const AttnView* views;
+    const TaGroup* groups; const int* list;
+    float* O; int ldo;
+    float* lse;                  // [rows][heads], natural log (public)
+    float* lse2; float* delta;   // [rows][heads], scratch of the backward
+    float* dQ; float* dK; float* dV;
+    int lddq, lddk, lddv;
+};
+
+// rows [0, rows_valid) of a [.][64] slab at src (row stride ld) -> registers (4 float4 per thread), the rest zero; then registers -> dst [64][TA_LD].
+// The next tile is fetched while the current one is multiplied, so that its global-memory latency hides under the MFMAs.
+__device__ __forceinline__ void ta_fetch_tile(f32x4 (&x)[4], const float* __restrict__ src, int ld, int rows_valid, int tid) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int idx = e * 256 + tid, r = idx >> 4, c = (idx & 15) * 4;
+        x[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (r < rows_valid) x[e] = *reinterpret_cast<const f32x4*>(src + (size_t)r * ld + c);
+    }
+}
+__device__ __forceinline__ void ta_put_tile(float* dst, const f32x4 (&x)[4], int tid) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int idx = e * 256 + tid, r = idx >> 4, c = (idx & 15) * 4;
+        *reinterpret_cast<f32x4*>(dst + r * TA_LD + c) = x[e];
+    }
+}
+// the A fragments of one row: a[ks] = row[4 ks + fk]
+__device__ __forceinline__ void ta_load_frag(float (&a)[16], const float* __restrict__ row, bool ok, int fk) {
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) a[ks] = ok ? row[4 * ks + fk] : 0.f;
+}
+// acc (16 x 64 of the wave) += A B, A in registers.  TB: B[k][col] = Bs[col][k], else Bs[k][col]
+template <bool TB>
+__device__ __forceinline__ void ta_mm_reg(f32x4 (&acc)[4], const float (&a)[16], const float* Bs, int fr, int fk) {
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+        const int k = ks * 4 + fk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float b = TB ? Bs[(j * 16 + fr) * TA_LD + k] : Bs[k * TA_LD + j * 16 + fr];
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks], b, acc[j], 0, 0, 0);
+        }
+    }
+}
+// the same with A = the wave's 16 rows of an LDS tile, B[k][col] = Bs[k][col]
+__device__ __forceinline__ void ta_mm_lds(f32x4 (&acc)[4], const float* As, const float* Bs, int fr, int fk) {
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+        const int k = ks * 4 + fk;
+        const float a = As[fr * TA_LD + k];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Bs[k * TA_LD + j * 16 + fr], acc[j], 0, 0, 0);
+    }
+}
+// accumulator layout -> the wave's 16 rows of an LDS tile
+__device__ __forceinline__ void ta_stage(float* Ws, const f32x4 (&x)[4], int fr, int fk) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Ws[(fk * 4 + r) * TA_LD + j * 16 + fr] = x[j][r];
+}
+__device__ __forceinline__ float ta_max16(float v) {
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ float ta_sum16(float v) {
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ bool ta_valid(const AttnView& v, int j) { return j < v.nk && !(j >= v.skip_lo && j < v.skip_hi); }
+__device__ __forceinline__ bool ta_tile_skipped(const AttnView& v, int k0) { return k0 >= v.nk || (k0 >= v.skip_lo && k0 + TA_T <= v.skip_hi); }
+// the first key tile at or after k0 that the view reads (>= nk: none)
+__device__ __forceinline__ int ta_next_tile(const AttnView& v, int k0) {
+    while (k0 < v.nk && ta_tile_skipped(v, k0)) k0 += TA_T;
+    return k0;
+}
+
+__global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
+    __shared__ __attribute__((aligned(16))) float Ks[TA_T * TA_LD];
+    __shared__ __attribute__((aligned(16))) float Vs[TA_T * TA_LD];
+    __shared__ __attribute__((aligned(16))) float Ps[TA_T * TA_LD];
+    const AttnView v = a.views[blockIdx.z];
+    const int q0 = blockIdx.x * TA_T, h = blockIdx.y;
+    if (q0 >= v.nq) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const float inf = __builtin_inff();
+    float qa[16];
+    {
+        const int qr = q0 + w * 16 + fr;
+        ta_load_frag(qa, a.Q + (size_t)(v.q_row0 + qr) * a.ldq + h * TA_T, qr < v.nq, fk);
+    }
+    float m[4], l[4];
+    f32x4 o[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[r] = -inf; l[r] = 0.f; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 rk[4], rv[4];
+    auto fetch = [&](int k) {
+        ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
+        ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
+    };
+    int k0 = ta_next_tile(v, 0);
+    if (k0 < v.nk) fetch(k0);
+    while (k0 < v.nk) {
+        __syncthreads();
+        ta_put_tile(Ks, rk, tid);
+        ta_put_tile(Vs, rv, tid);
+        __syncthreads();
+        const int k_next = ta_next_tile(v, k0 + TA_T);
+        if (k_next < v.nk) fetch(k_next);
+        f32x4 s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        ta_mm_reg<true>(s, qa, Ks, fr, fk);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool ok = ta_valid(v, k0 + j * 16 + fr);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[j][r] = ok ? s[j][r] * TA_C : -inf;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float mx = ta_max16(fmaxf(fmaxf(s[0][r], s[1][r]), fmaxf(s[2][r], s[3][r])));
+            const float mn = fmaxf(m[r], mx), ms = mn == -inf ? 0.f : mn;
+            const float alpha = exp2f(m[r] - ms);
+            float sum = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float p = exp2f(s[j][r] - ms);
+                s[j][r] = p;
+                sum += p;
+                o[j][r] *= alpha;
+            }
+            l[r] = l[r] * alpha + ta_sum16(sum);
+            m[r] = mn;
+        }
+        ta_stage(Ps + w * 16 * TA_LD, s, fr, fk);
+        __syncthreads();
+        ta_mm_lds(o, Ps + w * 16 * TA_LD, Vs, fr, fk);
+        k0 = k_next;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int qr = q0 + w * 16 + fk * 4 + r;
+        const bool ok = qr < v.nq;
+        const size_t row = (size_t)(v.q_row0 + qr);
+        const float inv = l[r] > 0.f ? 1.0f / l[r] : 0.f;
+        float d = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float x = o[j][r] * inv;
+            if (ok && a.O) a.O[row * a.ldo + h * TA_T + j * 16 + fr] = x;
+            if (a.delta) d += x * (ok ? a.dO[row * a.lddo + h * TA_T + j * 16 + fr] : 0.f);
+        }
+        if (a.delta) {
+            d = ta_sum16(d);
+            if (ok && fr == 0) a.delta[row * a.heads + h] = d;
+        }
+        if (ok && fr == 0) {
+            const float l2 = l[r] > 0.f ? m[r] + log2f(l[r]) : inf;
+            if (a.lse2) a.lse2[row * a.heads + h] = l2;
+            if (a.lse) a.lse[row * a.heads + h] = l[r] > 0.f ? l2 * TA_LN2 : -inf;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
+    __shared__ __attribute__((aligned(16))) float Ks[TA_T * TA_LD];
+    __shared__ __attribute__((aligned(16))) float Vs[TA_T * TA_LD];
+    __shared__ __attribute__((aligned(16))) float Ps[TA_T * TA_LD];
+    const AttnView v = a.views[blockIdx.z];
+    const int q0 = blockIdx.x * TA_T, h = blockIdx.y;
+    if (q0 >= v.nq) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const float inf = __builtin_inff();
+    float qa[16], da[16];
+    {
+        const int qr = q0 + w * 16 + fr;
+        ta_load_frag(qa, a.Q + (size_t)(v.q_row0 + qr) * a.ldq + h * TA_T, qr < v.nq, fk);
+        ta_load_frag(da, a.dO + (size_t)(v.q_row0 + qr) * a.lddo + h * TA_T, qr < v.nq, fk);
+    }
+    float lr[4], dl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int qr = q0 + w * 16 + fk * 4 + r;
+        const size_t i = (size_t)(v.q_row0 + qr) * a.heads + h;
+        lr[r] = qr < v.nq ? a.lse2[i] : inf;
+        dl[r] = qr < v.nq ? a.delta[i] : 0.f;
+    }
+    f32x4 dq[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dq[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 rk[4], rv[4];
+    auto fetch = [&](int k) {
+        ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
+        ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
+    };
+    int k0 = ta_next_tile(v, 0);
+    if (k0 < v.nk) fetch(k0);
+    while (k0 < v.nk) {
+        __syncthreads();
+        ta_put_tile(Ks, rk, tid);
+        ta_put_tile(Vs, rv, tid);
+        __syncthreads();
+        const int k_next = ta_next_tile(v, k0 + TA_T);
+        if (k_next < v.nk) fetch(k_next);
+        f32x4 s[4], dp[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        ta_mm_reg<true>(s, qa, Ks, fr, fk);
+        ta_mm_reg<true>(dp, da, Vs, fr, fk);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool ok = ta_valid(v, k0 + j * 16 + fr);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = ok ? exp2f(s[j][r] * TA_C - lr[r]) : 0.f;
+                s[j][r] = p * (dp[j][r] - dl[r]);
+            }
+        }
+        ta_stage(Ps + w * 16 * TA_LD, s, fr, fk);
+        __syncthreads();
+        ta_mm_lds(dq, Ps + w * 16 * TA_LD, Ks, fr, fk);
+        k0 = k_next;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int qr = q0 + w * 16 + fk * 4 + r;
+        if (qr >= v.nq) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a.dQ[(size_t)(v.q_row0 + qr) * a.lddq + h * TA_T + j * 16 + fr] = dq[j][r] * TA_SCALE;
+    }
+}
+
+__global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
+    __shared__ __attribute__((aligned(16))) float Qs[TA_T * TA_LD];
+    __shared__ __attribute__((aligned(16))) float Ds[TA_T * TA_LD];
+    __shared__ __attribute__((aligned(16))) float Ps[TA_T * TA_LD];
+    const TaGroup g = a.groups[blockIdx.z];
+    const int k0 = blockIdx.x * TA_T, h = blockIdx.y;
+    if (k0 >= g.extent) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const float inf = __builtin_inff();
+    float ka[16], va[16];
+    {
+        const int kr = k0 + w * 16 + fr;
+        ta_load_frag(ka, a.K + (size_t)(g.kv_row0 + kr) * a.ldk + h * TA_T, kr < g.extent, fk);
+        ta_load_frag(va, a.V + (size_t)(g.kv_row0 + kr) * a.ldv + h * TA_T, kr < g.extent, fk);
+    }
+    f32x4 dk[4], dv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { dk[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    // the walk over (view in table order, query tile in row order), one step ahead of the products: vi == g.count at the end
+    auto advance = [&](int& vi, int& q0, AttnView& v) {
+        if (vi >= 0 && q0 + TA_T < v.nq) { q0 += TA_T; return; }
+        q0 = 0;
+        for (++vi; vi < g.count; ++vi) {
+            v = a.views[a.list[g.first + vi]];
+            if (v.nq > 0 && !ta_tile_skipped(v, k0)) return;
+        }
+    };
+    f32x4 rq[4], rd[4];
+    auto fetch = [&](const AttnView& v, int q0) {
+        ta_fetch_tile(rq, a.Q + (size_t)(v.q_row0 + q0) * a.ldq + h * TA_T, a.ldq, v.nq - q0, tid);
+        ta_fetch_tile(rd, a.dO + (size_t)(v.q_row0 + q0) * a.lddo + h * TA_T, a.lddo, v.nq - q0, tid);
+    };
+    int vi = -1, q0 = 0;
+    AttnView v{};
+    advance(vi, q0, v);
+    if (vi < g.count) fetch(v, q0);
+    while (vi < g.count) {
+        __syncthreads();
+        ta_put_tile(Qs, rq, tid);
+        ta_put_tile(Ds, rd, tid);
+        __syncthreads();
+        int vi_next = vi, q_next = q0;
+        AttnView v_next = v;
+        advance(vi_next, q_next, v_next);
+        if (vi_next < g.count) fetch(v_next, q_next);
+        bool kok[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) kok[r] = ta_valid(v, k0 + w * 16 + fk * 4 + r);
+        float lc[4], dc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int qi = q0 + j * 16 + fr;
+            const size_t i = (size_t)(v.q_row0 + qi) * a.heads + h;
+            lc[j] = qi < v.nq ? a.lse2[i] : inf;
+            dc[j] = qi < v.nq ? a.delta[i] : 0.f;
+        }
+        f32x4 st[4], dpt[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { st[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dpt[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        ta_mm_reg<true>(st, ka, Qs, fr, fk);
+        ta_mm_reg<true>(dpt, va, Ds, fr, fk);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = kok[r] ? exp2f(st[j][r] * TA_C - lc[j]) : 0.f;
+                st[j][r] = p;
+                dpt[j][r] = p * (dpt[j][r] - dc[j]);
+            }
+        ta_stage(Ps + w * 16 * TA_LD, st, fr, fk);
+        __syncthreads();
+        ta_mm_lds(dv, Ps + w * 16 * TA_LD, Ds, fr, fk);
+        __syncthreads();
+        ta_stage(Ps + w * 16 * TA_LD, dpt, fr, fk);
+        __syncthreads();
+        ta_mm_lds(dk, Ps + w * 16 * TA_LD, Qs, fr, fk);
+        vi = vi_next; q0 = q_next; v = v_next;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int kr = k0 + w * 16 + fk * 4 + r;
+        if (kr >= g.extent) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (a.dK) a.dK[(size_t)(g.kv_row0 + kr) * a.lddk + h * TA_T + j * 16 + fr] = dk[j][r] * TA_SCALE;
+            if (a.dV) a.dV[(size_t)(g.kv_row0 + kr) * a.lddv + h * TA_T + j * 16 + fr] = dv[j][r];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------------------------
+static size_t ta_up256(size_t v) { return (v + 255) / 256 * 256; }
+static bool ta_misaligned(const void* p) { return ((size_t)p & 15) != 0; }
+
+// what the table says, found on the host: the key groups (views partitioned by kv_row0, in order of first appearance; inside a group the
+// views keep the order of the table), the row counts and the grid extents
+struct TaPlan {
+    std::vector<TaGroup> groups;
+    std::vector<int> list;
+    int total_q_rows = 0, max_nq = 0, max_extent = 0;
+    long long total_kv_rows = 0;
+};
+
+// nullptr, or why the table is refused.  want_groups: also build the key groups and refuse overlapping ones.
+static const char* ta_plan(const int32_t* views, int n, bool want_groups, TaPlan& P) {
+    if (!views) return "null argument (views)";
+    if (n <= 0) return "n_views must be positive";
+    if (n > 65535) return "more than 65535 views in one call";
+    for (int i = 0; i < n; ++i) {
+        const int32_t* v = views + 6 * (size_t)i;
+        for (int e = 0; e < 6; ++e)
+            if (v[e] < 0) return "negative table entry";
+        if (v[4] > v[5] || v[5] > v[3]) return "a skip range needs skip_lo <= skip_hi <= nk";
+        if ((long long)v[0] + v[1] > 0x7fffffffLL / 2 || (long long)v[2] + v[3] > 0x7fffffffLL / 2) return "row index too large";
+        P.total_q_rows = std::max(P.total_q_rows, v[0] + v[1]);
+        P.max_nq = std::max(P.max_nq, v[1]);
+        P.total_kv_rows = std::max<long long>(P.total_kv_rows, (long long)v[2] + v[3]);
+    }
+    if (!want_groups) return nullptr;
+    // views ordered by (kv_row0, table index): one run per group
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return views[6 * (size_t)x + 2] < views[6 * (size_t)y + 2]; });
+    std::vector<TaGroup> sorted;   // in kv_row0 order; `first` holds the smallest table index of the group for now
+    std::vector<int> group_of(n);
+    for (int i = 0; i < n; ++i) {
+        const int32_t* v = views + 6 * (size_t)order[i];
+        if (sorted.empty() || sorted.back().kv_row0 != v[2]) sorted.push_back(TaGroup{v[2], 0, order[i], 0});
+        sorted.back().extent = std::max(sorted.back().extent, (int)v[3]);
+        sorted.back().count += 1;
+        group_of[order[i]] = (int)sorted.size() - 1;
+    }
+    long long end = -1;
+    for (const TaGroup& g : sorted) {
+        if (g.extent == 0) continue;
+        if (g.kv_row0 < end) return "overlapping key groups: views that share key rows must share kv_row0";
+        end = (long long)g.kv_row0 + g.extent;
+    }
+    // groups in order of first appearance, lists in table order
+    std::vector<int> by_first(sorted.size());
+    for (size_t i = 0; i < sorted.size(); ++i) by_first[i] = (int)i;
+    std::sort(by_first.begin(), by_first.end(), [&](int x, int y) { return sorted[x].first < sorted[y].first; });
+    std::vector<int> new_id(sorted.size());
+    int first = 0;
+    for (size_t i = 0; i < by_first.size(); ++i) {
+        TaGroup g = sorted[by_first[i]];
+        new_id[by_first[i]] = (int)i;
+        g.first = first;
+        first += g.count;
+        g.count = 0;   // refilled below
+        P.max_extent = std::max(P.max_extent, g.extent);
+        P.groups.push_back(g);
+    }
+    P.list.assign(n, 0);
+    for (int i = 0; i < n; ++i) {
+        TaGroup& g = P.groups[new_id[group_of[i]]];
+        P.list[g.first + g.count++] = i;
+    }
+    return nullptr;
+}
+
+// scratch: [views n x 6 int32 | groups n x 4 int32 | list n int32 | lse2 rows x heads fp32 | delta rows x heads fp32], each part a multiple of 256 bytes
+static size_t ta_tables_bytes(int n) { return ta_up256((size_t)n * 24) + ta_up256((size_t)n * 16) + ta_up256((size_t)n * 4); }
+static size_t ta_scratch(int n, long long q_rows, int heads) { return ta_tables_bytes(n) + 2 * ta_up256((size_t)q_rows * heads * 4); }
+
+// The tables travel through one pinned buffer per calling thread; the event says when the previous call's copy has left it.
+struct TaPin {
+    void* host = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+};
+static thread_local TaPin ta_pin;
+
+static int ta_upload(const TaPlan& P, const int32_t* views, int n, bool want_groups, char* scratch, hipStream_t s, const char* who) {
+    const size_t bytes = ta_tables_bytes(n);
+    TaPin& pin = ta_pin;
+    if (pin.ev) {
+        if (hipEventSynchronize(pin.ev) != hipSuccess) return fail("%s: waiting for the previous table upload failed", who);
+        hipEventDestroy(pin.ev);
+        pin.ev = nullptr;
+    }
+    if (pin.cap < bytes) {
+        if (pin.host) hipHostFree(pin.host);
+        pin.host = nullptr; pin.cap = 0;
+        if (hipHostMalloc(&pin.host, bytes, hipHostMallocDefault) != hipSuccess) { pin.host = nullptr; return fail("%s: no pinned memory for the tables", who); }
+        pin.cap = bytes;
+    }
+    char* h = reinterpret_cast<char*>(pin.host);
+    memset(h, 0, bytes);
+    memcpy(h, views, (size_t)n * 24);
+    if (want_groups) {
+        memcpy(h + ta_up256((size_t)n * 24), P.groups.data(), P.groups.size() * sizeof(TaGroup));
+        memcpy(h + ta_up256((size_t)n * 24) + ta_up256((size_t)n * 16), P.list.data(), (size_t)n * 4);
+    }
+    if (hipMemcpyAsync(scratch, h, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return fail("%s: the table upload failed", who);
+    if (hipEventCreateWithFlags(&pin.ev, hipEventDisableTiming) != hipSuccess) { pin.ev = nullptr; return fail("%s: no event", who); }
+    if (hipEventRecord(pin.ev, s) != hipSuccess) return fail("%s: no event", who);
+    return 0;
+}
+
+static const char* ta_args_error(const must3r_hip_attn_train_args* a, bool grad) {
+    if (!a->q || !a->k || !a->v) return "null argument (q, k, v)";
+    if (grad && !a->dO) return "null argument (dO)";
+    if (!grad && !a->O) return "null argument (O)";
+    if (a->heads <= 0) return "heads must be positive";
+    const int D = a->heads * TA_T;
+    auto bad_ld = [&](int ld) { return ld < D || ld % 4 != 0; };
+    if (bad_ld(a->ldq) || bad_ld(a->ldk) || bad_ld(a->ldv)) return "a leading dimension must be at least heads * 64 and a multiple of 4";
+    if (grad ? bad_ld(a->lddo) || (a->dQ && bad_ld(a->lddq)) || (a->dK && bad_ld(a->lddk)) || (a->dV && bad_ld(a->lddv)) : bad_ld(a->ldo))
+        return "a leading dimension must be at least heads * 64 and a multiple of 4";
+    if (ta_misaligned(a->q) || ta_misaligned(a->k) || ta_misaligned(a->v) || ta_misaligned(a->dO) || ta_misaligned(a->O) || ta_misaligned(a->lse) ||
+        ta_misaligned(a->dQ) || ta_misaligned(a->dK) || ta_misaligned(a->dV))
+        return "tensors must be 16-byte aligned";
+    return nullptr;
+}
+
+static TaArgs ta_kernel_args(const must3r_hip_attn_train_args* a, const TaPlan& P, char* scratch) {
+    const int n = a->n_views;
+    TaArgs k{};
+    k.Q = a->q; k.K = a->k; k.V = a->v; k.dO = a->dO;
+    k.ldq = a->ldq; k.ldk = a->ldk; k.ldv = a->ldv; k.lddo = a->lddo; k.heads = a->heads;
+    char* p = scratch;
+    k.views = reinterpret_cast<const AttnView*>(p); p += ta_up256((size_t)n * 24);
+    k.groups = reinterpret_cast<const TaGroup*>(p); p += ta_up256((size_t)n * 16);
+    k.list = reinterpret_cast<const int*>(p); p += ta_up256((size_t)n * 4);
+    k.lse2 = reinterpret_cast<float*>(p); p += ta_up256((size_t)P.total_q_rows * a->heads * 4);
+    k.delta = reinterpret_cast<float*>(p);
+    return k;
+}
+
+}  // namespace m3r
+using namespace m3r;
+
+extern "C" size_t must3r_hip_attn_train_scratch_bytes(int n_views, int total_q_rows, int total_kv_rows, int heads) {
+    if (n_views <= 0 || n_views > 65535 || total_q_rows < 0 || total_kv_rows < 0 || heads <= 0 || heads > 65535) {
+        fail("attn_train_scratch_bytes: n_views in [1, 65535], non-negative row counts and heads in [1, 65535] are required");
+        return 0;
+    }
+    return ta_scratch(n_views, total_q_rows, heads);
+}
+
+extern "C" int must3r_hip_attn_train_groups(const int32_t* views_host, int n_views) {
+    TaPlan P;
+    if (const char* e = ta_plan(views_host, n_views, true, P)) { fail("attn_train_groups: %s", e); return -1; }
+    return (int)P.groups.size();
+}
+
+extern "C" int must3r_hip_attn_forward_f32(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!a) return fail("attn_forward_f32: null argument");
+    if (const char* e = ta_args_error(a, false)) return fail("attn_forward_f32: %s", e);
+    if (a->heads > 65535) return fail("attn_forward_f32: more than 65535 heads");
+    TaPlan P;
+    if (const char* e = ta_plan(a->views, a->n_views, false, P)) return fail("attn_forward_f32: %s", e);
+    if (!scratch || ta_misaligned(scratch) || scratch_bytes < ta_scratch(a->n_views, P.total_q_rows, a->heads)) return fail("attn_forward_f32: scratch too small");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (P.max_nq == 0) return 0;
+    if (ta_upload(P, a->views, a->n_views, false, reinterpret_cast<char*>(scratch), s, "attn_forward_f32")) return 1;
+    TaArgs k = ta_kernel_args(a, P, reinterpret_cast<char*>(scratch));
+    k.dO = nullptr; k.lse2 = nullptr; k.delta = nullptr;
+    k.O = a->O; k.ldo = a->ldo; k.lse = a->lse;
+    hipLaunchKernelGGL(attn_fwd_f32, dim3((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views), dim3(256), 0, s, k);
+    if (hipGetLastError() != hipSuccess) return fail("attn_forward_f32: launch failed");
+    return 0;
+}
+
+extern "C" int must3r_hip_attn_grad(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!a) return fail("attn_grad: null argument");
+    if (const char* e = ta_args_error(a, true)) return fail("attn_grad: %s", e);
+    if (a->heads > 65535) return fail("attn_grad: more than 65535 heads");
+    TaPlan P;
+    if (const char* e = ta_plan(a->views, a->n_views, true, P)) return fail("attn_grad: %s", e);
+    if (!scratch || ta_misaligned(scratch) || scratch_bytes < ta_scratch(a->n_views, P.total_q_rows, a->heads)) return fail("attn_grad: scratch too small");
+    const bool want_kv = a->dK || a->dV;
+    if (!a->dQ && !want_kv) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (ta_upload(P, a->views, a->n_views, true, reinterpret_cast<char*>(scratch), s, "attn_grad")) return 1;
+    TaArgs k = ta_kernel_args(a, P, reinterpret_cast<char*>(scratch));
+    k.dQ = a->dQ; k.dK = a->dK; k.dV = a->dV; k.lddq = a->lddq; k.lddk = a->lddk; k.lddv = a->lddv;
+    const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views);
+    if (P.max_nq > 0) hipLaunchKernelGGL(attn_fwd_f32, qgrid, dim3(256), 0, s, k);   // lse2 and delta into scratch
+    if (want_kv && P.max_extent > 0)
+        hipLaunchKernelGGL(attn_dkv_f32, dim3((P.max_extent + TA_T - 1) / TA_T, a->heads, (unsigned)P.groups.size()), dim3(256), 0, s, k);
+    if (a->dQ && P.max_nq > 0) hipLaunchKernelGGL(attn_dq_f32, qgrid, dim3(256), 0, s, k);
+    if (hipGetLastError() != hipSuccess) return fail("attn_grad: launch failed");
+    return 0;
+}

@@ -1,0 +1,241 @@
+"""The attention core with a backward pass: ``softmax(Q K^T / 8) V`` per head of 64 (``CoreAttention.attention``, blocks/attention.py) under
+``torch.autograd``, driven by the 6-int view table of the native decoder (q_row0, nq, kv_row0, nk, skip_lo, skip_hi)::
+
+    qkv = ...                                                         # [R, 3 D] fp32, D = heads * 64
+    views = self_views(n_scenes, views_per_scene, n)                  # or memory_views(...) for the cross attention over a scene's memory
+    o = attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], views, heads)
+    loss(o).backward()                                                # qkv.grad
+
+The fp32 forward (``must3r_hip_attn_forward_f32``) and the backward (``must3r_hip_attn_grad``, include/must3r_hip.h ABI 20) run fp32 operands on the fp32
+MFMA; the forward saves q, k, v and the host table and nothing else, the backward recomputes the scores.  ``dtype=_lib.F16`` / ``_lib.BF16`` runs the
+native inference forward (``must3r_hip_op_attention``) on cast operands instead, so that a fine-tuned model sees the arithmetic it will be served with; the
+backward is the same fp32 one.  Only the gradients ``needs_input_grad`` asks for are computed.  dK and dV sum over every view that reads a key row:
+views that share key rows must share ``kv_row0`` (one key group; the decoder's tables do), and overlapping groups are refused.  A query row without a
+valid key has O = 0 and zero gradients (the reference would give NaN).  First order only (``once_differentiable``); CPU tensors raise.
+"""
+import ctypes as C
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+
+HEAD = 64
+
+
+def self_views(n_scenes, views_per_scene, n):
+    """The decoder's self-attention table (model.hip:1004): view j of scene b attends its own ``n`` tokens at rows ``(b V + j) n``."""
+    return [[(b * views_per_scene + j) * n, n, (b * views_per_scene + j) * n, n, 0, 0] for b in range(n_scenes) for j in range(views_per_scene)]
+
+
+def memory_views(n_scenes, views_per_scene, n, Nm, mask=True, causal=False):
+    """The decoder's cross-attention table of a memory update (model.hip:1005-1015): scene b's keys are ``Nm`` memory rows followed by the ``V n`` new
+    tokens, at rows ``b (Nm + V n)``; the queries are the scene's views at rows ``(b V + j) n``.  ``mask``: view j does not attend its own tokens (skip
+    ``[Nm + j n, Nm + (j + 1) n)``); ``causal`` (with ``mask``): view j attends the memory and the views before it, a prefix of ``Nm + j n`` rows -- with
+    an empty memory view 0 attends view 1's tokens instead, rows ``[n, 2 n)`` behind an excluded ``[0, n)``.  A lone view attends the memory alone."""
+    V, Rs = views_per_scene, views_per_scene * n
+    out = []
+    for b in range(n_scenes):
+        for j in range(V):
+            q0, k0 = (b * V + j) * n, b * (Nm + Rs)
+            if V == 1:
+                out.append([q0, n, k0, Nm, 0, 0])
+            elif mask and causal:
+                out.append([q0, n, k0, 2 * n, 0, n] if Nm == 0 and j == 0 else [q0, n, k0, Nm + j * n, 0, 0])
+            elif mask:
+                out.append([q0, n, k0, Nm + Rs, Nm + j * n, Nm + (j + 1) * n])
+            else:
+                out.append([q0, n, k0, Nm + Rs, 0, 0])
+    return out
+
+
+def _dev(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"must3r_amd.train_attention: {what} must be a tensor on the GPU (there is no CPU path)")
+    return t
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _table(views):
+    t = torch.as_tensor(views, dtype=torch.int32).cpu().contiguous()
+    if t.ndim != 2 or t.shape[1] != 6 or t.shape[0] == 0:
+        raise ValueError(f"attention: views of shape {tuple(t.shape)}, expected [n, 6] with n > 0")
+    return t
+
+
+def n_groups(views):
+    """Number of key groups of a table (``must3r_hip_attn_train_groups``); raises where the backward would refuse the table."""
+    t = _table(views)
+    n = _lib.load().must3r_hip_attn_train_groups(C.c_void_p(t.data_ptr()), int(t.shape[0]))
+    if n < 0:
+        raise _lib.HipError(_lib.load().must3r_hip_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def _covers(spans, rows):
+    """Do the half-open spans cover [0, rows)?"""
+    end = 0
+    for lo, hi in sorted(s for s in spans if s[1] > s[0]):
+        if lo > end:
+            return False
+        end = max(end, hi)
+    return end >= rows
+
+
+def q_spans(tab):
+    return [(int(v[0]), int(v[0] + v[1])) for v in tab.tolist()]
+
+
+def kv_spans(tab):
+    ext = {}
+    for v in tab.tolist():
+        ext[v[2]] = max(ext.get(v[2], 0), v[3])
+    return [(k, k + e) for k, e in ext.items()]
+
+
+def _fp32_rows(t, what, heads):
+    """fp32 [R, heads * 64] with a contiguous last dimension and a row stride the kernels take, without a copy where possible."""
+    if t.ndim != 2 or t.shape[1] != heads * HEAD:
+        raise ValueError(f"attention: {what} of shape {tuple(t.shape)}, expected [rows, {heads * HEAD}]")
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    if t.stride(1) != 1 or t.data_ptr() % 16 or (t.shape[0] > 1 and (t.stride(0) % 4 or t.stride(0) < heads * HEAD)):
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def _ld(t):
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def _check_table(tab, Rq, Rk):
+    v = tab.to(torch.int64)
+    if bool((v < 0).any()):
+        raise ValueError("attention: negative table entry")
+    if int((v[:, 0] + v[:, 1]).max()) > Rq or int((v[:, 2] + v[:, 3]).max()) > Rk:
+        raise ValueError(f"attention: the table reaches past the {Rq} query rows or the {Rk} key rows")
+    if bool((v[:, 4] > v[:, 5]).any()) or bool((v[:, 5] > v[:, 3]).any()):
+        raise ValueError("attention: a skip range needs skip_lo <= skip_hi <= nk")
+
+
+def _args(q, k, v, tab, heads):
+    a = _lib.AttnTrainArgs()
+    a.q, a.k, a.v = _ptr(q), _ptr(k), _ptr(v)
+    a.ldq, a.ldk, a.ldv = _ld(q), _ld(k), _ld(v)
+    a.heads, a.n_views, a.views = heads, int(tab.shape[0]), C.c_void_p(tab.data_ptr())
+    return a
+
+
+def _scratch(tab, heads, dev):
+    lib = _lib.load()
+    v = tab.to(torch.int64)
+    nbytes = lib.must3r_hip_attn_train_scratch_bytes(int(tab.shape[0]), int((v[:, 0] + v[:, 1]).max()), int((v[:, 2] + v[:, 3]).max()), heads)
+    if not nbytes:
+        raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+
+
+def _new(rows, cols, dev, covered):
+    return (torch.empty if covered else torch.zeros)((rows, cols), dtype=torch.float32, device=dev)
+
+
+def attention_forward(q, k, v, tab, heads, want_lse=False):
+    """``must3r_hip_attn_forward_f32`` on fp32 row-strided tensors and an int32 CPU table: O [Rq, heads * 64] (zeros in rows of no view), and lse
+    [Rq, heads] (natural log) with ``want_lse``."""
+    lib = _lib.load()
+    dev, Rq = q.device, int(q.shape[0])
+    covered = _covers(q_spans(tab), Rq)
+    o = _new(Rq, heads * HEAD, dev, covered)
+    lse = _new(Rq, heads, dev, covered) if want_lse else None
+    a = _args(q, k, v, tab, heads)
+    a.O, a.ldo, a.lse = _ptr(o), heads * HEAD, _ptr(lse)
+    with torch.cuda.device(dev):
+        scratch, nbytes = _scratch(tab, heads, dev)
+        _lib.check(lib.must3r_hip_attn_forward_f32(C.byref(a), _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(dev))))
+    return (o, lse) if want_lse else o
+
+
+def attention_forward16(q, k, v, tab, heads, dtype):
+    """The native inference forward (``must3r_hip_op_attention``) on operands cast to the 16-bit type of ``dtype``, cast back to fp32."""
+    lib = _lib.load()
+    if dtype not in (_lib.F16, _lib.BF16):
+        raise ValueError("attention: dtype must be None, _lib.F16 or _lib.BF16")
+    dev, Rq = q.device, int(q.shape[0])
+    td = torch.float16 if dtype == _lib.F16 else torch.bfloat16
+    q16, k16, v16 = (t.to(td).contiguous() for t in (q, k, v))
+    o16 = (torch.empty if _covers(q_spans(tab), Rq) else torch.zeros)((Rq, heads * HEAD), dtype=td, device=dev)
+    tab_dev = tab.to(dev)
+    D = heads * HEAD
+    with torch.cuda.device(dev):
+        _lib.check(lib.must3r_hip_op_attention(dtype, _ptr(q16), _ptr(k16), _ptr(v16), _ptr(o16), D, D, D, D, heads, _ptr(tab_dev), int(tab.shape[0]),
+                                               int(tab[:, 1].max()), 0, None, 0, C.c_void_p(_lib.stream_ptr(dev))))
+    return o16.to(torch.float32)
+
+
+def attention_grad(q, k, v, dO, tab, heads, want=(True, True, True)):
+    """``must3r_hip_attn_grad`` on fp32 row-strided tensors: ``(dQ, dK, dV)``, ``None`` where ``want`` says so; zeros in rows the table leaves out."""
+    lib = _lib.load()
+    dev, D = q.device, heads * HEAD
+    dq = _new(int(q.shape[0]), D, dev, _covers(q_spans(tab), int(q.shape[0]))) if want[0] else None
+    kv_covered = _covers(kv_spans(tab), int(k.shape[0]))
+    dk = _new(int(k.shape[0]), D, dev, kv_covered) if want[1] else None
+    dv = _new(int(v.shape[0]), D, dev, kv_covered) if want[2] else None
+    if not any(want):
+        return None, None, None
+    a = _args(q, k, v, tab, heads)
+    a.dO, a.lddo = _ptr(dO), _ld(dO)
+    a.dQ, a.dK, a.dV, a.lddq, a.lddk, a.lddv = _ptr(dq), _ptr(dk), _ptr(dv), D, D, D
+    with torch.cuda.device(dev):
+        scratch, nbytes = _scratch(tab, heads, dev)
+        _lib.check(lib.must3r_hip_attn_grad(C.byref(a), _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(dev))))
+    return dq, dk, dv
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, tab, heads, dtype):
+        ctx.save_for_backward(q, k, v)
+        ctx.tab, ctx.heads = tab, heads
+        return _forward(q, k, v, tab, heads, dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v = ctx.saved_tensors
+        heads = ctx.heads
+        f = [_fp32_rows(t, n, heads) for t, n in ((q, "q"), (k, "k"), (v, "v"), (grad_out, "the upstream gradient"))]
+        grads = attention_grad(*f, ctx.tab, heads, want=tuple(ctx.needs_input_grad[:3]))
+        out = [None if g is None else g.to(t.dtype) for g, t in zip(grads, (q, k, v))]
+        return (*out, None, None, None)
+
+
+def _forward(q, k, v, tab, heads, dtype):
+    f = [_fp32_rows(t, n, heads) for t, n in ((q, "q"), (k, "k"), (v, "v"))]
+    return attention_forward(*f, tab, heads) if dtype is None else attention_forward16(*f, tab, heads, int(dtype))
+
+
+def attention(q, k, v, views, heads, dtype=None):
+    """O ``[Rq, heads * 64]`` fp32 from q ``[Rq, heads * 64]`` and k, v ``[Rk, heads * 64]`` (fp32 GPU tensors, possibly column slices of one packed tensor:
+    the last dimension contiguous, the row stride is passed through) and ``views`` (int32 CPU tensor or list ``[n][6]``); differentiable at q, k and v.
+    ``dtype``: ``None`` for the fp32 forward, ``_lib.F16`` / ``_lib.BF16`` for the native inference forward on cast operands."""
+    heads = int(heads)
+    if heads <= 0:
+        raise ValueError("attention: heads must be positive")
+    for t, what in ((q, "q"), (k, "k"), (v, "v")):
+        _dev(t, what)
+        if t.ndim != 2 or t.shape[1] != heads * HEAD:
+            raise ValueError(f"attention: {what} of shape {tuple(t.shape)}, expected [rows, {heads * HEAD}]")
+    if k.shape[0] != v.shape[0]:
+        raise ValueError("attention: k and v differ in their row counts")
+    if dtype is not None and int(dtype) not in (_lib.F16, _lib.BF16):
+        raise ValueError("attention: dtype must be None, _lib.F16 or _lib.BF16")
+    tab = _table(views)
+    _check_table(tab, int(q.shape[0]), int(k.shape[0]))
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        n_groups(tab)   # a table the backward would refuse is refused here, before the forward runs
+        return _Attention.apply(q, k, v, tab, heads, dtype)
+    return _forward(q, k, v, tab, heads, dtype)
