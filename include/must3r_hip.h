@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MUST3R_HIP_ABI_VERSION 20
+#define MUST3R_HIP_ABI_VERSION 21
 
 typedef struct must3r_hip_ctx must3r_hip_ctx;
 
@@ -739,6 +739,86 @@ size_t must3r_hip_attn_train_scratch_bytes(int n_views, int total_q_rows, int to
 int must3r_hip_attn_train_groups(const int32_t* views_host, int n_views);
 int must3r_hip_attn_forward_f32(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream);
 int must3r_hip_attn_grad(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ABI 21.  Training forward and backward of the two residual sublayers of the reference's Block (blocks/layers.py:36-54; also two of the three sublayers of
+ * CachedDecoderBlock), fp32, stateless, no atomics: repeated calls agree bit for bit and a row of a row-wise output does not depend on the other rows of the call.
+ *   MLP sublayer        y^ = LN(x) gamma + beta;  z = y^ W1^T + b1;  h = gelu(z);  out = x + h W2^T + b2                        W1 [hidden][D], W2 [D][hidden]
+ *   attention sublayer  y^ = LN(x) gamma + beta;  qkv = y^ Wqkv^T + bqkv  [M][3 D] = q | k | v;  q, k rotated by RoPE2D;
+ *                       o = softmax(q k^T / 8) v per head of 64 and view (ABI 20);  out = x + o Wproj^T + bproj                 Wqkv [3 D][D], Wproj [D][D]
+ *   gelu(z) = z Phi(z),  gelu'(z) = Phi(z) + z phi(z),  Phi(z) = erfc(-z / sqrt 2) / 2 (the negative tail is a product, not a cancellation),
+ *   phi(z) = exp(-z^2 / 2) / sqrt(2 pi); both finite for every finite z, gelu' exactly 1 / 0 for z >= 40 / z <= -40.
+ *   RoPE2D (croco), per head of 64: columns [0, 32) rotate with pos[r][0], [32, 64) with pos[r][1]; the pairs are (i, i + 16), i < 16, with the angle
+ *   pos * f0 * freq^(-i / 16): a' = a cos - b sin, b' = b cos + a sin.  direction -1 is the transposed rotation (sin -> -sin), which is the backward.
+ * The operator forms (row-major fp32, leading dimensions in elements):
+ *   op_linear_f32      out[M][N] (ldc) = A[M][K] (lda) W[N][K]^T + bias[N] (bias may be NULL) on v_mfma_f32_16x16x4_f32, 128 x 128 x 16 tiles; epi:
+ *                        MUST3R_LIN_BIAS; MUST3R_LIN_BIAS_RES: out = res (ldres; may alias out) + that; MUST3R_LIN_BIAS_GELU: out = gelu(z), and zout (ldz) = z
+ *                        where zout is given.  Refused: K % 16, N % 4, a leading dimension % 4 or shorter than its row, pointers not 16-byte aligned.
+ *   op_layernorm_f32   y[M][D] = (x - mu) rstd gamma + beta, D % 64 == 0, D <= 1024, 16-byte aligned pointers; two-pass statistics of its own (the backward's
+ *                        recomputed statistics use the same formulas in another summation order)
+ *   op_gelu_f32        g[n] = gelu(z[n]), dg[n] = gelu'(z[n]); either output may be NULL
+ *   op_gelu_grad_f32   dz[M][N] (lddz) = dh (ldh) gelu'(z (ldz)); N and the leading dimensions % 4, 16-byte aligned; dz may alias dh
+ *   op_rope_f32        rotates the first rope_cols (a multiple of 64) columns of t[R][ld] in place; pos int64 [R][2] and rope_tab, the table of
+ *                        must3r_hip_rope_table ([rope_npos][16][2]), are DEVICE pointers.  The caller guarantees 0 <= pos < rope_npos (the kernel clamps, it
+ *                        never reads outside the table).  direction +1 / -1.
+ *   op_layernorm_grad_add   must3r_hip_op_layernorm_grad with dx = add + (the LayerNorm backward); add [M][D] may be NULL (then it is that entry point) and
+ *                        may alias dx.  A template flag of the same kernel: the entry points without add keep their bits.
+ * The sublayer entry points.  The forward saves nothing; *_grad recomputes the sublayer's forward into scratch and differentiates it.  Every gradient output may be
+ * NULL, costs nothing then and is not written: no dW and db of a Linear, no weight-gradient launch (db of the last Linear alone: its column sums of dy and no forward); no dx, dgamma and dbeta, no data gradient of the first Linear
+ * and no LayerNorm backward; no dgamma and dbeta, no column sums.  dx = dy + (the gradient through the branch).
+ *   mlp_sublayer_grad   y^, (z -> S1, h -> S2), [dW2, db2 = wgrad(dy, h)], dh = dgrad(dy, W2) -> S2, dz = dh gelu'(z) in place, [dW1, db1 = wgrad(dz, y^)],
+ *                       dy^ = dgrad(dz, W1) over y^, layernorm_grad_add(x, dy^, add = dy).
+ *   attn_sublayer_grad  y^, qkv (rotated), o = attn_forward_f32, [dWproj, dbproj = wgrad(dy, o)], do = dgrad(dy, Wproj), dqkv = attn_grad (q, k, v and dQ, dK, dV
+ *                       the column blocks of the packed tensors), the transposed rotation of dq | dk, [dWqkv, dbqkv = wgrad(dqkv, y^)], dy^ = dgrad(dqkv, Wqkv)
+ *                       over y^, layernorm_grad_add(x, dy^, add = dy).
+ * Shapes: D % 64 == 0, D <= 1024 (the LayerNorm backward's limit), heads = D / 64, hidden % 16 == 0.  views: the HOST table of ABI 20, int32 [n_views][6], inside
+ * the M rows (queries and keys are rows of the same tensor); ragged tables are fine, a row of no view attends nothing (o = 0, so out = x + bproj), overlapping key
+ * groups are refused by attn_sublayer_grad as by must3r_hip_attn_grad.
+ * Scratch, each part rounded up to 256 bytes, in this order (no device needed; 0 on a bad shape; rows are not chunked):
+ *   mlp_sublayer_scratch_bytes(M, D, hidden)  = 4 M D + 2 * 4 M hidden + max(op_linear_wgrad_scratch_bytes(M, D, hidden), (M, hidden, D))
+ *                                               + op_layernorm_grad_scratch_bytes(M, D)                       [y^ | S1 | S2 | partials | LayerNorm]
+ *   attn_sublayer_scratch_bytes(M, D, n_views) = 4 M D + 12 M D + 4 M D + 4 M D + 12 M D + max(op_linear_wgrad_scratch_bytes(M, 3 D, D), (M, D, D))
+ *                                               + op_layernorm_grad_scratch_bytes(M, D) + attn_train_scratch_bytes(n_views, M, M, D / 64)
+ *                                                                                  [y^ | qkv | o | do | dqkv | partials | LayerNorm | attention core]
+ * The forward entry points take the same scratch (they use its first parts).
+ * Refused with an error: null required pointers, M <= 0, D not a multiple of 64 or above 1024, hidden not a multiple of 16, pointers not 16-byte aligned, a table
+ * with negative entries or reaching past M, overlapping key groups (grad), rope_npos <= 0, scratch NULL, misaligned or too small. */
+#define MUST3R_LIN_BIAS 0
+#define MUST3R_LIN_BIAS_RES 1
+#define MUST3R_LIN_BIAS_GELU 2
+typedef struct must3r_hip_mlp_sublayer_args {
+    const float* x; const float* gamma; const float* beta; const float* W1; const float* b1; const float* W2; const float* b2;
+    const float* dy;                   /* *_grad only */
+    int32_t M, D, hidden;
+    float eps;
+    float* out;                        /* *_forward only */
+    float* dx; float* dgamma; float* dbeta; float* dW1; float* db1; float* dW2; float* db2;   /* *_grad, each optional */
+} must3r_hip_mlp_sublayer_args;
+typedef struct must3r_hip_attn_sublayer_args {
+    const float* x; const float* gamma; const float* beta; const float* Wqkv; const float* bqkv; const float* Wproj; const float* bproj;
+    const float* dy;                   /* *_grad only */
+    const int64_t* pos;                /* DEVICE int64 [M][2] */
+    const float* rope_tab;             /* DEVICE fp32 [rope_npos][16][2] */
+    const int32_t* views;              /* HOST int32 [n_views][6] */
+    int32_t M, D, n_views, rope_npos;
+    float eps;
+    int32_t reserved;
+    float* out;                        /* *_forward only */
+    float* dx; float* dgamma; float* dbeta; float* dWqkv; float* dbqkv; float* dWproj; float* dbproj;   /* *_grad, each optional */
+} must3r_hip_attn_sublayer_args;
+int must3r_hip_op_linear_f32(int epi, const float* A, int lda, const float* W, const float* bias, const float* res, int ldres, float* out, int ldc, float* zout,
+                             int ldz, int M, int N, int K, void* stream);
+int must3r_hip_op_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int M, int D, float eps, void* stream);
+int must3r_hip_op_gelu_f32(const float* z, float* g, float* dg, long long n, void* stream);
+int must3r_hip_op_gelu_grad_f32(const float* dh, int ldh, const float* z, int ldz, float* dz, int lddz, int M, int N, void* stream);
+int must3r_hip_op_rope_f32(float* t, int ld, const int64_t* pos, const float* rope_tab, int rope_npos, int R, int rope_cols, int direction, void* stream);
+int must3r_hip_op_layernorm_grad_add(const float* x, const float* gamma, const float* dy, const float* add, float* dx, float* dgamma, float* dbeta, int M, int D,
+                                     float eps, void* scratch, size_t scratch_bytes, void* stream);
+size_t must3r_hip_mlp_sublayer_scratch_bytes(int M, int D, int hidden);
+int must3r_hip_mlp_sublayer_forward(const must3r_hip_mlp_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream);
+int must3r_hip_mlp_sublayer_grad(const must3r_hip_mlp_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream);
+size_t must3r_hip_attn_sublayer_scratch_bytes(int M, int D, int n_views);
+int must3r_hip_attn_sublayer_forward(const must3r_hip_attn_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream);
+int must3r_hip_attn_sublayer_grad(const must3r_hip_attn_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream);
 
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);

@@ -15,13 +15,14 @@ ATTN_FP8 = 0x100   # OR-able: fp8 (e4m3) attention operands, include/must3r_hip.
 MEM_KV, MEM_NORM_Y, MEM_RAW = 0, 1, 2
 PART_ENCODER, PART_DECODER = 1, 2
 EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = range(6)
-ABI_VERSION = 20
+ABI_VERSION = 21
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
 LOSS_W_SCALAR, LOSS_W_MEAN, LOSS_W_CONF, LOSS_W_PIXEL = range(4)
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
+LIN_BIAS, LIN_BIAS_RES, LIN_BIAS_GELU = range(3)
 
 class Config(C.Structure):
     _fields_ = [("img_size", C.c_int32), ("patch_size", C.c_int32),
@@ -143,6 +144,24 @@ class AttnTrainArgs(C.Structure):
                 ("ldo", C.c_int32), ("lddq", C.c_int32), ("lddk", C.c_int32), ("lddv", C.c_int32)]
 
 
+class MlpSublayerArgs(C.Structure):
+    """must3r_hip_mlp_sublayer_args: inputs and (optional) outputs of the MLP sublayer's training forward / backward (include/must3r_hip.h, ABI 21)."""
+    _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
+                ("dy", C.c_void_p), ("M", C.c_int32), ("D", C.c_int32), ("hidden", C.c_int32), ("eps", C.c_float), ("out", C.c_void_p),
+                ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dW1", C.c_void_p), ("db1", C.c_void_p), ("dW2", C.c_void_p),
+                ("db2", C.c_void_p)]
+
+
+class AttnSublayerArgs(C.Structure):
+    """must3r_hip_attn_sublayer_args: inputs, device positions and RoPE table, HOST view table and (optional) outputs of the attention sublayer's training
+    forward / backward (include/must3r_hip.h, ABI 21)."""
+    _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("Wqkv", C.c_void_p), ("bqkv", C.c_void_p), ("Wproj", C.c_void_p),
+                ("bproj", C.c_void_p), ("dy", C.c_void_p), ("pos", C.c_void_p), ("rope_tab", C.c_void_p), ("views", C.c_void_p),
+                ("M", C.c_int32), ("D", C.c_int32), ("n_views", C.c_int32), ("rope_npos", C.c_int32), ("eps", C.c_float), ("reserved", C.c_int32),
+                ("out", C.c_void_p), ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dWqkv", C.c_void_p), ("dbqkv", C.c_void_p),
+                ("dWproj", C.c_void_p), ("dbproj", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -229,6 +248,18 @@ PROTOTYPES = {
     "must3r_hip_attn_train_groups": (i32, [vp, i32]),
     "must3r_hip_attn_forward_f32": (i32, [P(AttnTrainArgs), vp, sz, vp]),
     "must3r_hip_attn_grad": (i32, [P(AttnTrainArgs), vp, sz, vp]),
+    "must3r_hip_op_linear_f32": (i32, [i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "must3r_hip_op_layernorm_f32": (i32, [vp, vp, vp, vp, i32, i32, fp, vp]),
+    "must3r_hip_op_gelu_f32": (i32, [vp, vp, vp, C.c_longlong, vp]),
+    "must3r_hip_op_gelu_grad_f32": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp]),
+    "must3r_hip_op_rope_f32": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp]),
+    "must3r_hip_op_layernorm_grad_add": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, fp, vp, sz, vp]),
+    "must3r_hip_mlp_sublayer_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_mlp_sublayer_forward": (i32, [P(MlpSublayerArgs), vp, sz, vp]),
+    "must3r_hip_mlp_sublayer_grad": (i32, [P(MlpSublayerArgs), vp, sz, vp]),
+    "must3r_hip_attn_sublayer_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_attn_sublayer_forward": (i32, [P(AttnSublayerArgs), vp, sz, vp]),
+    "must3r_hip_attn_sublayer_grad": (i32, [P(AttnSublayerArgs), vp, sz, vp]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -16,6 +16,7 @@
 //                         un-permuted row, db[o] = sum_s of the column-sum partials.
 //   ln_grad_kernel        per row: g^ = dY gamma, dx = rstd (g^ - mean(g^) - x^ mean(g^ x^)), in place over dY; row-walking waves keep
 //                         per-lane column sums of dY x^ and dY, one partial per block.
+//                         <ADD> (ABI 21): dx = add + that, the residual of a pre-norm sublayer (train_block.hip); <false> is the kernel as it was.
 //   ln_grad_reduce_kernel sums the block partials in a fixed two-level order (16 interleaved slices, then the slices): dgamma, dbeta.
 // The split count of the weight gradient and the block count of the LayerNorm backward are functions of the row count alone.  No atomics:
 // every output element has one writer and a fixed order of operations.
@@ -283,8 +284,12 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restri
 }
 
 // dx may alias dy (each element is read before it is written, by the lane that writes it).  part [blocks][2][D]: column sums of dy x^ and dy.
+// ADD: dx = add + (the LayerNorm backward), the residual branch of a pre-norm sublayer; add may alias dx for the same reason.  The instantiation
+// without it is the kernel as it was.
+template <bool ADD>
 __global__ void __launch_bounds__(256) ln_grad_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float2* __restrict__ stats,
-                                                      const float* dy, float* dx, int M, int D, int rows_per_block, float* __restrict__ part) {
+                                                      const float* dy, const float* add, float* dx, int M, int D, int rows_per_block,
+                                                      float* __restrict__ part) {
     __shared__ float red[3 * 2 * 64 * LNG_MAX_T];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, T = D / 64;
     const int r_lo = blockIdx.x * rows_per_block, r_hi = min(M, r_lo + rows_per_block);
@@ -314,7 +319,11 @@ __global__ void __launch_bounds__(256) ln_grad_kernel(const float* __restrict__ 
         if (dx) {
 #pragma unroll
             for (int t = 0; t < LNG_MAX_T; ++t)
-                if (t < T) dx[o + t * 64 + lane] = st.y * (gh[t] - m1 - xh[t] * m2);
+                if (t < T) {
+                    const float v = st.y * (gh[t] - m1 - xh[t] * m2);
+                    if constexpr (ADD) dx[o + t * 64 + lane] = add[o + t * 64 + lane] + v;
+                    else dx[o + t * 64 + lane] = v;
+                }
         }
     }
     if (!part) return;
@@ -423,11 +432,12 @@ static int run_stats(const float* x, int M, int D, float eps, float2* stats, hip
 }
 
 // part: lng_blocks(M) x 2 x D floats, or NULL when neither dgamma nor dbeta is asked for
-static int run_ln_grad(const float* x, const float* gamma, const float2* stats, const float* dy, float* dx, float* dgamma, float* dbeta, int M, int D,
-                       float* part, hipStream_t s) {
+static int run_ln_grad(const float* x, const float* gamma, const float2* stats, const float* dy, const float* add, float* dx, float* dgamma, float* dbeta,
+                       int M, int D, float* part, hipStream_t s) {
     const int NB = lng_blocks(M), rpb = lng_rows_per_block(M);
     const bool cols = dgamma || dbeta;
-    hipLaunchKernelGGL(ln_grad_kernel, dim3(NB), dim3(256), 0, s, x, gamma, stats, dy, dx, M, D, rpb, cols ? part : nullptr);
+    if (add && dx) hipLaunchKernelGGL(ln_grad_kernel<true>, dim3(NB), dim3(256), 0, s, x, gamma, stats, dy, add, dx, M, D, rpb, cols ? part : nullptr);
+    else hipLaunchKernelGGL(ln_grad_kernel<false>, dim3(NB), dim3(256), 0, s, x, gamma, stats, dy, nullptr, dx, M, D, rpb, cols ? part : nullptr);
     if (cols) hipLaunchKernelGGL(ln_grad_reduce_kernel, dim3(D / 16), dim3(256), 0, s, part, NB, D, dgamma, dbeta);
     if (hipGetLastError() != hipSuccess) return fail("layernorm_grad: launch failed");
     return 0;
@@ -530,7 +540,7 @@ extern "C" int must3r_hip_head_grad(const must3r_hip_head_grad_args* a, void* sc
         if (!a->dx) return fail("head_grad: dgamma / dbeta without dx is not provided for (dY lives in the dx buffer)");
         hipLaunchKernelGGL(perm_w_kernel, dim3(O), dim3(256), 0, s, a->W, D, Wp);
         M3R_RUN(run_dgrad(true, z, Wp, a->dx, R, O, D, s));
-        M3R_RUN(run_ln_grad(a->x, a->gamma, stats, a->dx, a->dx, a->dgamma, a->dbeta, R, D, lpart, s));
+        M3R_RUN(run_ln_grad(a->x, a->gamma, stats, a->dx, nullptr, a->dx, a->dgamma, a->dbeta, R, D, lpart, s));
     }
     return 0;
 }
@@ -567,15 +577,25 @@ extern "C" size_t must3r_hip_op_layernorm_grad_scratch_bytes(int M, int D) {
     return lng_scratch(M, D);
 }
 
-extern "C" int must3r_hip_op_layernorm_grad(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int M, int D,
-                                            float eps, void* scratch, size_t scratch_bytes, void* stream) {
-    if (M <= 0 || D <= 0 || D % 64 || D > 64 * LNG_MAX_T) return fail("op_layernorm_grad: M must be positive, D a multiple of 64 and at most 1024");
-    if (!x || !gamma || !dy) return fail("op_layernorm_grad: null argument");
+static int op_layernorm_grad(const char* who, const float* x, const float* gamma, const float* dy, const float* add, float* dx, float* dgamma, float* dbeta,
+                             int M, int D, float eps, void* scratch, size_t scratch_bytes, void* stream) {
+    if (M <= 0 || D <= 0 || D % 64 || D > 64 * LNG_MAX_T) return fail("%s: M must be positive, D a multiple of 64 and at most 1024", who);
+    if (!x || !gamma || !dy) return fail("%s: null argument", who);
     if (!dx && !dgamma && !dbeta) return 0;
-    if (!scratch || misaligned(scratch) || scratch_bytes < lng_scratch(M, D)) return fail("op_layernorm_grad: scratch too small");
+    if (!scratch || misaligned(scratch) || scratch_bytes < lng_scratch(M, D)) return fail("%s: scratch too small", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float2* stats = reinterpret_cast<float2*>(scratch);
     float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + up256((size_t)M * 8));
     M3R_RUN(run_stats(x, M, D, eps, stats, s));
-    return run_ln_grad(x, gamma, stats, dy, dx, dgamma, dbeta, M, D, part, s);
+    return run_ln_grad(x, gamma, stats, dy, add, dx, dgamma, dbeta, M, D, part, s);
+}
+
+extern "C" int must3r_hip_op_layernorm_grad(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int M, int D,
+                                            float eps, void* scratch, size_t scratch_bytes, void* stream) {
+    return op_layernorm_grad("op_layernorm_grad", x, gamma, dy, nullptr, dx, dgamma, dbeta, M, D, eps, scratch, scratch_bytes, stream);
+}
+
+extern "C" int must3r_hip_op_layernorm_grad_add(const float* x, const float* gamma, const float* dy, const float* add, float* dx, float* dgamma,
+                                                float* dbeta, int M, int D, float eps, void* scratch, size_t scratch_bytes, void* stream) {
+    return op_layernorm_grad("op_layernorm_grad_add", x, gamma, dy, add, dx, dgamma, dbeta, M, D, eps, scratch, scratch_bytes, stream);
 }
