@@ -16,6 +16,16 @@
  *     seen.  A context is bound to one device and is not re-entrant (one forward in flight per context),
  *     like the reference (slam/slam.py:533 runs forwards from a single worker thread).
  *   - "16-bit" buffers hold bf16 or fp16 elements according to the `dtype` argument.
+ *   - stream order: every entry point that takes a `stream` enqueues ALL of its work on it -- kernels, memsets, and the copies of the tables it builds on
+ *     the host -- and returns without waiting for it; nothing goes to the null stream or to a stream of the library's own, so the caller's stream order is the
+ *     only ordering between calls (tests/test_stream_order_gpu.py holds every such entry point to this on a delayed side stream).  The one entry point that
+ *     synchronises the host with `stream` is must3r_hip_export_count (it returns totals).  Beyond that a call may wait on the host only for staging of its own:
+ *     host-built tables travel through rings of pinned slots (per calling thread: 4 for must3r_hip_resample, 4 for must3r_hip_attn_forward_f32 /
+ *     must3r_hip_attn_grad and the attention sublayer entry points built on them; per context: 32 for the view tables of must3r_hip_encode / must3r_hip_decode),
+ *     and a call that finds its next slot still in flight waits for THAT copy, not for the stream; the growth of a context's workspace to a larger shape
+ *     synchronises once.
+ *     A context, and a calling thread's staging, serve one stream at a time: the device slots of the forwards' view tables are ordered by stream order only, so
+ *     two streams must not share a context (or interleave calls of one thread) without ordering the streams themselves.
  */
 #ifndef MUST3R_HIP_H
 #define MUST3R_HIP_H

@@ -448,17 +448,22 @@ static const char* ta_plan(const int32_t* views, int n, bool want_groups, TaPlan
 static size_t ta_tables_bytes(int n) { return ta_up256((size_t)n * 24) + ta_up256((size_t)n * 16) + ta_up256((size_t)n * 4); }
 static size_t ta_scratch(int n, long long q_rows, int heads) { return ta_tables_bytes(n) + 2 * ta_up256((size_t)q_rows * heads * 4); }
 
-// The tables travel through one pinned buffer per calling thread; the event says when the previous call's copy has left it.
+// The tables travel through a ring of pinned buffers per calling thread (as resample's, image.hip); a slot's event says when the copy out of it has left it, and
+// the slot is reused only then.  With ONE buffer the second upload of a call waited for the first, which is queued behind everything the stream still has to do:
+// attn_sublayer_grad uploads twice (forward recompute, backward), so every such call drained the caller's stream on the host (tests/test_stream_order_gpu.py).
 struct TaPin {
     void* host = nullptr;
     size_t cap = 0;
     hipEvent_t ev = nullptr;
 };
-static thread_local TaPin ta_pin;
+constexpr int kTaPinSlots = 4;
+static thread_local TaPin ta_pins[kTaPinSlots];
+static thread_local int ta_pin_next = 0;
 
 static int ta_upload(const TaPlan& P, const int32_t* views, int n, bool want_groups, char* scratch, hipStream_t s, const char* who) {
     const size_t bytes = ta_tables_bytes(n);
-    TaPin& pin = ta_pin;
+    TaPin& pin = ta_pins[ta_pin_next];
+    ta_pin_next = (ta_pin_next + 1) % kTaPinSlots;
     if (pin.ev) {
         if (hipEventSynchronize(pin.ev) != hipSuccess) return fail("%s: waiting for the previous table upload failed", who);
         hipEventDestroy(pin.ev);
