@@ -18,10 +18,12 @@
  *   - "16-bit" buffers hold bf16 or fp16 elements according to the `dtype` argument.
  *   - stream order: every entry point that takes a `stream` enqueues ALL of its work on it -- kernels, memsets, and the copies of the tables it builds on
  *     the host -- and returns without waiting for it; nothing goes to the null stream or to a stream of the library's own, so the caller's stream order is the
- *     only ordering between calls (tests/test_stream_order_gpu.py holds every such entry point to this on a delayed side stream).  The one entry point that
+ *     only ordering between calls (tests/test_stream_order_gpu.py holds every such entry point to this on a delayed side stream).  The entry points of
+ *     must3r_hip_cross_sublayer_args take their stream as the descriptor's `stream` field instead of a trailing argument and are held to the same guarantee
+ *     (tests/test_cross_grad_gpu.py).  The one entry point that
  *     synchronises the host with `stream` is must3r_hip_export_count (it returns totals).  Beyond that a call may wait on the host only for staging of its own:
  *     host-built tables travel through rings of pinned slots (per calling thread: 4 for must3r_hip_resample, 4 for must3r_hip_attn_forward_f32 /
- *     must3r_hip_attn_grad and the attention sublayer entry points built on them; per context: 32 for the view tables of must3r_hip_encode / must3r_hip_decode),
+ *     must3r_hip_attn_grad and the attention and cross-attention sublayer entry points built on them; per context: 32 for the view tables of must3r_hip_encode / must3r_hip_decode),
  *     and a call that finds its next slot still in flight waits for THAT copy, not for the stream; the growth of a context's workspace to a larger shape
  *     synchronises once.
  *     A context, and a calling thread's staging, serve one stream at a time: the device slots of the forwards' view tables are ordered by stream order only, so
@@ -829,6 +831,57 @@ int must3r_hip_mlp_sublayer_grad(const must3r_hip_mlp_sublayer_args* a, void* sc
 size_t must3r_hip_attn_sublayer_scratch_bytes(int M, int D, int n_views);
 int must3r_hip_attn_sublayer_forward(const must3r_hip_attn_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream);
 int must3r_hip_attn_sublayer_grad(const must3r_hip_attn_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ABI 21, additive.  Training forward and backward of the third residual sublayer of the reference's CachedDecoderBlock (blocks/layers.py:90-99,
+ * CachedCrossAttention blocks/attention.py:129-149): the cross attention of the tokens x over the token memory.  fp32, stateless, composed like
+ * must3r_hip_attn_sublayer_* from the operator forms above; no atomics.
+ *   y^ = LN(x) gamma + beta                               x [M][D]
+ *   q  = y^ Wq^T + bq                                     no RoPE: the reference builds cross_attn with pos_embed=None
+ *   k | v = mem Wk^T + bk | mem Wv^T + bv                 mem [Rm][ldmem], projected ONCE per memory row into one packed [Rm][2 D] tensor
+ *   o  = softmax(q k^T / 8) v per head of 64 and view     ABI 20; views = HOST int32 [n_views][6]: the q rows index x, the kv rows index mem
+ *   out = x + o Wproj^T + bproj
+ * Wk == NULL (then bk, Wv, bv and their gradients are NULL too) is the reference's `kv` memory mode: mem is [Rm][ldmem >= 2 D] and already holds k | v, nothing
+ * is projected.  Otherwise ldmem >= D.  Leading dimensions are multiples of 4; D % 64 == 0, D <= 1024, heads = D / 64; pointers 16-byte aligned; biases may be NULL.
+ * The stream travels in the descriptor (`stream`, a hipStream_t): all work goes to it, the uploaded view tables included, and no call waits for it on the host.
+ * The forward saves nothing; cross_sublayer_grad recomputes the forward into scratch and differentiates it:
+ *   y^, q, k | v, [o = attn_forward_f32, dWproj, dbproj = wgrad(dy, o)], do = dgrad(dy, Wproj), (dq, dk | dv) = attn_grad, [dWk, dbk = wgrad(dk, mem)],
+ *   [dWv, dbv = wgrad(dv, mem)], [dmem = dk Wk + dv Wv: ONE launch of the data-gradient kernel whose weight operand is the two row blocks Wk, Wv -- one k-ordered
+ *   accumulator chain per element, the bits of must3r_hip_op_linear_dgrad_f32 on a packed [2 D][D] copy of Wk over Wv, no such copy and no read-modify-write of
+ *   dmem], [dWq, dbq = wgrad(dq, y^)], dy^ = dgrad(dq, Wq) over y^, layernorm_grad_add(x, dy^, add = dy).
+ * In the `kv` mode dmem = dK | dV is written by the attention backward straight into the caller's buffer (lddk = lddv = lddmem).
+ * Every gradient output may be NULL, costs nothing then and is not written: none of dmem, dWk, dbk, dWv, dbv, no dK / dV launch; none of dx, dgamma, dbeta, dWq, dbq,
+ * no dQ launch, no data gradient through Wq and no LayerNorm backward; no dW and db of a Linear, no weight-gradient launch for it; dbproj alone, the column sums of
+ * dy and no recomputed forward.  dx = dy + (the gradient through the branch).
+ * Coverage: a row of x that belongs to no view has o = 0 (out = x + bproj, dx = dy).  Memory rows outside every key group's span take exact zeros in the packed
+ * dK | dV (zeroed on the caller's stream when the spans do not cover [0, Rm)), so that dmem is written completely and dWk, dWv never see unwritten scratch.
+ * Determinism: repeated calls agree bit for bit; a view's rows of out / dx and a scene's rows of dmem are the same bits alone and in a batch.  Overlapping key groups
+ * are refused by cross_sublayer_grad as by must3r_hip_attn_grad.
+ * Scratch (no device needed; 0 on a bad shape; rows are not chunked), each part rounded up to 256 bytes, in this order:
+ *   cross_sublayer_scratch_bytes(M, Rm, D, n_views, kv_ready) = 4 M D + 4 M D + [8 Rm D] + 4 M D + 4 M D + 4 M D + [8 Rm D]
+ *         + max(op_linear_wgrad_scratch_bytes(M, D, D), [op_linear_wgrad_scratch_bytes(Rm, D, D)]) + op_layernorm_grad_scratch_bytes(M, D)
+ *         + attn_train_scratch_bytes(n_views, M, Rm, D / 64)
+ *                                                [y^ | q | k|v | o | do | dq | dk|dv | weight-gradient partials | LayerNorm | attention core]
+ *   the parts in brackets are absent with kv_ready != 0 (the `kv` mode).  The forward takes the same scratch.
+ * Refused with an error before anything is read or launched: null required pointers (x, mem, gamma, beta, Wq, Wproj, views; out / dy), M or Rm <= 0, D not a
+ * multiple of 64 or above 1024, ldmem / lddmem short or not a multiple of 4, pointers not 16-byte aligned, a table with negative entries or reaching past the M query
+ * rows or the Rm key rows, skip_lo > skip_hi or skip_hi > nk, Wk without Wv or the reverse (and bk, bv or their gradients without Wk), overlapping key groups (grad),
+ * scratch NULL, misaligned or too small. */
+typedef struct must3r_hip_cross_sublayer_args {
+    const float* x; const float* mem; const float* gamma; const float* beta;
+    const float* Wq; const float* bq; const float* Wk; const float* bk; const float* Wv; const float* bv; const float* Wproj; const float* bproj;
+    const float* dy;                   /* *_grad only */
+    const int32_t* views;              /* HOST int32 [n_views][6] */
+    float* out;                        /* *_forward only */
+    float* dx; float* dmem; float* dgamma; float* dbeta; float* dWq; float* dbq; float* dWk; float* dbk; float* dWv; float* dbv; float* dWproj;
+    float* dbproj;                     /* *_grad, each optional; dmem [Rm][lddmem] */
+    int32_t M, Rm, D, n_views, ldmem, lddmem;
+    float eps;
+    int32_t reserved;
+    void* stream;                      /* hipStream_t */
+} must3r_hip_cross_sublayer_args;
+size_t must3r_hip_cross_sublayer_scratch_bytes(int M, int Rm, int D, int n_views, int kv_ready);
+int must3r_hip_cross_sublayer_forward(const must3r_hip_cross_sublayer_args* a, void* scratch, size_t scratch_bytes);
+int must3r_hip_cross_sublayer_grad(const must3r_hip_cross_sublayer_args* a, void* scratch, size_t scratch_bytes);
 
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);

@@ -162,6 +162,18 @@ class AttnSublayerArgs(C.Structure):
                 ("dWproj", C.c_void_p), ("dbproj", C.c_void_p)]
 
 
+class CrossSublayerArgs(C.Structure):
+    """must3r_hip_cross_sublayer_args: inputs, HOST view table, (optional) outputs and the stream of the cross-attention sublayer's training forward /
+    backward (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("x", C.c_void_p), ("mem", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("Wq", C.c_void_p), ("bq", C.c_void_p),
+                ("Wk", C.c_void_p), ("bk", C.c_void_p), ("Wv", C.c_void_p), ("bv", C.c_void_p), ("Wproj", C.c_void_p), ("bproj", C.c_void_p),
+                ("dy", C.c_void_p), ("views", C.c_void_p), ("out", C.c_void_p),
+                ("dx", C.c_void_p), ("dmem", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dWq", C.c_void_p), ("dbq", C.c_void_p),
+                ("dWk", C.c_void_p), ("dbk", C.c_void_p), ("dWv", C.c_void_p), ("dbv", C.c_void_p), ("dWproj", C.c_void_p), ("dbproj", C.c_void_p),
+                ("M", C.c_int32), ("Rm", C.c_int32), ("D", C.c_int32), ("n_views", C.c_int32), ("ldmem", C.c_int32), ("lddmem", C.c_int32),
+                ("eps", C.c_float), ("reserved", C.c_int32), ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -260,6 +272,9 @@ PROTOTYPES = {
     "must3r_hip_attn_sublayer_scratch_bytes": (sz, [i32, i32, i32]),
     "must3r_hip_attn_sublayer_forward": (i32, [P(AttnSublayerArgs), vp, sz, vp]),
     "must3r_hip_attn_sublayer_grad": (i32, [P(AttnSublayerArgs), vp, sz, vp]),
+    "must3r_hip_cross_sublayer_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "must3r_hip_cross_sublayer_forward": (i32, [P(CrossSublayerArgs), vp, sz]),
+    "must3r_hip_cross_sublayer_grad": (i32, [P(CrossSublayerArgs), vp, sz]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

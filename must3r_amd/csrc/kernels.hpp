@@ -228,6 +228,11 @@ int head_layernorm(must3r_hip_ctx* c, DType dt, const float* x, const float* gam
 int head_linear(must3r_hip_ctx* c, DType dt, const void* hcat, const void* wcat, const float* bias_ps, float* pointmaps, int rows, int D, int OUT, int ntok,
                 int gw, int H, int Wimg, int head_views, long long head_scene_skip, hipStream_t s);
 
+// the data gradient of a Linear whose weight rows live in two parameters (train_head.hip dgrad_kernel<false, true>):
+// out[M][K] (ldo) = dZ[M][O] (ldz) [W0 [O0][K] ; W1 [O - O0][K]], O0 % 16 == 0: one launch and one k-ordered accumulator chain per element, the bits of
+// must3r_hip_op_linear_dgrad_f32 on a packed copy of W0 over W1.  Used by must3r_hip_cross_sublayer_grad (dmem = dK Wk + dV Wv); fails with the ABI's error text.
+int launch_dgrad_seg_f32(const float* dZ, int ldz, const float* W0, const float* W1, int O0, float* out, int ldo, int M, int O, int K, hipStream_t s);
+
 // debug: mapping of ds_read_b64_tr_b16 (out: 256 shorts)
 int launch_tr_probe(short* out, hipStream_t s);
 

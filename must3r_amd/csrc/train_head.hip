@@ -9,6 +9,8 @@
 //                         consecutive floats of G (448-byte reads); dZ is never materialised.
 //   dgrad_kernel<GATHER>  dY[M, K] = dZ[M, O] W[O, K]: 128 x 128 tiles, 16-deep steps over O through LDS, 4 waves of 64 x 64.  dZ rows are
 //                         read along their fast dimension (LDS rows padded to 20 floats: conflict-free), W rows as they lie.
+//                         <., SEG> (ABI 21, additive): the rows of W live in two parameters (launch_dgrad_seg_f32, kernels.hpp: dmem = dK Wk + dV Wv
+//                         of train_cross.hip); the same steps and the same k-ordered chain, so the bits of the plain kernel on a packed copy.
 //   wgrad_kernel<GATHER>  P_s[O, K] = sum_{r in split s} dZ[r, o] x^[r, k]: both operands have the contraction as their slow dimension, the
 //                         LDS tiles [r][.] feed the MFMA lanes with consecutive addresses.  x^ = (x - mu) rstd is formed on load.  The
 //                         blocks of the first column tile also leave the column sums of their dZ rows (db partials).
@@ -103,9 +105,19 @@ __global__ void __launch_bounds__(256) split3_kernel(const float* __restrict__ y
     }
 }
 
+// the second row block of a two-segment W and the row stride of out (dgrad_kernel<., true>)
+struct DgSeg {
+    const float* W1;
+    int O0, ldo;
+};
+
 // out[M, K] = dZ[M, O] W[O, K];  O % 16 == 0, K % 4 == 0; tail rows and columns are zero-filled on load and not stored
-template <bool GATHER>
-__global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __restrict__ W, float* __restrict__ out, int M, int O, int K, int n_tiles) {
+// SEG: the rows of W live in two parameters, W [O0][K] and seg.W1 [O - O0][K] with O0 % 16 == 0 (a 16-deep step never straddles the seam), and out has
+// the row stride seg.ldo.  The steps and the k-ordered chain are the same: the bits of the plain kernel on a packed copy of W over W1.  The instantiations
+// without it are the kernel as it was.
+template <bool GATHER, bool SEG = false>
+__global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __restrict__ W, float* __restrict__ out, int M, int O, int K, int n_tiles,
+                                                    DgSeg seg = DgSeg{nullptr, 0, 0}) {
     __shared__ __attribute__((aligned(16))) float As[HM * HAP];
     __shared__ __attribute__((aligned(16))) float Bs[HK * HBP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
@@ -134,7 +146,11 @@ __global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __rest
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             ra[e] = aok[e] ? *reinterpret_cast<const f32x4*>(z.p + abase[e] + dz_col<GATHER>(z, k0 + ac[e])) : f32x4{0.f, 0.f, 0.f, 0.f};
-            rb[e] = bok[e] ? *reinterpret_cast<const f32x4*>(W + (size_t)(k0 + br[e]) * K + n0 + bc[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
+            const float* wrow = W + (size_t)(k0 + br[e]) * K;
+            if constexpr (SEG) {
+                if (k0 >= seg.O0) wrow = seg.W1 + (size_t)(k0 - seg.O0 + br[e]) * K;
+            }
+            rb[e] = bok[e] ? *reinterpret_cast<const f32x4*>(wrow + n0 + bc[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
     fetch(0);
@@ -170,7 +186,7 @@ __global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __rest
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int n = n0 + wn * 64 + j * 16 + fr;
-                if (n < K) out[(size_t)m * K + n] = acc[i][j][r];
+                if (n < K) out[(size_t)m * (SEG ? seg.ldo : K) + n] = acc[i][j][r];
             }
         }
 }
@@ -404,8 +420,8 @@ static int run_dgrad(bool gather, const DzSrc& z, const float* W, float* out, in
     const int n_tiles = (K + HN - 1) / HN;
     const long long blocks = (long long)((M + HM - 1) / HM) * n_tiles;
     if (blocks > 0x7fffffffLL) return fail("linear_dgrad: too many rows");
-    if (gather) hipLaunchKernelGGL(dgrad_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles);
-    else hipLaunchKernelGGL(dgrad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles);
+    if (gather) hipLaunchKernelGGL((dgrad_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
+    else hipLaunchKernelGGL((dgrad_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
     if (hipGetLastError() != hipSuccess) return fail("linear_dgrad: launch failed");
     return 0;
 }
@@ -482,6 +498,21 @@ static int head_forward(int dtype, const float* x, const float* y, const float* 
     }
     if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
     return head_linear(nullptr, dt, hcat, wcat, bias_ps, pointmaps, R, D, O, ntok, Wimg / 16, H, Wimg, 0, 0, s);
+}
+
+int launch_dgrad_seg_f32(const float* dZ, int ldz, const float* W0, const float* W1, int O0, float* out, int ldo, int M, int O, int K, hipStream_t s) {
+    if (M <= 0 || O <= 0 || K <= 0) return fail("linear_dgrad (two segments): bad shape");
+    if (!dZ || !W0 || !W1 || !out) return fail("linear_dgrad (two segments): null argument");
+    if (O % 16 || O0 % 16 || O0 <= 0 || O0 >= O) return fail("linear_dgrad (two segments): O and the seam must be multiples of 16, the seam inside (0, O)");
+    if (K % 4 || ldz < O || ldz % 4 || ldo < K) return fail("linear_dgrad (two segments): K and ldz must be multiples of 4, ldz >= O, ldo >= K");
+    if (misaligned(dZ) || misaligned(W0) || misaligned(W1)) return fail("linear_dgrad (two segments): dZ and the weights must be 16-byte aligned");
+    const int n_tiles = (K + HN - 1) / HN;
+    const long long blocks = (long long)((M + HM - 1) / HM) * n_tiles;
+    if (blocks > 0x7fffffffLL) return fail("linear_dgrad (two segments): too many rows");
+    const DzSrc z{dZ, ldz, 0, 0, 0, 0};
+    hipLaunchKernelGGL((dgrad_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, z, W0, out, M, O, K, n_tiles, DgSeg{W1, O0, ldo});
+    if (hipGetLastError() != hipSuccess) return fail("linear_dgrad (two segments): launch failed");
+    return 0;
 }
 
 }  // namespace m3r
