@@ -31,6 +31,7 @@
 #include "abi.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
+#include "train_common.hpp"
 
 namespace m3r {
 
@@ -374,9 +375,6 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------------
-static size_t ta_up256(size_t v) { return (v + 255) / 256 * 256; }
-static bool ta_misaligned(const void* p) { return ((size_t)p & 15) != 0; }
-
 // what the table says, found on the host: the key groups (views partitioned by kv_row0, in order of first appearance; inside a group the
 // views keep the order of the table), the row counts and the grid extents
 struct TaPlan {
@@ -445,8 +443,19 @@ static const char* ta_plan(const int32_t* views, int n, bool want_groups, TaPlan
 }
 
 // scratch: [views n x 6 int32 | groups n x 4 int32 | list n int32 | lse2 rows x heads fp32 | delta rows x heads fp32], each part a multiple of 256 bytes
-static size_t ta_tables_bytes(int n) { return ta_up256((size_t)n * 24) + ta_up256((size_t)n * 16) + ta_up256((size_t)n * 4); }
-static size_t ta_scratch(int n, long long q_rows, int heads) { return ta_tables_bytes(n) + 2 * ta_up256((size_t)q_rows * heads * 4); }
+struct TaLayout { size_t views, groups, list, tables_bytes, lse2, delta, total; };   // tables_bytes: the three tables, one upload
+static TaLayout ta_layout(int n, long long q_rows, int heads) {
+    TaLayout L{};
+    ScratchCursor c;
+    L.views = c.take((size_t)n * 24);
+    L.groups = c.take((size_t)n * 16);
+    L.list = c.take((size_t)n * 4);
+    L.tables_bytes = c.off;
+    L.lse2 = c.take((size_t)q_rows * heads * 4);
+    L.delta = c.take((size_t)q_rows * heads * 4);
+    L.total = c.off;
+    return L;
+}
 
 // The tables travel through a ring of pinned buffers per calling thread (as resample's, image.hip); a slot's event says when the copy out of it has left it, and
 // the slot is reused only then.  With ONE buffer the second upload of a call waited for the first, which is queued behind everything the stream still has to do:
@@ -461,7 +470,8 @@ static thread_local TaPin ta_pins[kTaPinSlots];
 static thread_local int ta_pin_next = 0;
 
 static int ta_upload(const TaPlan& P, const int32_t* views, int n, bool want_groups, char* scratch, hipStream_t s, const char* who) {
-    const size_t bytes = ta_tables_bytes(n);
+    const TaLayout L = ta_layout(n, 0, 0);
+    const size_t bytes = L.tables_bytes;
     TaPin& pin = ta_pins[ta_pin_next];
     ta_pin_next = (ta_pin_next + 1) % kTaPinSlots;
     if (pin.ev) {
@@ -479,8 +489,8 @@ static int ta_upload(const TaPlan& P, const int32_t* views, int n, bool want_gro
     memset(h, 0, bytes);
     memcpy(h, views, (size_t)n * 24);
     if (want_groups) {
-        memcpy(h + ta_up256((size_t)n * 24), P.groups.data(), P.groups.size() * sizeof(TaGroup));
-        memcpy(h + ta_up256((size_t)n * 24) + ta_up256((size_t)n * 16), P.list.data(), (size_t)n * 4);
+        memcpy(h + L.groups, P.groups.data(), P.groups.size() * sizeof(TaGroup));
+        memcpy(h + L.list, P.list.data(), (size_t)n * 4);
     }
     if (hipMemcpyAsync(scratch, h, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return fail("%s: the table upload failed", who);
     if (hipEventCreateWithFlags(&pin.ev, hipEventDisableTiming) != hipSuccess) { pin.ev = nullptr; return fail("%s: no event", who); }
@@ -498,23 +508,22 @@ static const char* ta_args_error(const must3r_hip_attn_train_args* a, bool grad)
     if (bad_ld(a->ldq) || bad_ld(a->ldk) || bad_ld(a->ldv)) return "a leading dimension must be at least heads * 64 and a multiple of 4";
     if (grad ? bad_ld(a->lddo) || (a->dQ && bad_ld(a->lddq)) || (a->dK && bad_ld(a->lddk)) || (a->dV && bad_ld(a->lddv)) : bad_ld(a->ldo))
         return "a leading dimension must be at least heads * 64 and a multiple of 4";
-    if (ta_misaligned(a->q) || ta_misaligned(a->k) || ta_misaligned(a->v) || ta_misaligned(a->dO) || ta_misaligned(a->O) || ta_misaligned(a->lse) ||
-        ta_misaligned(a->dQ) || ta_misaligned(a->dK) || ta_misaligned(a->dV))
+    if (misaligned(a->q) || misaligned(a->k) || misaligned(a->v) || misaligned(a->dO) || misaligned(a->O) || misaligned(a->lse) ||
+        misaligned(a->dQ) || misaligned(a->dK) || misaligned(a->dV))
         return "tensors must be 16-byte aligned";
     return nullptr;
 }
 
 static TaArgs ta_kernel_args(const must3r_hip_attn_train_args* a, const TaPlan& P, char* scratch) {
-    const int n = a->n_views;
     TaArgs k{};
     k.Q = a->q; k.K = a->k; k.V = a->v; k.dO = a->dO;
     k.ldq = a->ldq; k.ldk = a->ldk; k.ldv = a->ldv; k.lddo = a->lddo; k.heads = a->heads;
-    char* p = scratch;
-    k.views = reinterpret_cast<const AttnView*>(p); p += ta_up256((size_t)n * 24);
-    k.groups = reinterpret_cast<const TaGroup*>(p); p += ta_up256((size_t)n * 16);
-    k.list = reinterpret_cast<const int*>(p); p += ta_up256((size_t)n * 4);
-    k.lse2 = reinterpret_cast<float*>(p); p += ta_up256((size_t)P.total_q_rows * a->heads * 4);
-    k.delta = reinterpret_cast<float*>(p);
+    const TaLayout L = ta_layout(a->n_views, P.total_q_rows, a->heads);
+    k.views = reinterpret_cast<const AttnView*>(scratch + L.views);
+    k.groups = reinterpret_cast<const TaGroup*>(scratch + L.groups);
+    k.list = reinterpret_cast<const int*>(scratch + L.list);
+    k.lse2 = reinterpret_cast<float*>(scratch + L.lse2);
+    k.delta = reinterpret_cast<float*>(scratch + L.delta);
     return k;
 }
 
@@ -526,7 +535,7 @@ extern "C" size_t must3r_hip_attn_train_scratch_bytes(int n_views, int total_q_r
         fail("attn_train_scratch_bytes: n_views in [1, 65535], non-negative row counts and heads in [1, 65535] are required");
         return 0;
     }
-    return ta_scratch(n_views, total_q_rows, heads);
+    return ta_layout(n_views, total_q_rows, heads).total;
 }
 
 extern "C" int must3r_hip_attn_train_groups(const int32_t* views_host, int n_views) {
@@ -541,7 +550,7 @@ extern "C" int must3r_hip_attn_forward_f32(const must3r_hip_attn_train_args* a, 
     if (a->heads > 65535) return fail("attn_forward_f32: more than 65535 heads");
     TaPlan P;
     if (const char* e = ta_plan(a->views, a->n_views, false, P)) return fail("attn_forward_f32: %s", e);
-    if (!scratch || ta_misaligned(scratch) || scratch_bytes < ta_scratch(a->n_views, P.total_q_rows, a->heads)) return fail("attn_forward_f32: scratch too small");
+    if (!scratch || misaligned(scratch) || scratch_bytes < ta_layout(a->n_views, P.total_q_rows, a->heads).total) return fail("attn_forward_f32: scratch too small");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (P.max_nq == 0) return 0;
     if (ta_upload(P, a->views, a->n_views, false, reinterpret_cast<char*>(scratch), s, "attn_forward_f32")) return 1;
@@ -559,7 +568,7 @@ extern "C" int must3r_hip_attn_grad(const must3r_hip_attn_train_args* a, void* s
     if (a->heads > 65535) return fail("attn_grad: more than 65535 heads");
     TaPlan P;
     if (const char* e = ta_plan(a->views, a->n_views, true, P)) return fail("attn_grad: %s", e);
-    if (!scratch || ta_misaligned(scratch) || scratch_bytes < ta_scratch(a->n_views, P.total_q_rows, a->heads)) return fail("attn_grad: scratch too small");
+    if (!scratch || misaligned(scratch) || scratch_bytes < ta_layout(a->n_views, P.total_q_rows, a->heads).total) return fail("attn_grad: scratch too small");
     const bool want_kv = a->dK || a->dV;
     if (!a->dQ && !want_kv) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -3,6 +3,9 @@
 //   MLP sublayer         y = x + fc2(gelu(fc1(LN(x))))             (croco Mlp, erf GELU)
 // The forward saves nothing but its inputs; the backward recomputes the sublayer's forward into scratch and differentiates it with the plain operator
 // forms of train_head.hip (linear_dgrad_f32, linear_wgrad_f32, layernorm_grad with the residual added) and the attention core of train_attention.hip.
+// What the two backward passes share with each other and with the cross sublayer's (the shortcut for the last bias alone, the gradients at proj, the closing
+// tail) is train_common.hpp's, as are the host helpers and the view-table check; what is written out here is a sublayer's own: RoPE and its transpose, GELU
+// and its derivative.
 //
 //   linear_fwd_f32<EPI>   out[M, N] = A[M, K] W[N, K]^T + bias on v_mfma_f32_16x16x4_f32: the NT sibling of dgrad_kernel -- 128 x 128 tiles, 16-deep steps
 //                         over K through LDS, 4 waves of 64 x 64, the next K-tile fetched into registers under the products of the current one.  Both
@@ -16,11 +19,10 @@
 // Phi(z) + z phi(z).  (gelu_erf of common.hpp is a fitted quartic for 16-bit outputs and has no matching derivative.)
 // No atomics: every output element has one writer and a fixed order of operations; a row of any row-wise output does not depend on the other rows.
 #include <algorithm>
-#include <utility>
-#include <vector>
 
 #include "abi.hpp"
 #include "common.hpp"
+#include "train_common.hpp"
 
 namespace m3r {
 
@@ -217,14 +219,6 @@ __global__ void __launch_bounds__(256) rope_rows_f32(float* __restrict__ t, long
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------------
-#define M3R_RUN(expr)                 \
-    do {                              \
-        int rc__ = (expr);            \
-        if (rc__) return rc__;        \
-    } while (0)
-
-static size_t tb_up256(size_t v) { return (v + 255) / 256 * 256; }
-static bool tb_misaligned(const void* p) { return ((size_t)p & 15) != 0; }
 static unsigned tb_grid(long long items) {
     const long long b = (items + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
@@ -239,8 +233,8 @@ static int run_linear(const char* who, int epi, const float* A, int lda, const f
     if (K % 16 || N % 4) return fail("%s: K must be a multiple of 16 and N of 4", who);
     if (lda < K || lda % 4 || ldc < N || ldc % 4 || (epi == LIN_BIAS_RES && (ldres < N || ldres % 4)) || (epi == LIN_BIAS_GELU && zout && (ldz < N || ldz % 4)))
         return fail("%s: a leading dimension must cover its row and be a multiple of 4", who);
-    if (tb_misaligned(A) || tb_misaligned(W) || tb_misaligned(bias) || tb_misaligned(out) || (epi == LIN_BIAS_RES && tb_misaligned(res)) ||
-        (epi == LIN_BIAS_GELU && tb_misaligned(zout)))
+    if (misaligned(A) || misaligned(W) || misaligned(bias) || misaligned(out) || (epi == LIN_BIAS_RES && misaligned(res)) ||
+        (epi == LIN_BIAS_GELU && misaligned(zout)))
         return fail("%s: tensors must be 16-byte aligned", who);
     const int n_tiles = (N + BN - 1) / BN;
     const long long blocks = (long long)((M + BM - 1) / BM) * n_tiles;
@@ -267,7 +261,7 @@ static int run_rope(const char* who, float* t, int ld, const int64_t* pos, const
     if (!t || !pos || !tab) return fail("%s: null argument", who);
     if (npos <= 0) return fail("%s: the table needs at least one position", who);
     if (ld < rope_cols || ld % 4) return fail("%s: the leading dimension must cover rope_cols and be a multiple of 4", who);
-    if (tb_misaligned(t) || tb_misaligned(pos) || tb_misaligned(tab)) return fail("%s: tensors must be 16-byte aligned", who);
+    if (misaligned(t) || misaligned(pos) || misaligned(tab)) return fail("%s: tensors must be 16-byte aligned", who);
     const int items = rope_cols / 8;
     hipLaunchKernelGGL(rope_rows_f32, dim3(tb_grid((long long)R * items)), dim3(256), 0, s, t, (long long)ld, reinterpret_cast<const long long*>(pos), tab, npos,
                        (long long)R, items, (float)direction);
@@ -280,33 +274,25 @@ static int run_gelu_grad(const char* who, const float* dh, int ldh, const float*
     if (M == 0) return 0;
     if (!dh || !z || !dz) return fail("%s: null argument", who);
     if (ldh < N || ldh % 4 || ldz < N || ldz % 4 || lddz < N || lddz % 4) return fail("%s: a leading dimension must cover its row and be a multiple of 4", who);
-    if (tb_misaligned(dh) || tb_misaligned(z) || tb_misaligned(dz)) return fail("%s: tensors must be 16-byte aligned", who);
+    if (misaligned(dh) || misaligned(z) || misaligned(dz)) return fail("%s: tensors must be 16-byte aligned", who);
     hipLaunchKernelGGL(gelu_grad_f32, dim3(tb_grid((long long)M * (N / 4))), dim3(256), 0, s, dh, (long long)ldh, z, (long long)ldz, dz, (long long)lddz, M, N / 4);
     if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
     return 0;
-}
-
-static const char* width_error(int M, int D) {
-    if (M <= 0) return "M must be positive";
-    if (D <= 0 || D % 64) return "D must be a positive multiple of 64";
-    if (D > 1024) return "D must not exceed 1024";
-    if (M > 0x7fffffff / 4) return "too many rows";
-    return nullptr;
 }
 
 // MLP scratch: [y M D | S1 M hidden | S2 M hidden | weight-gradient partials | LayerNorm backward]
 struct MlpLayout { size_t y, s1, s2, wg, wg_bytes, ln, ln_bytes, total; };
 static MlpLayout mlp_layout(int M, int D, int hidden) {
     MlpLayout L{};
-    size_t o = 0;
-    L.y = o; o += tb_up256((size_t)M * D * 4);
-    L.s1 = o; o += tb_up256((size_t)M * hidden * 4);
-    L.s2 = o; o += tb_up256((size_t)M * hidden * 4);
+    ScratchCursor c;
+    L.y = c.take((size_t)M * D * 4);
+    L.s1 = c.take((size_t)M * hidden * 4);
+    L.s2 = c.take((size_t)M * hidden * 4);
     L.wg_bytes = std::max(must3r_hip_op_linear_wgrad_scratch_bytes(M, D, hidden), must3r_hip_op_linear_wgrad_scratch_bytes(M, hidden, D));
-    L.wg = o; o += tb_up256(L.wg_bytes);
+    L.wg = c.take(L.wg_bytes);
     L.ln_bytes = must3r_hip_op_layernorm_grad_scratch_bytes(M, D);
-    L.ln = o; o += tb_up256(L.ln_bytes);
-    L.total = o;
+    L.ln = c.take(L.ln_bytes);
+    L.total = c.off;
     return L;
 }
 
@@ -314,71 +300,47 @@ static MlpLayout mlp_layout(int M, int D, int hidden) {
 struct AttnLayout { size_t y, qkv, o, dO, dqkv, wg, wg_bytes, ln, ln_bytes, core, core_bytes, total; };
 static AttnLayout attn_layout(int M, int D, int n_views) {
     AttnLayout L{};
-    size_t o = 0;
-    L.y = o; o += tb_up256((size_t)M * D * 4);
-    L.qkv = o; o += tb_up256((size_t)M * 3 * D * 4);
-    L.o = o; o += tb_up256((size_t)M * D * 4);
-    L.dO = o; o += tb_up256((size_t)M * D * 4);
-    L.dqkv = o; o += tb_up256((size_t)M * 3 * D * 4);
+    ScratchCursor c;
+    L.y = c.take((size_t)M * D * 4);
+    L.qkv = c.take((size_t)M * 3 * D * 4);
+    L.o = c.take((size_t)M * D * 4);
+    L.dO = c.take((size_t)M * D * 4);
+    L.dqkv = c.take((size_t)M * 3 * D * 4);
     L.wg_bytes = std::max(must3r_hip_op_linear_wgrad_scratch_bytes(M, 3 * D, D), must3r_hip_op_linear_wgrad_scratch_bytes(M, D, D));
-    L.wg = o; o += tb_up256(L.wg_bytes);
+    L.wg = c.take(L.wg_bytes);
     L.ln_bytes = must3r_hip_op_layernorm_grad_scratch_bytes(M, D);
-    L.ln = o; o += tb_up256(L.ln_bytes);
+    L.ln = c.take(L.ln_bytes);
     L.core_bytes = must3r_hip_attn_train_scratch_bytes(n_views, M, M, D / 64);
-    L.core = o; o += tb_up256(L.core_bytes);
-    L.total = o;
+    L.core = c.take(L.core_bytes);
+    L.total = c.off;
     return L;
 }
 
-static bool spans_cover(std::vector<std::pair<long long, long long>> spans, long long rows) {
-    std::sort(spans.begin(), spans.end());
-    long long end = 0;
-    for (const auto& sp : spans) {
-        if (sp.second <= sp.first) continue;
-        if (sp.first > end) return false;
-        end = std::max(end, sp.second);
-    }
-    return end >= rows;
-}
-
-// the table must stay inside the M rows; *covered: every row is a query row of a view and a key row of a group (nothing for the caller to zero)
-static const char* table_error(const int32_t* views, int n, int M, bool* covered) {
-    if (!views) return "null argument (views)";
-    if (n <= 0 || n > 65535) return "n_views must be in [1, 65535]";
-    std::vector<std::pair<long long, long long>> q, kv;
-    for (int i = 0; i < n; ++i) {
-        const int32_t* v = views + 6 * (size_t)i;
-        for (int e = 0; e < 6; ++e)
-            if (v[e] < 0) return "negative table entry";
-        if ((long long)v[0] + v[1] > M || (long long)v[2] + v[3] > M) return "the table reaches past the M rows";
-        q.emplace_back(v[0], (long long)v[0] + v[1]);
-        kv.emplace_back(v[2], (long long)v[2] + v[3]);
-    }
-    *covered = spans_cover(q, M) && spans_cover(kv, M);
-    return nullptr;
-}
-
 static const char* mlp_args_error(const must3r_hip_mlp_sublayer_args* a, bool grad) {
-    if (const char* e = width_error(a->M, a->D)) return e;
+    if (const char* e = rows_width_error(a->M, a->D)) return e;
     if (a->hidden <= 0 || a->hidden % 16) return "hidden must be a positive multiple of 16";
     if (!a->x || !a->gamma || !a->beta || !a->W1 || !a->W2) return "null argument (x, gamma, beta, W1, W2)";
     if (grad ? !a->dy : !a->out) return grad ? "null argument (dy)" : "null argument (out)";
-    if (tb_misaligned(a->x) || tb_misaligned(a->gamma) || tb_misaligned(a->beta) || tb_misaligned(a->W1) || tb_misaligned(a->W2) || tb_misaligned(a->b1) || tb_misaligned(a->b2) || tb_misaligned(a->dy) ||
-        tb_misaligned(a->out) || tb_misaligned(a->dx) || tb_misaligned(a->dW1) || tb_misaligned(a->dW2))
+    if (misaligned(a->x) || misaligned(a->gamma) || misaligned(a->beta) || misaligned(a->W1) || misaligned(a->W2) || misaligned(a->b1) || misaligned(a->b2) || misaligned(a->dy) ||
+        misaligned(a->out) || misaligned(a->dx) || misaligned(a->dW1) || misaligned(a->dW2))
         return "tensors must be 16-byte aligned";
     return nullptr;
 }
 
+// *covered: every row is a query row of a view and a key row of a group (nothing to zero)
 static const char* attn_args_error(const must3r_hip_attn_sublayer_args* a, bool grad, bool* covered) {
-    if (const char* e = width_error(a->M, a->D)) return e;
+    if (const char* e = rows_width_error(a->M, a->D)) return e;
     if (!a->x || !a->gamma || !a->beta || !a->Wqkv || !a->Wproj) return "null argument (x, gamma, beta, Wqkv, Wproj)";
     if (!a->pos || !a->rope_tab) return "null argument (pos, rope_tab)";
     if (a->rope_npos <= 0) return "the RoPE table needs at least one position";
     if (grad ? !a->dy : !a->out) return grad ? "null argument (dy)" : "null argument (out)";
-    if (tb_misaligned(a->x) || tb_misaligned(a->gamma) || tb_misaligned(a->beta) || tb_misaligned(a->Wqkv) || tb_misaligned(a->Wproj) || tb_misaligned(a->bqkv) || tb_misaligned(a->bproj) || tb_misaligned(a->dy) ||
-        tb_misaligned(a->out) || tb_misaligned(a->dx) || tb_misaligned(a->dWqkv) || tb_misaligned(a->dWproj) || tb_misaligned(a->pos) || tb_misaligned(a->rope_tab))
+    if (misaligned(a->x) || misaligned(a->gamma) || misaligned(a->beta) || misaligned(a->Wqkv) || misaligned(a->Wproj) || misaligned(a->bqkv) || misaligned(a->bproj) || misaligned(a->dy) ||
+        misaligned(a->out) || misaligned(a->dx) || misaligned(a->dWqkv) || misaligned(a->dWproj) || misaligned(a->pos) || misaligned(a->rope_tab))
         return "tensors must be 16-byte aligned";
-    return table_error(a->views, a->n_views, a->M, covered);
+    bool q_covered = false, kv_covered = false;
+    const char* e = view_table_error(a->views, a->n_views, a->M, a->M, &q_covered, &kv_covered);
+    *covered = q_covered && kv_covered;
+    return e;
 }
 
 }  // namespace m3r
@@ -392,7 +354,7 @@ extern "C" int must3r_hip_op_linear_f32(int epi, const float* A, int lda, const 
 extern "C" int must3r_hip_op_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int M, int D, float eps, void* stream) {
     if (M <= 0 || D <= 0 || D % 64 || D > 1024) return fail("op_layernorm_f32: M must be positive, D a multiple of 64 and at most 1024");
     if (!x || !gamma || !beta || !y) return fail("op_layernorm_f32: null argument");
-    if (tb_misaligned(x) || tb_misaligned(gamma) || tb_misaligned(beta) || tb_misaligned(y)) return fail("op_layernorm_f32: tensors must be 16-byte aligned");
+    if (misaligned(x) || misaligned(gamma) || misaligned(beta) || misaligned(y)) return fail("op_layernorm_f32: tensors must be 16-byte aligned");
     return run_ln("op_layernorm_f32", x, gamma, beta, y, M, D, eps, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -415,14 +377,16 @@ extern "C" int must3r_hip_op_rope_f32(float* t, int ld, const int64_t* pos, cons
 }
 
 extern "C" size_t must3r_hip_mlp_sublayer_scratch_bytes(int M, int D, int hidden) {
-    if (width_error(M, D) || hidden <= 0 || hidden % 16) return 0;
+    if (rows_width_error(M, D) || hidden <= 0 || hidden % 16) return 0;
     return mlp_layout(M, D, hidden).total;
 }
 
 extern "C" size_t must3r_hip_attn_sublayer_scratch_bytes(int M, int D, int n_views) {
-    if (width_error(M, D) || n_views <= 0 || n_views > 65535) return 0;
+    if (rows_width_error(M, D) || n_views <= 0 || n_views > 65535) return 0;
     return attn_layout(M, D, n_views).total;
 }
+
+// Inside the sublayer entry points the stream is `s`, a hipStream_t: the run_* launchers take it as it is, the must3r_hip_op_* calls as their void*.
 
 extern "C" int must3r_hip_mlp_sublayer_forward(const must3r_hip_mlp_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream) {
     const char* who = "mlp_sublayer_forward";
@@ -430,7 +394,7 @@ extern "C" int must3r_hip_mlp_sublayer_forward(const must3r_hip_mlp_sublayer_arg
     if (const char* e = mlp_args_error(a, false)) return fail("%s: %s", who, e);
     const int M = a->M, D = a->D, Hd = a->hidden;
     const MlpLayout L = mlp_layout(M, D, Hd);
-    if (!scratch || tb_misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
+    if (!scratch || misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* p = reinterpret_cast<char*>(scratch);
     float* y = reinterpret_cast<float*>(p + L.y);
@@ -446,31 +410,23 @@ extern "C" int must3r_hip_mlp_sublayer_grad(const must3r_hip_mlp_sublayer_args* 
     if (const char* e = mlp_args_error(a, true)) return fail("%s: %s", who, e);
     const int M = a->M, D = a->D, Hd = a->hidden;
     const MlpLayout L = mlp_layout(M, D, Hd);
-    if (!scratch || tb_misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
-    const bool want_w2 = a->dW2 || a->db2, want_w1 = a->dW1 || a->db1, want_ln = a->dx || a->dgamma || a->dbeta;
-    const bool want_dz = want_w1 || want_ln;
-    if (!want_w2 && !want_dz) return 0;
+    if (!scratch || misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
+    const bool want_dz = a->dW1 || a->db1 || a->dx || a->dgamma || a->dbeta;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* p = reinterpret_cast<char*>(scratch);
     float* y = reinterpret_cast<float*>(p + L.y);
     float* s1 = reinterpret_cast<float*>(p + L.s1);
     float* s2 = reinterpret_cast<float*>(p + L.s2);
-    if (want_w2 && !a->dW2) {
-        // db of fc2 alone is the column sums of dy: no forward
-        M3R_RUN(must3r_hip_op_linear_wgrad_f32(a->dy, D, nullptr, 0, nullptr, a->db2, M, D, Hd, p + L.wg, L.wg_bytes, stream));
-        if (!want_dz) return 0;
-    }
+    M3R_RUN(last_bias_alone(a, L, p, a->dW2, a->db2, Hd, s));
+    if (!a->dW2 && !want_dz) return 0;
     // the forward once more: y = LN(x), z = fc1(y) -> S1 (only the activation's derivative reads it), h = gelu(z) -> S2 (only dW2 reads it)
     M3R_RUN(run_ln(who, a->x, a->gamma, a->beta, y, M, D, a->eps, s));
     M3R_RUN(run_linear(who, LIN_BIAS_GELU, y, D, a->W1, a->b1, nullptr, 0, s2, Hd, want_dz ? s1 : nullptr, Hd, M, Hd, D, s));
-    if (a->dW2) M3R_RUN(must3r_hip_op_linear_wgrad_f32(a->dy, D, s2, Hd, a->dW2, a->db2, M, D, Hd, p + L.wg, L.wg_bytes, stream));
+    if (a->dW2) M3R_RUN(must3r_hip_op_linear_wgrad_f32(a->dy, D, s2, Hd, a->dW2, a->db2, M, D, Hd, p + L.wg, L.wg_bytes, s));
     if (!want_dz) return 0;
-    M3R_RUN(must3r_hip_op_linear_dgrad_f32(a->dy, D, a->W2, s2, M, D, Hd, stream));                 // dh over h
+    M3R_RUN(must3r_hip_op_linear_dgrad_f32(a->dy, D, a->W2, s2, M, D, Hd, s));                      // dh over h
     M3R_RUN(run_gelu_grad(who, s2, Hd, s1, Hd, s2, Hd, M, Hd, s));                                  // dz over dh
-    if (want_w1) M3R_RUN(must3r_hip_op_linear_wgrad_f32(s2, Hd, y, D, a->dW1, a->db1, M, Hd, D, p + L.wg, L.wg_bytes, stream));
-    if (!want_ln) return 0;
-    M3R_RUN(must3r_hip_op_linear_dgrad_f32(s2, Hd, a->W1, y, M, Hd, D, stream));                    // dL/dy over y
-    return must3r_hip_op_layernorm_grad_add(a->x, a->gamma, y, a->dy, a->dx, a->dgamma, a->dbeta, M, D, a->eps, p + L.ln, L.ln_bytes, stream);
+    return sublayer_grad_tail(a, L, p, s2, Hd, a->W1, Hd, a->dW1, a->db1, y, s);
 }
 
 // y = LN(x) -> qkv = y Wqkv^T + b, rotated on its first 2 D columns -> o = attention(q, k, v)
@@ -478,17 +434,10 @@ static int attn_recompute(const char* who, const must3r_hip_attn_sublayer_args* 
     const int M = a->M, D = a->D;
     float* y = reinterpret_cast<float*>(p + L.y);
     float* qkv = reinterpret_cast<float*>(p + L.qkv);
-    float* o = reinterpret_cast<float*>(p + L.o);
     M3R_RUN(run_ln(who, a->x, a->gamma, a->beta, y, M, D, a->eps, s));
     M3R_RUN(run_linear(who, LIN_BIAS, y, D, a->Wqkv, a->bqkv, nullptr, 0, qkv, 3 * D, nullptr, 0, M, 3 * D, D, s));
     M3R_RUN(run_rope(who, qkv, 3 * D, a->pos, a->rope_tab, a->rope_npos, M, 2 * D, 1, s));
-    if (!covered && hipMemsetAsync(o, 0, (size_t)M * D * 4, s) != hipSuccess) return fail("%s: memset failed", who);   // a row of no view attends nothing
-    must3r_hip_attn_train_args t{};
-    t.q = qkv; t.k = qkv + D; t.v = qkv + 2 * D;
-    t.ldq = t.ldk = t.ldv = 3 * D;
-    t.heads = D / 64; t.n_views = a->n_views; t.views = a->views;
-    t.O = o; t.ldo = D;
-    return must3r_hip_attn_forward_f32(&t, p + L.core, L.core_bytes, s);
+    return sublayer_attend(who, a, L, p, core_args(a, qkv, 3 * D, qkv + D, qkv + 2 * D, 3 * D), reinterpret_cast<float*>(p + L.o), covered, s);
 }
 
 extern "C" int must3r_hip_attn_sublayer_forward(const must3r_hip_attn_sublayer_args* a, void* scratch, size_t scratch_bytes, void* stream) {
@@ -497,7 +446,7 @@ extern "C" int must3r_hip_attn_sublayer_forward(const must3r_hip_attn_sublayer_a
     bool covered = false;
     if (const char* e = attn_args_error(a, false, &covered)) return fail("%s: %s", who, e);
     const AttnLayout L = attn_layout(a->M, a->D, a->n_views);
-    if (!scratch || tb_misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
+    if (!scratch || misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* p = reinterpret_cast<char*>(scratch);
     M3R_RUN(attn_recompute(who, a, L, p, covered, s));
@@ -513,37 +462,25 @@ extern "C" int must3r_hip_attn_sublayer_grad(const must3r_hip_attn_sublayer_args
     const int M = a->M, D = a->D;
     if (must3r_hip_attn_train_groups(a->views, a->n_views) < 0) return 1;   // overlapping key groups: the error text is the core's
     const AttnLayout L = attn_layout(M, D, a->n_views);
-    if (!scratch || tb_misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
-    const bool want_wp = a->dWproj || a->dbproj, want_wq = a->dWqkv || a->dbqkv, want_ln = a->dx || a->dgamma || a->dbeta;
-    const bool want_dqkv = want_wq || want_ln;
-    if (!want_wp && !want_dqkv) return 0;
+    if (!scratch || misaligned(scratch) || scratch_bytes < L.total) return fail("%s: scratch too small", who);
+    const bool want_dqkv = a->dWqkv || a->dbqkv || a->dx || a->dgamma || a->dbeta;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     char* p = reinterpret_cast<char*>(scratch);
     float* y = reinterpret_cast<float*>(p + L.y);
     float* qkv = reinterpret_cast<float*>(p + L.qkv);
-    float* o = reinterpret_cast<float*>(p + L.o);
     float* dO = reinterpret_cast<float*>(p + L.dO);
     float* dqkv = reinterpret_cast<float*>(p + L.dqkv);
-    if (want_wp && !a->dWproj) {
-        // db of proj alone needs neither o nor the forward
-        M3R_RUN(must3r_hip_op_linear_wgrad_f32(a->dy, D, nullptr, 0, nullptr, a->dbproj, M, D, D, p + L.wg, L.wg_bytes, stream));
-        if (!want_dqkv) return 0;
-    }
+    M3R_RUN(last_bias_alone(a, L, p, a->dWproj, a->dbproj, D, s));
+    if (!a->dWproj && !want_dqkv) return 0;
     M3R_RUN(attn_recompute(who, a, L, p, covered, s));
-    if (a->dWproj) M3R_RUN(must3r_hip_op_linear_wgrad_f32(a->dy, D, o, D, a->dWproj, a->dbproj, M, D, D, p + L.wg, L.wg_bytes, stream));
+    M3R_RUN(proj_grad(a, L, p, reinterpret_cast<float*>(p + L.o), want_dqkv ? dO : nullptr, s));
     if (!want_dqkv) return 0;
-    M3R_RUN(must3r_hip_op_linear_dgrad_f32(a->dy, D, a->Wproj, dO, M, D, D, stream));
     if (!covered && hipMemsetAsync(dqkv, 0, (size_t)M * 3 * D * 4, s) != hipSuccess) return fail("%s: memset failed", who);
-    must3r_hip_attn_train_args t{};
-    t.q = qkv; t.k = qkv + D; t.v = qkv + 2 * D; t.dO = dO;
-    t.ldq = t.ldk = t.ldv = 3 * D; t.lddo = D;
-    t.heads = D / 64; t.n_views = a->n_views; t.views = a->views;
+    must3r_hip_attn_train_args t = core_args(a, qkv, 3 * D, qkv + D, qkv + 2 * D, 3 * D);
+    t.dO = dO; t.lddo = D;
     t.dQ = dqkv; t.dK = dqkv + D; t.dV = dqkv + 2 * D;
     t.lddq = t.lddk = t.lddv = 3 * D;
     M3R_RUN(must3r_hip_attn_grad(&t, p + L.core, L.core_bytes, s));
     M3R_RUN(run_rope(who, dqkv, 3 * D, a->pos, a->rope_tab, a->rope_npos, M, 2 * D, -1, s));
-    if (want_wq) M3R_RUN(must3r_hip_op_linear_wgrad_f32(dqkv, 3 * D, y, D, a->dWqkv, a->dbqkv, M, 3 * D, D, p + L.wg, L.wg_bytes, stream));
-    if (!want_ln) return 0;
-    M3R_RUN(must3r_hip_op_linear_dgrad_f32(dqkv, 3 * D, a->Wqkv, y, M, 3 * D, D, stream));         // dL/dy over y
-    return must3r_hip_op_layernorm_grad_add(a->x, a->gamma, y, a->dy, a->dx, a->dgamma, a->dbeta, M, D, a->eps, p + L.ln, L.ln_bytes, stream);
+    return sublayer_grad_tail(a, L, p, dqkv, 3 * D, a->Wqkv, 3 * D, a->dWqkv, a->dbqkv, y, s);
 }

@@ -25,6 +25,7 @@
 #include "abi.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
+#include "train_common.hpp"
 
 namespace m3r {
 
@@ -390,13 +391,6 @@ __global__ void __launch_bounds__(256) ln_grad_reduce_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------------
-#define M3R_RUN(expr)                 \
-    do {                              \
-        int rc__ = (expr);            \
-        if (rc__) return rc__;        \
-    } while (0)
-
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 static int wgrad_splits(long long R) {
     const long long s = (R + WGRAD_ROWS_PER_SPLIT - 1) / WGRAD_ROWS_PER_SPLIT;
     return (int)(s < 1 ? 1 : (s > WGRAD_MAX_SPLITS ? WGRAD_MAX_SPLITS : s));
@@ -413,8 +407,6 @@ static int lng_blocks(int R) { const int rpb = lng_rows_per_block(R); return (R 
 
 static size_t wgrad_scratch(int M, int O, int K) { return up256((size_t)wgrad_splits(M) * O * K * 4) + up256((size_t)wgrad_splits(M) * O * 4); }
 static size_t lng_scratch(int M, int D) { return up256((size_t)M * 8) + up256((size_t)lng_blocks(M) * 2 * D * 4); }
-
-static bool misaligned(const void* p) { return ((size_t)p & 15) != 0; }
 
 static int run_dgrad(bool gather, const DzSrc& z, const float* W, float* out, int M, int O, int K, hipStream_t s) {
     const int n_tiles = (K + HN - 1) / HN;

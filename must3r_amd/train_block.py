@@ -23,39 +23,11 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .train_attention import _table, n_groups, self_views
+from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _new, _Proj, _ptr, _rows, _scratch, _stream
+from .train_attention import _check_table, _table, n_groups, self_views
 
-HEAD = 64
 ROPE_NPOS = 256          # positions of the default table (a 4096-pixel side), as the native model's
 _rope_tables = {}
-
-
-def _dev(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"must3r_amd.train_block: {what} must be a tensor on the GPU (there is no CPU path)")
-    return t
-
-
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(_lib.stream_ptr(dev))
-
-
-def _scratch(nbytes, dev):
-    if not nbytes:
-        raise _lib.HipError(_lib.load().must3r_hip_last_error().decode("utf-8", "replace") or "train_block: bad shape")
-    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-
-
-def _new(need, dev, *shape):
-    return torch.empty(shape, dtype=torch.float32, device=dev) if need else None
 
 
 def rope_table(device, freq=100.0, f0=1.0, npos=ROPE_NPOS):
@@ -187,11 +159,7 @@ def mlp_forward(x, gamma, beta, W1, b1, W2, b2, eps=1e-6):
     lib = _lib.load()
     a = _mlp_args(x, gamma, beta, W1, b1, W2, b2, eps)
     out = torch.empty_like(x)
-    a.out = _ptr(out)
-    with torch.cuda.device(x.device):
-        nbytes = lib.must3r_hip_mlp_sublayer_scratch_bytes(a.M, a.D, a.hidden)
-        scratch = _scratch(nbytes, x.device)
-        _lib.check(lib.must3r_hip_mlp_sublayer_forward(C.byref(a), _ptr(scratch), nbytes, _stream(x.device)))
+    _call_sublayer(lib.must3r_hip_mlp_sublayer_forward, a, lib.must3r_hip_mlp_sublayer_scratch_bytes(a.M, a.D, a.hidden), x.device, out=out)
     return out
 
 
@@ -201,15 +169,8 @@ def mlp_grad(x, gamma, beta, W1, b1, W2, b2, dy, eps=1e-6, want=(True,) * 7):
     a = _mlp_args(x, gamma, beta, W1, b1, W2, b2, eps)
     dev, D, Hd = x.device, a.D, a.hidden
     outs = [_new(w, dev, *s) for w, s in zip(want, (x.shape, (D,), (D,), (Hd, D), (Hd,), (D, Hd), (D,)))]
-    if not any(want):
-        return outs
-    a.dy = _ptr(dy)
-    for n, t in zip(MLP_OUTPUTS, outs):
-        setattr(a, n, _ptr(t))
-    with torch.cuda.device(dev):
-        nbytes = lib.must3r_hip_mlp_sublayer_scratch_bytes(a.M, D, Hd)
-        scratch = _scratch(nbytes, dev)
-        _lib.check(lib.must3r_hip_mlp_sublayer_grad(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
+    if any(want):
+        _call_sublayer(lib.must3r_hip_mlp_sublayer_grad, a, lib.must3r_hip_mlp_sublayer_scratch_bytes(a.M, D, Hd), dev, dy=dy, **dict(zip(MLP_OUTPUTS, outs)))
     return outs
 
 
@@ -225,11 +186,7 @@ def attn_forward(x, pos, tab, rope_tab, gamma, beta, Wqkv, bqkv, Wproj, bproj, e
     lib = _lib.load()
     a = _attn_args(x, pos, tab, rope_tab, gamma, beta, Wqkv, bqkv, Wproj, bproj, eps)
     out = torch.empty_like(x)
-    a.out = _ptr(out)
-    with torch.cuda.device(x.device):
-        nbytes = lib.must3r_hip_attn_sublayer_scratch_bytes(a.M, a.D, a.n_views)
-        scratch = _scratch(nbytes, x.device)
-        _lib.check(lib.must3r_hip_attn_sublayer_forward(C.byref(a), _ptr(scratch), nbytes, _stream(x.device)))
+    _call_sublayer(lib.must3r_hip_attn_sublayer_forward, a, lib.must3r_hip_attn_sublayer_scratch_bytes(a.M, a.D, a.n_views), x.device, out=out)
     return out
 
 
@@ -239,29 +196,14 @@ def attn_grad(x, pos, tab, rope_tab, gamma, beta, Wqkv, bqkv, Wproj, bproj, dy, 
     a = _attn_args(x, pos, tab, rope_tab, gamma, beta, Wqkv, bqkv, Wproj, bproj, eps)
     dev, D = x.device, a.D
     outs = [_new(w, dev, *s) for w, s in zip(want, (x.shape, (D,), (D,), (3 * D, D), (3 * D,), (D, D), (D,)))]
-    if not any(want):
-        return outs
-    a.dy = _ptr(dy)
-    for n, t in zip(ATTN_OUTPUTS, outs):
-        setattr(a, n, _ptr(t))
-    with torch.cuda.device(dev):
-        nbytes = lib.must3r_hip_attn_sublayer_scratch_bytes(a.M, D, a.n_views)
-        scratch = _scratch(nbytes, dev)
-        _lib.check(lib.must3r_hip_attn_sublayer_grad(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
+    if any(want):
+        _call_sublayer(lib.must3r_hip_attn_sublayer_grad, a, lib.must3r_hip_attn_sublayer_scratch_bytes(a.M, D, a.n_views), dev, dy=dy, **dict(zip(ATTN_OUTPUTS, outs)))
     return outs
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # autograd
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def _rows(t):
-    return _f32(t).view(-1, t.shape[-1])
-
-
-def _back(grads, saved):
-    return [None if g is None else g.reshape(t.shape).to(t.dtype) for g, t in zip(grads, saved)]
-
-
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -322,20 +264,6 @@ class _Attn(torch.autograd.Function):
         return (*_back(grads, saved), None, None, None, None)
 
 
-def _check_x(x, what):
-    _dev(x, what)
-    if x.ndim < 2 or x.numel() == 0:
-        raise ValueError(f"{what} of shape {tuple(x.shape)}, expected [..., D] with rows")
-    return int(x.shape[-1])
-
-
-def _check_params(name, D, **shapes):
-    for n, (t, shape) in shapes.items():
-        _dev(t, n)
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{name}: {n} of shape {tuple(t.shape)}, expected {shape} for tokens of width {D}")
-
-
 def linear(x, weight, bias):
     """``x @ weight.T + bias`` in fp32 on the fp32 MFMA; x [..., K] with K % 16 == 0, weight [N, K] with N % 4 == 0, bias [N]."""
     K = _check_x(x, "linear: x")
@@ -371,7 +299,8 @@ def mlp_sublayer(x, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b, eps=1e-6):
 def attention_sublayer(x, pos, views, heads, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, rope=(100.0, 1.0), eps=1e-6, npos=ROPE_NPOS):
     """``x + proj(attn(rope(qkv(LN(x)))))``; x [..., D] with D = heads * 64, pos int64 [..., 2] (y, x) per row on the GPU, ``views`` the 6-int table of
     ``train_attention`` over the flattened rows (``self_views``; ragged tables are fine), ``rope = (freq, f0)``; differentiable at x and the six
-    parameters.  A position outside the table's ``npos`` positions is refused."""
+    parameters.  A position outside the table's ``npos`` positions is refused, and so is a table with a bad skip range (``skip_lo <= skip_hi <= nk``): with
+    ``ValueError`` here, as in ``cross_attention_sublayer`` (it used to surface as ``HipError`` from the attention core)."""
     D = _check_x(x, "attention_sublayer: x")
     if int(heads) * HEAD != D:
         raise ValueError(f"attention_sublayer: width {D} is not heads * 64 = {int(heads) * HEAD}")
@@ -384,30 +313,13 @@ def attention_sublayer(x, pos, views, heads, norm_w, norm_b, qkv_w, qkv_b, proj_
         raise ValueError(f"attention_sublayer: {pos.numel() // 2} positions for {R} rows")
     pos = pos.reshape(R, 2).contiguous()
     tab = _table(views)
-    v = tab.to(torch.int64)
-    if bool((v < 0).any()) or int((v[:, 0] + v[:, 1]).max()) > R or int((v[:, 2] + v[:, 3]).max()) > R:
-        raise ValueError(f"attention_sublayer: the table has negative entries or reaches past the {R} rows")
+    _check_table(tab, R, R)
     rope_tab = rope_table(x.device, rope[0], rope[1], npos)
     inputs = (x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b)
     if torch.is_grad_enabled() and any(t.requires_grad for t in inputs):
         n_groups(tab)   # a table the backward would refuse is refused here, before the forward runs
         return _Attn.apply(*inputs, pos, tab, rope_tab, float(eps))
     return attn_forward(_rows(x), pos, tab, rope_tab, *(_f32(t) for t in inputs[1:]), float(eps)).view(x.shape)
-
-
-class _Affine(nn.Module):
-    def __init__(self, dim):
-        super().__init__()
-        self.weight = nn.Parameter(torch.ones(dim))
-        self.bias = nn.Parameter(torch.zeros(dim))
-
-
-class _Proj(nn.Module):
-    def __init__(self, dim, out):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(out, dim))
-        self.bias = nn.Parameter(torch.zeros(out))
-        nn.init.xavier_uniform_(self.weight)
 
 
 class _AttnParams(nn.Module):

@@ -26,26 +26,14 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import train_block as TB
+from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _ld, _new, _Proj, _ptr, _rows, _stream
+from ._train_common import _strided_rows as _mem_rows
 from .train_attention import _check_table, _table, n_groups
 from .train_attention import self_views as _self_views
-from .train_block import HEAD, ROPE_NPOS, _Affine, _AttnParams, _back, _check_params, _check_x, _dev, _f32, _MlpParams, _new, _Proj, _ptr, _rows, _scratch
+from .train_block import ROPE_NPOS, _AttnParams, _MlpParams
 
 MEMORY_MODES = ("norm_y", "kv", "raw")
 CROSS_OUTPUTS = ("dx", "dmem", "dgamma", "dbeta", "dWq", "dbq", "dWk", "dbk", "dWv", "dbv", "dWproj", "dbproj")
-
-
-def _mem_rows(mem, width):
-    """fp32 [Rm, width] with a contiguous last dimension and a row stride the kernels take, without a copy where possible."""
-    t = mem.detach()
-    if t.dtype != torch.float32:
-        t = t.to(torch.float32)
-    if t.stride(1) != 1 or t.data_ptr() % 16 or (t.shape[0] > 1 and (t.stride(0) % 4 or t.stride(0) < width)):
-        t = t.clone(memory_format=torch.contiguous_format)
-    return t
-
-
-def _ld(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
 
 
 def _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps):
@@ -54,7 +42,7 @@ def _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, 
     a.Wq, a.bq, a.Wk, a.bk, a.Wv, a.bv, a.Wproj, a.bproj = (_ptr(t) for t in (Wq, bq, Wk, bk, Wv, bv, Wproj, bproj))
     a.views = C.c_void_p(tab.data_ptr())
     a.M, a.Rm, a.D, a.n_views, a.ldmem, a.eps = int(x.shape[0]), int(mem.shape[0]), int(x.shape[1]), int(tab.shape[0]), _ld(mem), float(eps)
-    a.stream = C.c_void_p(_lib.stream_ptr(x.device))
+    a.stream = _stream(x.device)
     return a
 
 
@@ -62,12 +50,9 @@ def cross_forward(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj
     """``must3r_hip_cross_sublayer_forward`` on fp32 GPU tensors (x contiguous, mem row-strided) and an int32 CPU table; ``Wk = bk = Wv = bv = None``: mem holds k | v."""
     lib = _lib.load()
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        a = _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps)
-        a.out = _ptr(out)
-        nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(a.M, a.Rm, a.D, a.n_views, 1 if Wk is None else 0)
-        scratch = _scratch(nbytes, x.device)
-        _lib.check(lib.must3r_hip_cross_sublayer_forward(C.byref(a), _ptr(scratch), nbytes))
+    a = _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps)
+    nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(a.M, a.Rm, a.D, a.n_views, 1 if Wk is None else 0)
+    _call_sublayer(lib.must3r_hip_cross_sublayer_forward, a, nbytes, x.device, out=out)
     return out
 
 
@@ -84,15 +69,10 @@ def cross_grad(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, d
         outs[1] = dmem
     if not any(want):
         return outs
-    with torch.cuda.device(dev):
-        a = _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps)
-        a.dy = _ptr(dy)
-        for n, t in zip(CROSS_OUTPUTS, outs):
-            setattr(a, n, _ptr(t))
-        a.lddmem = _ld(outs[1]) if outs[1] is not None else 0
-        nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(M, Rm, D, a.n_views, 1 if kv_ready else 0)
-        scratch = _scratch(nbytes, dev)
-        _lib.check(lib.must3r_hip_cross_sublayer_grad(C.byref(a), _ptr(scratch), nbytes))
+    a = _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps)
+    a.lddmem = _ld(outs[1]) if outs[1] is not None else 0
+    nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(M, Rm, D, a.n_views, 1 if kv_ready else 0)
+    _call_sublayer(lib.must3r_hip_cross_sublayer_grad, a, nbytes, dev, dy=dy, **dict(zip(CROSS_OUTPUTS, outs)))
     return outs
 
 

@@ -21,6 +21,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._train_common import _Affine, _back, _dev, _f32, _new, _Proj, _ptr, _scratch, _stream
 
 PATCH, CHANNELS = 16, 7
 OUT = CHANNELS * PATCH * PATCH
@@ -31,26 +32,6 @@ def wgrad_splits(rows):
     """Over how many blocks the weight gradient splits its sum over ``rows`` token rows (``must3r_hip_head_grad_splits``): a function of the
     row count alone, so that the order of the additions, and with it every bit of the result, is fixed by the shapes."""
     return max(1, min(WGRAD_MAX_SPLITS, -(-int(rows) // WGRAD_ROWS_PER_SPLIT))) if rows > 0 else 0
-
-
-def _dev(t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"must3r_amd.train_head: {what} must be a tensor on the GPU (there is no CPU path)")
-    return t
-
-
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _scratch(nbytes, dev):
-    if not nbytes:
-        raise _lib.HipError(_lib.load().must3r_hip_last_error().decode("utf-8", "replace"))
-    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
 
 
 def _check_shapes(tokens, img_shape, norm_weight, norm_bias, proj_weight, proj_bias):
@@ -77,7 +58,7 @@ def head_forward(x, gamma, beta, W, b, n_views, H, Wimg, eps=1e-6, dtype=_lib.F1
         nbytes = lib.must3r_hip_head_forward_scratch_bytes(n_views, H, Wimg, D)
         scratch = _scratch(nbytes, x.device)
         _lib.check(lib.must3r_hip_head_forward(dtype, _ptr(x), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(b), n_views, H, Wimg, D, eps, _ptr(out),
-                                               _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(x.device))))
+                                               _ptr(scratch), nbytes, _stream(x.device)))
     return out
 
 
@@ -91,7 +72,7 @@ def head_linear(y, W, b, n_views, H, Wimg, dtype=_lib.F16):
         nbytes = lib.must3r_hip_head_forward_scratch_bytes(n_views, H, Wimg, D)
         scratch = _scratch(nbytes, y.device)
         _lib.check(lib.must3r_hip_op_head_linear(dtype, _ptr(y), _ptr(W), _ptr(b), n_views, H, Wimg, D, _ptr(out), _ptr(scratch), nbytes,
-                                                 C.c_void_p(_lib.stream_ptr(y.device))))
+                                                 _stream(y.device)))
     return out
 
 
@@ -99,11 +80,10 @@ def head_grad(x, gamma, beta, W, G, n_views, H, Wimg, eps=1e-6, want=(True,) * 5
     """``must3r_hip_head_grad`` on contiguous fp32 tensors: ``(dx, dgamma, dbeta, dW, db)``, ``None`` where ``want`` says so."""
     lib = _lib.load()
     D, dev = int(x.shape[-1]), x.device
-    new = lambda need, *shape: torch.empty(shape, dtype=torch.float32, device=dev) if need else None
     want_dx, want_dg, want_dbeta, want_dw, want_db = want
     # dY lives in the dx buffer: the column sums of the LayerNorm backward need one even when the tokens are frozen
-    dx = new(want_dx or want_dg or want_dbeta, *x.shape)
-    dgamma, dbeta, dW, db = new(want_dg, D), new(want_dbeta, D), new(want_dw, OUT, D), new(want_db, OUT)
+    dx = _new(want_dx or want_dg or want_dbeta, dev, *x.shape)
+    dgamma, dbeta, dW, db = _new(want_dg, dev, D), _new(want_dbeta, dev, D), _new(want_dw, dev, OUT, D), _new(want_db, dev, OUT)
     a = _lib.HeadGradArgs()
     a.x, a.gamma, a.beta, a.W, a.G = _ptr(x), _ptr(gamma), _ptr(beta), _ptr(W), _ptr(G)
     a.n_views, a.H, a.Wimg, a.D, a.eps = n_views, H, Wimg, D, eps
@@ -111,7 +91,7 @@ def head_grad(x, gamma, beta, W, G, n_views, H, Wimg, eps=1e-6, want=(True,) * 5
     with torch.cuda.device(dev):
         nbytes = lib.must3r_hip_head_grad_scratch_bytes(n_views, H, Wimg, D)
         scratch = _scratch(nbytes, dev)
-        _lib.check(lib.must3r_hip_head_grad(C.byref(a), _ptr(scratch), nbytes, C.c_void_p(_lib.stream_ptr(dev))))
+        _lib.check(lib.must3r_hip_head_grad(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
     return (dx if want_dx else None), dgamma, dbeta, dW, db
 
 
@@ -133,8 +113,7 @@ class _Head(torch.autograd.Function):
         n_views, H, W, eps = ctx.geom
         x, gamma, beta, Wt, _ = (_f32(t) for t in saved)
         grads = head_grad(x.view(-1, x.shape[-1]), gamma, beta, Wt, _f32(grad_out), n_views, H, W, eps, want=tuple(ctx.needs_input_grad[:5]))
-        out = [None if g is None else g.reshape(t.shape).to(t.dtype) for g, t in zip(grads, saved)]
-        return (*out, None, None, None, None)
+        return (*_back(grads, saved), None, None, None, None)
 
 
 def prediction_head(tokens, img_shape, norm_weight, norm_bias, proj_weight, proj_bias, eps=1e-6, dtype=_lib.F16):
@@ -152,21 +131,6 @@ def prediction_head(tokens, img_shape, norm_weight, norm_bias, proj_weight, proj
     n_views = tokens.numel() // (N * D)
     out = head_forward(_f32(tokens).view(-1, D), *(_f32(t) for t in inputs[1:]), n_views, H, W, float(eps), int(dtype))
     return out.view(*tokens.shape[:-2], H, W, CHANNELS)
-
-
-class _Affine(nn.Module):
-    def __init__(self, dim):
-        super().__init__()
-        self.weight = nn.Parameter(torch.ones(dim))
-        self.bias = nn.Parameter(torch.zeros(dim))
-
-
-class _Proj(nn.Module):
-    def __init__(self, dim, out):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(out, dim))
-        self.bias = nn.Parameter(torch.zeros(out))
-        nn.init.xavier_uniform_(self.weight)
 
 
 class _HeadDec(nn.Module):

@@ -18,26 +18,24 @@ import pytest
 import torch
 
 import attn_grad_ref as AR
+import grad_parity as GP
 from must3r_amd import _lib, train_attention as TA
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-U = 2.0 ** -24
 CANARY = -7.25e11
 _rows = []
+
+_HEADER = (
+    "# tests/test_attn_grad_gpu.py: per case and tensor, e_gpu = max |GPU - fp64|, e_ref = max |fp32 CPU autograd - fp64|, both in units of",
+    "# 2^-24 max|g64|; bound = 4 e_ref + 32; ratio = e_gpu / bound.  O is the fp32 forward's output, held to the same bound.",
+)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _table():
     yield
-    path = os.environ.get("M3R_ATTN_GRAD_TABLE")
-    if _rows and path:
-        with open(path, "w") as f:
-            f.write("# tests/test_attn_grad_gpu.py: per case and tensor, e_gpu = max |GPU - fp64|, e_ref = max |fp32 CPU autograd - fp64|, both in units of\n"
-                    "# 2^-24 max|g64|; bound = 4 e_ref + 32; ratio = e_gpu / bound.  O is the fp32 forward's output, held to the same bound.\n")
-            f.write(f"{'case':<34}{'tensor':<10}{'max|g64|':>12}{'e_gpu':>10}{'e_ref':>10}{'ratio':>8}\n")
-            for r in _rows:
-                f.write(f"{r[0]:<34}{r[1]:<10}{r[2]:>12.4e}{r[3]:>10.2f}{r[4]:>10.2f}{r[5]:>8.3f}\n")
+    GP.write_table(os.environ.get("M3R_ATTN_GRAD_TABLE"), _HEADER, _rows, (34, 10), worst=False)
 
 
 @functools.lru_cache(maxsize=None)
@@ -69,23 +67,7 @@ def _gpu(d, dO=None, want=(True, True, True), views=None):
     return dict(O=o, dQ=dq, dK=dk, dV=dv)
 
 
-def _compare(tag, got, g64, g32):
-    bad = []
-    for k in g64:
-        g = got[k].detach().cpu()
-        assert g.dtype == torch.float32 and g.shape == g64[k].shape, (tag, k)
-        assert bool(torch.isfinite(g64[k]).all()), (tag, k, "the fp64 yardstick is not finite")
-        m = float(g64[k].abs().max())
-        e_gpu = float((g.double() - g64[k]).abs().max())
-        e_ref = float((g32[k].double() - g64[k]).abs().max())
-        bound = 4 * e_ref + 32 * U * m
-        unit = U * m if m > 0 else 1.0
-        ratio = e_gpu / bound if bound > 0 else (0.0 if e_gpu == 0 else float("inf"))
-        _rows.append((tag, k, m, e_gpu / unit, e_ref / unit, ratio))
-        print(f"{tag} {k}: max|g64| {m:.4e} e_gpu {e_gpu / unit:.2f} e_ref {e_ref / unit:.2f} (units of 2^-24 max|g64|) e_gpu / bound {ratio:.3f}")
-        if not e_gpu <= bound:
-            bad.append((k, e_gpu, e_ref, bound))
-    assert not bad, (tag, bad)
+_compare = functools.partial(GP.compare, _rows)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

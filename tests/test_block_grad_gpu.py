@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import block_ref as BR
+import grad_parity as GP
 from must3r_amd import _lib, train_block as TB
 
 pytestmark = pytest.mark.gpu
@@ -33,39 +34,20 @@ _rows = []
 # D, heads, hidden, tokens per view, seed: a key tile plus a tail, one exact tile and one all-tail view; the decoder's and the encoder's geometry
 GEOMS = {"d128_ragged": (128, 2, 512, (70, 64, 17), 41), "d768": (768, 12, 3072, (96, 96), 42), "d1024": (1024, 16, 4096, (96, 96), 43)}
 
+_HEADER = (
+    "# tests/test_block_grad_gpu.py: per case and tensor, e_gpu = max |GPU - fp64|, e_ref = max |fp32 CPU autograd - fp64|, both in units of",
+    "# 2^-24 max|g64|; bound = 4 e_ref + 32; ratio = e_gpu / bound.  Forward outputs are held to the same bound.  The two gelu rows are pointwise:",
+    "# the worst point of the grid, e_gpu in units of 2^-24 |z| Phi (gelu) or 2^-24 (Phi + |z| phi) (gelu'), bound (2 z^2 + 32) of those units.",
+)
+
 
 @pytest.fixture(scope="module", autouse=True)
 def _table():
     yield
-    path = os.environ.get("M3R_BLOCK_GRAD_TABLE")
-    if _rows and path:
-        with open(path, "w") as f:
-            f.write("# tests/test_block_grad_gpu.py: per case and tensor, e_gpu = max |GPU - fp64|, e_ref = max |fp32 CPU autograd - fp64|, both in units of\n"
-                    "# 2^-24 max|g64|; bound = 4 e_ref + 32; ratio = e_gpu / bound.  Forward outputs are held to the same bound.  The two gelu rows are pointwise:\n"
-                    "# the worst point of the grid, e_gpu in units of 2^-24 |z| Phi (gelu) or 2^-24 (Phi + |z| phi) (gelu'), bound (2 z^2 + 32) of those units.\n")
-            f.write(f"{'case':<30}{'tensor':<18}{'max|g64|':>12}{'e_gpu':>10}{'e_ref':>10}{'ratio':>8}\n")
-            for r in _rows:
-                f.write(f"{r[0]:<30}{r[1]:<18}{r[2]:>12.4e}{r[3]:>10.2f}{r[4]:>10.2f}{r[5]:>8.3f}\n")
-            f.write(f"# worst ratio {max(r[5] for r in _rows):.3f}\n")
+    GP.write_table(os.environ.get("M3R_BLOCK_GRAD_TABLE"), _HEADER, _rows, (30, 18))
 
 
-def _compare(tag, got, g64, g32):
-    bad = []
-    for k in g64:
-        g = got[k].detach().cpu()
-        assert g.dtype == torch.float32 and g.shape == g64[k].shape, (tag, k, g.dtype, g.shape)
-        assert bool(torch.isfinite(g64[k]).all()) and bool(torch.isfinite(g).all()), (tag, k, "not finite")
-        m = float(g64[k].abs().max())
-        e_gpu = float((g.double() - g64[k]).abs().max())
-        e_ref = float((g32[k].double() - g64[k]).abs().max())
-        bound = 4 * e_ref + 32 * U * m
-        unit = U * m if m > 0 else 1.0
-        ratio = e_gpu / bound if bound > 0 else (0.0 if e_gpu == 0 else float("inf"))
-        _rows.append((tag, k, m, e_gpu / unit, e_ref / unit, ratio))
-        print(f"{tag} {k}: max|g64| {m:.4e} e_gpu {e_gpu / unit:.2f} e_ref {e_ref / unit:.2f} (units of 2^-24 max|g64|) e_gpu / bound {ratio:.3f}")
-        if not e_gpu <= bound:
-            bad.append((k, e_gpu, e_ref, bound))
-    assert not bad, (tag, bad)
+_compare = functools.partial(GP.compare, _rows)
 
 
 @functools.lru_cache(maxsize=None)

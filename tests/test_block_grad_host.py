@@ -167,7 +167,8 @@ def test_attn_sublayer_refuses_before_touching_anything(fn):
                        (dict(Wqkv=C.c_void_p(0x400008)), "aligned"), (dict(pos=C.c_void_p(0x900008)), "aligned")):
         rc, msg = _attn_call(fn, **over)
         assert rc != 0 and word in msg, (over, msg)
-    for views, word in ((((0, 6, 0, 6, 0, 0), (6, 5, 6, 4, 0, 0)), "reaches past"), (((0, 6, 0, 11, 0, 0),), "reaches past"), (((0, -6, 0, 6, 0, 0),), "negative")):
+    for views, word in ((((0, 6, 0, 6, 0, 0), (6, 5, 6, 4, 0, 0)), "reaches past"), (((0, 6, 0, 11, 0, 0),), "reaches past"), (((0, -6, 0, 6, 0, 0),), "negative"),
+                        (((0, 6, 0, 6, 3, 7),), "skip")):
         rc, msg = _attn_call(fn, views=views)
         assert rc != 0 and word in msg, (views, msg)
     rc, msg = _attn_call(fn)

@@ -23,11 +23,11 @@ import pytest
 import torch
 
 import decblock_ref as DR
+import grad_parity as GP
 from must3r_amd import _lib, train_attention as TA, train_block as TB, train_cross as TC
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-U = 2.0 ** -24
 CANARY = -7.25e11
 KBIAS = "cross_attn.projk.bias"
 _rows = []
@@ -54,39 +54,20 @@ CROSS = {
 # name -> D, heads, hidden, scenes, V, n, Nm, seed
 BLOCKS = {"d128": (128, 2, 512, 2, 2, 35, 70, 81), "d768": (768, 12, 3072, 1, 2, 96, 96, 82)}
 
+_HEADER = (
+    "# tests/test_cross_grad_gpu.py: per case and tensor, e_gpu = max |GPU - fp64|, e_ref = max |fp32 CPU autograd - fp64|, both in units of",
+    "# 2^-24 m; bound = 4 e_ref + 32; ratio = e_gpu / bound.  m = max|g64|, except for cross_attn.projk.bias where every key of a view carries the",
+    "# bias (true gradient zero): there m = the largest column 1-norm of the fp64 dK.  Forward outputs are held to the same bound.",
+)
+
 
 @pytest.fixture(scope="module", autouse=True)
 def _table():
     yield
-    path = os.environ.get("M3R_CROSS_GRAD_TABLE")
-    if _rows and path:
-        with open(path, "w") as f:
-            f.write("# tests/test_cross_grad_gpu.py: per case and tensor, e_gpu = max |GPU - fp64|, e_ref = max |fp32 CPU autograd - fp64|, both in units of\n"
-                    "# 2^-24 m; bound = 4 e_ref + 32; ratio = e_gpu / bound.  m = max|g64|, except for cross_attn.projk.bias where every key of a view carries the\n"
-                    "# bias (true gradient zero): there m = the largest column 1-norm of the fp64 dK.  Forward outputs are held to the same bound.\n")
-            f.write(f"{'case':<30}{'tensor':<28}{'m':>12}{'e_gpu':>10}{'e_ref':>10}{'ratio':>8}\n")
-            for r in _rows:
-                f.write(f"{r[0]:<30}{r[1]:<28}{r[2]:>12.4e}{r[3]:>10.2f}{r[4]:>10.2f}{r[5]:>8.3f}\n")
-            f.write(f"# worst ratio {max(r[5] for r in _rows):.3f}\n")
+    GP.write_table(os.environ.get("M3R_CROSS_GRAD_TABLE"), _HEADER, _rows, (30, 28), magnitude="m")
 
 
-def _compare(tag, got, g64, g32, mags=None):
-    bad = []
-    for k in g64:
-        g = got[k].detach().cpu()
-        assert g.dtype == torch.float32 and g.shape == g64[k].shape, (tag, k, g.dtype, g.shape)
-        assert bool(torch.isfinite(g64[k]).all()) and bool(torch.isfinite(g).all()), (tag, k, "not finite")
-        m = float(g64[k].abs().max()) if not (mags and k in mags) else mags[k]
-        e_gpu = float((g.double() - g64[k]).abs().max())
-        e_ref = float((g32[k].double() - g64[k]).abs().max())
-        bound = 4 * e_ref + 32 * U * m
-        unit = U * m if m > 0 else 1.0
-        ratio = e_gpu / bound if bound > 0 else (0.0 if e_gpu == 0 else float("inf"))
-        _rows.append((tag, k, m, e_gpu / unit, e_ref / unit, ratio))
-        print(f"{tag} {k}: m {m:.4e} e_gpu {e_gpu / unit:.2f} e_ref {e_ref / unit:.2f} (units of 2^-24 m) e_gpu / bound {ratio:.3f}")
-        if not e_gpu <= bound:
-            bad.append((k, e_gpu, e_ref, bound))
-    assert not bad, (tag, bad)
+_compare = functools.partial(GP.compare, _rows)
 
 
 @functools.lru_cache(maxsize=None)
