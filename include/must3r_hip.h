@@ -883,6 +883,44 @@ size_t must3r_hip_cross_sublayer_scratch_bytes(int M, int Rm, int D, int n_views
 int must3r_hip_cross_sublayer_forward(const must3r_hip_cross_sublayer_args* a, void* scratch, size_t scratch_bytes);
 int must3r_hip_cross_sublayer_grad(const must3r_hip_cross_sublayer_args* a, void* scratch, size_t scratch_bytes);
 
+/* ABI 21, additive.  Training forward and backward of what the reference's decoder does to the new tokens of all layers after a memory update
+ * (feedback_mechanism.py:39-53, decoder.py:325-330): the feedback offset is added to the tokens of every layer but the last and each layer's norm_y is
+ * applied, for all layers in one launch each way (the training counterpart of the grouped LayerNorm with add_groups of the inference path):
+ *   Y_l = LN_l(X_l + (l < add_layers ? offset : 0)) gamma_l + beta_l        l = 0 .. L - 1 <= 31; X_l, Y_l [R][D] fp32 contiguous; offset [R][D], NULL with add_layers 0
+ * gamma_l and beta_l are given for every layer, or for none: the reference's `raw` memory mode, the add alone.  D % 64 == 0, D <= 1024; pointers 16-byte aligned.
+ * The backward gives, from dY_l: dX_l; doffset = the sum over l < add_layers of dX_l, added in ascending l (zeros with add_layers 0); dgamma_l and dbeta_l.
+ * The per-layer pointers travel BY VALUE in the descriptor, and so does the stream (`stream`, a hipStream_t): all work goes to it, nothing waits on the host.
+ * Every output may be NULL, costs nothing then and is not written: a NULL y[l] skips the layer's forward; no dgamma and no dbeta at all, no column sums and no
+ * reduce launch; no doffset, nothing accumulated; nothing asked for, no launch.
+ * Determinism: no atomics, one writer per element; a row's Y, dX and doffset do not depend on the other rows (the same bits alone and in a batch); the column
+ * sums go through one partial per (layer, block of 16 rows) and a fixed-order reduce, the block count a function of R alone; repeated calls agree bit for bit.
+ * A layer without the add has the bits of must3r_hip_op_layernorm_f32 (one row routine, csrc/train_ln.hpp).  The backward's statistics are the forward's.
+ * Scratch (no device needed; 0 on a bad shape): feedback_prepare_scratch_bytes = 8 L ceil(R / 16) D rounded up to 256, the column-sum partials; the backward
+ * takes it where a dgamma or dbeta is asked for, and reads neither argument otherwise; the forward never does.
+ * Refused with an error before anything is read or launched: a NULL descriptor, L outside [1, 32], R <= 0, D not a multiple of 64 or above 1024, add_layers
+ * outside [0, L], add_layers > 0 without offset, a NULL x[l] (dy[l], in the backward), gamma without beta or for some layers only, dgamma / dbeta without gamma,
+ * pointers not 16-byte aligned, scratch NULL, misaligned or too small (a backward with column sums). */
+#define MUST3R_FEEDBACK_MAX_LAYERS 32
+typedef struct must3r_hip_feedback_prepare_args {
+    const float* x[MUST3R_FEEDBACK_MAX_LAYERS];
+    const float* gamma[MUST3R_FEEDBACK_MAX_LAYERS];
+    const float* beta[MUST3R_FEEDBACK_MAX_LAYERS];
+    const float* dy[MUST3R_FEEDBACK_MAX_LAYERS];     /* *_grad only */
+    float* y[MUST3R_FEEDBACK_MAX_LAYERS];            /* *_forward only, each optional */
+    float* dx[MUST3R_FEEDBACK_MAX_LAYERS];           /* *_grad, each optional */
+    float* dgamma[MUST3R_FEEDBACK_MAX_LAYERS];
+    float* dbeta[MUST3R_FEEDBACK_MAX_LAYERS];
+    const float* offset;
+    float* doffset;                                  /* *_grad, optional */
+    int32_t L, R, D, add_layers;
+    float eps;
+    int32_t reserved;
+    void* stream;                                    /* hipStream_t */
+} must3r_hip_feedback_prepare_args;
+size_t must3r_hip_feedback_prepare_scratch_bytes(int L, int R, int D);
+int must3r_hip_feedback_prepare_forward(const must3r_hip_feedback_prepare_args* a, void* scratch, size_t scratch_bytes);
+int must3r_hip_feedback_prepare_grad(const must3r_hip_feedback_prepare_args* a, void* scratch, size_t scratch_bytes);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

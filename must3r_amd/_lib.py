@@ -174,6 +174,17 @@ class CrossSublayerArgs(C.Structure):
                 ("eps", C.c_float), ("reserved", C.c_int32), ("stream", C.c_void_p)]
 
 
+FEEDBACK_MAX_LAYERS = 32
+
+
+class FeedbackPrepareArgs(C.Structure):
+    """must3r_hip_feedback_prepare_args: the per-layer pointers by value, the offset, (optional) outputs and the stream of the feedback add + ``norm_y`` of
+    all layers, forward / backward (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [(n, C.c_void_p * FEEDBACK_MAX_LAYERS) for n in ("x", "gamma", "beta", "dy", "y", "dx", "dgamma", "dbeta")] + [
+        ("offset", C.c_void_p), ("doffset", C.c_void_p), ("L", C.c_int32), ("R", C.c_int32), ("D", C.c_int32), ("add_layers", C.c_int32),
+        ("eps", C.c_float), ("reserved", C.c_int32), ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -275,6 +286,9 @@ PROTOTYPES = {
     "must3r_hip_cross_sublayer_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
     "must3r_hip_cross_sublayer_forward": (i32, [P(CrossSublayerArgs), vp, sz]),
     "must3r_hip_cross_sublayer_grad": (i32, [P(CrossSublayerArgs), vp, sz]),
+    "must3r_hip_feedback_prepare_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_feedback_prepare_forward": (i32, [P(FeedbackPrepareArgs), vp, sz]),
+    "must3r_hip_feedback_prepare_grad": (i32, [P(FeedbackPrepareArgs), vp, sz]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

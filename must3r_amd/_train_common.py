@@ -1,4 +1,4 @@
-"""What the training modules (``train_head``, ``train_attention``, ``train_block``, ``train_cross``) share on the host: the checks that a tensor is on the GPU
+"""What the training modules (``train_head``, ``train_attention``, ``train_block``, ``train_cross``, ``train_decoder``) share on the host: the checks that a tensor is on the GPU
 and has the expected shape, the fp32 views handed to the library, scratch and output allocation, the one calling pattern of the sublayer entry points, and
 the two parameter holders.  Everything here is private to the package."""
 import ctypes as C

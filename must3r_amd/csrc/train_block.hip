@@ -23,6 +23,7 @@
 #include "abi.hpp"
 #include "common.hpp"
 #include "train_common.hpp"
+#include "train_ln.hpp"
 
 namespace m3r {
 
@@ -131,38 +132,17 @@ __global__ void __launch_bounds__(256) linear_fwd_f32(LinArgs p) {
         }
 }
 
-// one wave per row, the row read once with 16-byte loads and kept in registers (D % 64 == 0, D <= 1024: four float4 per lane); two-pass statistics
+// one wave per row, the row read once with 16-byte loads and kept in registers (D % 64 == 0, D <= 1024: four float4 per lane); two-pass statistics.
+// The row routine is train_ln.hpp's, shared with the feedback kernels of train_decoder.hip.
 __global__ void __launch_bounds__(256) ln_fwd_f32(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                   float* __restrict__ y, int M, int D, float eps) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
-    const float* xr = x + (size_t)row * D;
     f32x4 v[4];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = (j * 64 + lane) * 4;
-        v[j] = c < D ? *reinterpret_cast<const f32x4*>(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-    }
-    const float mu = wave_sum_dpp(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if ((j * 64 + lane) * 4 < D) {
-            const f32x4 d = v[j] - mu;
-            q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-        }
-    const float rstd = 1.0f / sqrtf(wave_sum_dpp(q) / (float)D + eps);
-    float* yr = y + (size_t)row * D;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = (j * 64 + lane) * 4;
-        if (c < D) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c), b = *reinterpret_cast<const f32x4*>(beta + c);
-            *reinterpret_cast<f32x4*>(yr + c) = (v[j] - mu) * rstd * g + b;
-        }
-    }
+    float mu, rstd;
+    ln_row_load(x + (size_t)row * D, lane, D, v);
+    ln_row_stats(v, lane, D, eps, mu, rstd);
+    ln_row_store(v, mu, rstd, gamma, beta, y + (size_t)row * D, lane, D);
 }
 
 // dz = dh gelu'(z) over [M][N], N % 4 == 0; dz may alias dh (each float4 is read before it is written, by the thread that writes it)
