@@ -752,6 +752,34 @@ int must3r_hip_attn_train_groups(const int32_t* views_host, int n_views);
 int must3r_hip_attn_forward_f32(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream);
 int must3r_hip_attn_grad(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ABI 21, additive.  Key masks in the attention core of ABI 20 (memory dropout: the random subset of memory rows the reference's training class hides from a view,
+ * decoder.py:388-433, blocks/dropout.py).  The descriptor embeds the ABI 20 one as its first member; besides the prefix nk and the interval [skip_lo, skip_hi) a
+ * view may name one row of a packed bit matrix:
+ *   key j of a view is valid when j < nk, j is not in [skip_lo, skip_hi) and, if view_mask[view] = r >= 0, bit j % 32 of word mask_bits[r][j / 32] is 1.
+ * Everything else is ABI 20: the formulas, the key groups, the order of additions, and the rule for a query row without a valid key (O = 0, lse = -inf, nothing
+ * into dK / dV, dQ = 0).  mask_bits is a DEVICE array uint32 [mask_rows][mask_ld], 8-byte aligned, mask_ld even (the 64 bits of a key tile are one aligned 8-byte
+ * load) with 32 mask_ld >= nk for every view that names a row; bits at or past a view's nk are ignored.  view_mask is a HOST array int32 [core.n_views], -1: no
+ * mask; it is uploaded with the view table, in the same copy through the same pinned ring.  Rows are shared freely among views, scenes and heads (the reference
+ * draws one mask per view position of a call and uses it for every scene, layer and head), so mask_rows is about the number of views of a call.
+ * A (view, key tile) pair whose 64 bits are all zero is skipped like a tile wholly inside the skip range: no K / V tile is fetched for it in the forward and the dQ
+ * walk, no Q / dO tile in the dK / dV walk.  The masked kernels are separate instantiations; mask_bits == NULL with view_mask == NULL launches the unmasked ones,
+ * the bits of must3r_hip_attn_forward_f32 / must3r_hip_attn_grad.  The stream travels in the descriptor (`stream`, a hipStream_t): all work goes to it, the
+ * uploaded tables included, and no call waits for it on the host.  No atomics; repeated calls agree bit for bit.
+ * Scratch (must3r_hip_attn_masked_scratch_bytes; no device needed; 0 on a bad shape): that of ABI 20 plus n_views int32 rounded up to 256 bytes, placed behind
+ * the view lists: [views | groups | per-group view lists | mask rows | lse | delta].  It is enough for a call without masks too.
+ * Refused with an error before anything is read or launched: everything the ABI 20 calls refuse; mask_bits without view_mask or the reverse; mask_ld odd or <= 0;
+ * mask_rows < 0; a view_mask entry outside [-1, mask_rows); 32 mask_ld below the nk of a view that names a row; mask_bits not 8-byte aligned. */
+typedef struct must3r_hip_attn_masked_args {
+    must3r_hip_attn_train_args core;
+    const uint32_t* mask_bits;         /* DEVICE uint32 [mask_rows][mask_ld] */
+    const int32_t* view_mask;          /* HOST int32 [core.n_views], -1: none */
+    int32_t mask_rows, mask_ld;
+    void* stream;                      /* hipStream_t */
+} must3r_hip_attn_masked_args;
+size_t must3r_hip_attn_masked_scratch_bytes(int n_views, int total_q_rows, int total_kv_rows, int heads);
+int must3r_hip_attn_masked_forward(const must3r_hip_attn_masked_args* a, void* scratch, size_t scratch_bytes);
+int must3r_hip_attn_masked_grad(const must3r_hip_attn_masked_args* a, void* scratch, size_t scratch_bytes);
+
 /* ABI 21.  Training forward and backward of the two residual sublayers of the reference's Block (blocks/layers.py:36-54; also two of the three sublayers of
  * CachedDecoderBlock), fp32, stateless, no atomics: repeated calls agree bit for bit and a row of a row-wise output does not depend on the other rows of the call.
  *   MLP sublayer        y^ = LN(x) gamma + beta;  z = y^ W1^T + b1;  h = gelu(z);  out = x + h W2^T + b2                        W1 [hidden][D], W2 [D][hidden]
@@ -882,6 +910,22 @@ typedef struct must3r_hip_cross_sublayer_args {
 size_t must3r_hip_cross_sublayer_scratch_bytes(int M, int Rm, int D, int n_views, int kv_ready);
 int must3r_hip_cross_sublayer_forward(const must3r_hip_cross_sublayer_args* a, void* scratch, size_t scratch_bytes);
 int must3r_hip_cross_sublayer_grad(const must3r_hip_cross_sublayer_args* a, void* scratch, size_t scratch_bytes);
+
+/* ABI 21, additive.  The cross-attention sublayer above with key masks handed to its attention core (must3r_hip_attn_masked_*): mask_bits, view_mask, mask_rows
+ * and mask_ld as there, the key rows of the masks index mem like the kv rows of the table.  Everything else is must3r_hip_cross_sublayer_*: the operand forms, the
+ * `kv` mode, the segmented dmem, the optional outputs, coverage, determinism and the stream in core.stream.  A memory row that every view of its group has
+ * dropped gets exact zeros in dK | dV, hence dmem = 0 in the `kv` mode and no contribution to dWk, dWv and dmem otherwise.  mask_bits == NULL with view_mask ==
+ * NULL is must3r_hip_cross_sublayer_forward / _grad, bit for bit.  Scratch: cross_sublayer_scratch_bytes with attn_masked_scratch_bytes in the place of
+ * attn_train_scratch_bytes.  Refused before anything is read or launched: what the unmasked calls refuse and what must3r_hip_attn_masked_* refuses of the masks. */
+typedef struct must3r_hip_cross_sublayer_masked_args {
+    must3r_hip_cross_sublayer_args core;
+    const uint32_t* mask_bits;         /* DEVICE uint32 [mask_rows][mask_ld] */
+    const int32_t* view_mask;          /* HOST int32 [core.n_views], -1: none */
+    int32_t mask_rows, mask_ld;
+} must3r_hip_cross_sublayer_masked_args;
+size_t must3r_hip_cross_sublayer_masked_scratch_bytes(int M, int Rm, int D, int n_views, int kv_ready);
+int must3r_hip_cross_sublayer_masked_forward(const must3r_hip_cross_sublayer_masked_args* a, void* scratch, size_t scratch_bytes);
+int must3r_hip_cross_sublayer_masked_grad(const must3r_hip_cross_sublayer_masked_args* a, void* scratch, size_t scratch_bytes);
 
 /* ABI 21, additive.  Training forward and backward of what the reference's decoder does to the new tokens of all layers after a memory update
  * (feedback_mechanism.py:39-53, decoder.py:325-330): the feedback offset is added to the tokens of every layer but the last and each layer's norm_y is

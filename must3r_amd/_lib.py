@@ -144,6 +144,13 @@ class AttnTrainArgs(C.Structure):
                 ("ldo", C.c_int32), ("lddq", C.c_int32), ("lddk", C.c_int32), ("lddv", C.c_int32)]
 
 
+class AttnMaskedArgs(C.Structure):
+    """must3r_hip_attn_masked_args: the ABI 20 descriptor, the packed key masks (DEVICE), each view's mask row (HOST) and the stream of the masked attention
+    training forward / backward (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("core", AttnTrainArgs), ("mask_bits", C.c_void_p), ("view_mask", C.c_void_p), ("mask_rows", C.c_int32), ("mask_ld", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
 class MlpSublayerArgs(C.Structure):
     """must3r_hip_mlp_sublayer_args: inputs and (optional) outputs of the MLP sublayer's training forward / backward (include/must3r_hip.h, ABI 21)."""
     _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
@@ -172,6 +179,12 @@ class CrossSublayerArgs(C.Structure):
                 ("dWk", C.c_void_p), ("dbk", C.c_void_p), ("dWv", C.c_void_p), ("dbv", C.c_void_p), ("dWproj", C.c_void_p), ("dbproj", C.c_void_p),
                 ("M", C.c_int32), ("Rm", C.c_int32), ("D", C.c_int32), ("n_views", C.c_int32), ("ldmem", C.c_int32), ("lddmem", C.c_int32),
                 ("eps", C.c_float), ("reserved", C.c_int32), ("stream", C.c_void_p)]
+
+
+class CrossSublayerMaskedArgs(C.Structure):
+    """must3r_hip_cross_sublayer_masked_args: the cross-attention sublayer's descriptor and the key masks handed to its attention core (include/must3r_hip.h,
+    ABI 21, additive)."""
+    _fields_ = [("core", CrossSublayerArgs), ("mask_bits", C.c_void_p), ("view_mask", C.c_void_p), ("mask_rows", C.c_int32), ("mask_ld", C.c_int32)]
 
 
 FEEDBACK_MAX_LAYERS = 32
@@ -271,6 +284,9 @@ PROTOTYPES = {
     "must3r_hip_attn_train_groups": (i32, [vp, i32]),
     "must3r_hip_attn_forward_f32": (i32, [P(AttnTrainArgs), vp, sz, vp]),
     "must3r_hip_attn_grad": (i32, [P(AttnTrainArgs), vp, sz, vp]),
+    "must3r_hip_attn_masked_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_attn_masked_forward": (i32, [P(AttnMaskedArgs), vp, sz]),
+    "must3r_hip_attn_masked_grad": (i32, [P(AttnMaskedArgs), vp, sz]),
     "must3r_hip_op_linear_f32": (i32, [i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
     "must3r_hip_op_layernorm_f32": (i32, [vp, vp, vp, vp, i32, i32, fp, vp]),
     "must3r_hip_op_gelu_f32": (i32, [vp, vp, vp, C.c_longlong, vp]),
@@ -286,6 +302,9 @@ PROTOTYPES = {
     "must3r_hip_cross_sublayer_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
     "must3r_hip_cross_sublayer_forward": (i32, [P(CrossSublayerArgs), vp, sz]),
     "must3r_hip_cross_sublayer_grad": (i32, [P(CrossSublayerArgs), vp, sz]),
+    "must3r_hip_cross_sublayer_masked_scratch_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "must3r_hip_cross_sublayer_masked_forward": (i32, [P(CrossSublayerMaskedArgs), vp, sz]),
+    "must3r_hip_cross_sublayer_masked_grad": (i32, [P(CrossSublayerMaskedArgs), vp, sz]),
     "must3r_hip_feedback_prepare_scratch_bytes": (sz, [i32, i32, i32]),
     "must3r_hip_feedback_prepare_forward": (i32, [P(FeedbackPrepareArgs), vp, sz]),
     "must3r_hip_feedback_prepare_grad": (i32, [P(FeedbackPrepareArgs), vp, sz]),

@@ -8,6 +8,10 @@
 //   dQ_i = s sum_j dS_ij k_j              dK_j  = s sum_i dS_ij q_i
 //
 // A query row without a valid key has O = 0, contributes nothing to dK / dV and gets dQ = 0 (as the inference kernels define it).
+// Key masks (the must3r_hip_attn_masked_* entry points; memory dropout): a view may also name a row of a packed bit matrix uint32 [mask_rows][mask_ld]; key j
+// is then valid only if bit j % 32 of word j / 32 of that row is set.  The three kernels are templates on MASK: the unmasked instantiations are the code they
+// were, the masked ones read a view's 64 bits of a key tile as one 8-byte load (mask_ld is even), test them on the key index a lane already holds, and skip
+// a (view, key tile) pair whose bits are all zero exactly like a tile wholly inside the skip range.
 // fp32 operands on v_mfma_f32_16x16x4_f32 (upstream gradients of a mean-reduced loss are of order 1e-8, below fp16's range); exp2f with log2(e) folded into the
 // scale.  The forward saves nothing but its inputs, the backward recomputes S:
 //
@@ -52,6 +56,8 @@ struct TaArgs {
     float* lse2; float* delta;   // [rows][heads], scratch of the backward
     float* dQ; float* dK; float* dV;
     int lddq, lddk, lddv;
+    // MASK instantiations only: the packed key masks [mask_rows][mask_ld], and per view of the table its row (-1: none)
+    const uint32_t* mask; const int* vmask; int mask_ld;
 };
 
 // rows [0, rows_valid) of a [.][64] slab at src (row stride ld) -> registers (4 float4 per thread), the rest zero; then registers -> dst [64][TA_LD].
@@ -124,6 +130,34 @@ __device__ __forceinline__ int ta_next_tile(const AttnView& v, int k0) {
     return k0;
 }
 
+// MASK: the mask row of a view of the table, nullptr where it names none
+template <bool MASK>
+__device__ __forceinline__ const uint32_t* ta_mask_row(const TaArgs& a, int view) {
+    if (!MASK) return nullptr;
+    const int r = a.vmask[view];
+    return r >= 0 ? a.mask + (size_t)r * a.mask_ld : nullptr;
+}
+// bit t: key k0 + t of the tile at k0 < nk passes the mask row (all ones without a row); the bits of keys at or past nk are cleared.  k0 is a multiple of 64 and
+// 32 mask_ld >= nk with mask_ld even, so that the two words are inside the row and 8-byte aligned.
+__device__ __forceinline__ uint64_t ta_tile_bits(const uint32_t* mrow, int k0, int nk) {
+    if (!mrow) return ~0ull;
+    const uint2 w = *reinterpret_cast<const uint2*>(mrow + (k0 >> 5));
+    const uint64_t b = (uint64_t)w.y << 32 | w.x;
+    const int left = nk - k0;
+    return left >= 64 ? b : b & ((1ull << left) - 1);
+}
+template <bool MASK>
+__device__ __forceinline__ bool ta_tile_skipped_m(const AttnView& v, int k0, const uint32_t* mrow) {
+    if (ta_tile_skipped(v, k0)) return true;
+    return MASK && ta_tile_bits(mrow, k0, v.nk) == 0;
+}
+template <bool MASK>
+__device__ __forceinline__ int ta_next_tile_m(const AttnView& v, int k0, const uint32_t* mrow) {
+    while (k0 < v.nk && ta_tile_skipped_m<MASK>(v, k0, mrow)) k0 += TA_T;
+    return k0;
+}
+
+template <bool MASK>
 __global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
     __shared__ __attribute__((aligned(16))) float Ks[TA_T * TA_LD];
     __shared__ __attribute__((aligned(16))) float Vs[TA_T * TA_LD];
@@ -131,6 +165,7 @@ __global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
     const AttnView v = a.views[blockIdx.z];
     const int q0 = blockIdx.x * TA_T, h = blockIdx.y;
     if (q0 >= v.nq) return;
+    const uint32_t* mrow = ta_mask_row<MASK>(a, blockIdx.z);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fk = lane >> 4;
     const float inf = __builtin_inff();
     float qa[16];
@@ -149,14 +184,15 @@ __global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
         ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
         ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
     };
-    int k0 = ta_next_tile(v, 0);
+    int k0 = ta_next_tile_m<MASK>(v, 0, mrow);
     if (k0 < v.nk) fetch(k0);
     while (k0 < v.nk) {
         __syncthreads();
         ta_put_tile(Ks, rk, tid);
         ta_put_tile(Vs, rv, tid);
         __syncthreads();
-        const int k_next = ta_next_tile(v, k0 + TA_T);
+        const int k_next = ta_next_tile_m<MASK>(v, k0 + TA_T, mrow);
+        const uint64_t mb = MASK ? ta_tile_bits(mrow, k0, v.nk) : ~0ull;
         if (k_next < v.nk) fetch(k_next);
         f32x4 s[4];
 #pragma unroll
@@ -164,7 +200,7 @@ __global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
         ta_mm_reg<true>(s, qa, Ks, fr, fk);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const bool ok = ta_valid(v, k0 + j * 16 + fr);
+            const bool ok = ta_valid(v, k0 + j * 16 + fr) && (!MASK || (mb >> (j * 16 + fr) & 1));
 #pragma unroll
             for (int r = 0; r < 4; ++r) s[j][r] = ok ? s[j][r] * TA_C : -inf;
         }
@@ -214,6 +250,7 @@ __global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
     }
 }
 
+template <bool MASK>
 __global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
     __shared__ __attribute__((aligned(16))) float Ks[TA_T * TA_LD];
     __shared__ __attribute__((aligned(16))) float Vs[TA_T * TA_LD];
@@ -221,6 +258,7 @@ __global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
     const AttnView v = a.views[blockIdx.z];
     const int q0 = blockIdx.x * TA_T, h = blockIdx.y;
     if (q0 >= v.nq) return;
+    const uint32_t* mrow = ta_mask_row<MASK>(a, blockIdx.z);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fk = lane >> 4;
     const float inf = __builtin_inff();
     float qa[16], da[16];
@@ -245,14 +283,15 @@ __global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
         ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
         ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
     };
-    int k0 = ta_next_tile(v, 0);
+    int k0 = ta_next_tile_m<MASK>(v, 0, mrow);
     if (k0 < v.nk) fetch(k0);
     while (k0 < v.nk) {
         __syncthreads();
         ta_put_tile(Ks, rk, tid);
         ta_put_tile(Vs, rv, tid);
         __syncthreads();
-        const int k_next = ta_next_tile(v, k0 + TA_T);
+        const int k_next = ta_next_tile_m<MASK>(v, k0 + TA_T, mrow);
+        const uint64_t mb = MASK ? ta_tile_bits(mrow, k0, v.nk) : ~0ull;
         if (k_next < v.nk) fetch(k_next);
         f32x4 s[4], dp[4];
 #pragma unroll
@@ -261,7 +300,7 @@ __global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
         ta_mm_reg<true>(dp, da, Vs, fr, fk);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const bool ok = ta_valid(v, k0 + j * 16 + fr);
+            const bool ok = ta_valid(v, k0 + j * 16 + fr) && (!MASK || (mb >> (j * 16 + fr) & 1));
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float p = ok ? exp2f(s[j][r] * TA_C - lr[r]) : 0.f;
@@ -282,6 +321,7 @@ __global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
     }
 }
 
+template <bool MASK>
 __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
     __shared__ __attribute__((aligned(16))) float Qs[TA_T * TA_LD];
     __shared__ __attribute__((aligned(16))) float Ds[TA_T * TA_LD];
@@ -301,12 +341,18 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) { dk[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     // the walk over (view in table order, query tile in row order), one step ahead of the products: vi == g.count at the end
-    auto advance = [&](int& vi, int& q0, AttnView& v) {
+    // mb: the view's mask bits of this key tile (MASK); a view that dropped the whole tile is passed over before any of its Q / dO tiles is fetched
+    auto advance = [&](int& vi, int& q0, AttnView& v, uint64_t& mb) {
         if (vi >= 0 && q0 + TA_T < v.nq) { q0 += TA_T; return; }
         q0 = 0;
         for (++vi; vi < g.count; ++vi) {
-            v = a.views[a.list[g.first + vi]];
-            if (v.nq > 0 && !ta_tile_skipped(v, k0)) return;
+            const int id = a.list[g.first + vi];
+            v = a.views[id];
+            if (v.nq > 0 && !ta_tile_skipped(v, k0)) {
+                if (!MASK) return;
+                mb = ta_tile_bits(ta_mask_row<MASK>(a, id), k0, v.nk);
+                if (mb) return;
+            }
         }
     };
     f32x4 rq[4], rd[4];
@@ -316,7 +362,8 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
     };
     int vi = -1, q0 = 0;
     AttnView v{};
-    advance(vi, q0, v);
+    uint64_t mb = ~0ull;
+    advance(vi, q0, v, mb);
     if (vi < g.count) fetch(v, q0);
     while (vi < g.count) {
         __syncthreads();
@@ -325,11 +372,12 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
         __syncthreads();
         int vi_next = vi, q_next = q0;
         AttnView v_next = v;
-        advance(vi_next, q_next, v_next);
+        uint64_t mb_next = mb;
+        advance(vi_next, q_next, v_next, mb_next);
         if (vi_next < g.count) fetch(v_next, q_next);
         bool kok[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) kok[r] = ta_valid(v, k0 + w * 16 + fk * 4 + r);
+        for (int r = 0; r < 4; ++r) kok[r] = ta_valid(v, k0 + w * 16 + fk * 4 + r) && (!MASK || (mb >> (w * 16 + fk * 4 + r) & 1));
         float lc[4], dc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -358,7 +406,7 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
         ta_stage(Ps + w * 16 * TA_LD, dpt, fr, fk);
         __syncthreads();
         ta_mm_lds(dk, Ps + w * 16 * TA_LD, Qs, fr, fk);
-        vi = vi_next; q0 = q_next; v = v_next;
+        vi = vi_next; q0 = q_next; v = v_next; mb = mb_next;
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -442,20 +490,25 @@ static const char* ta_plan(const int32_t* views, int n, bool want_groups, TaPlan
     return nullptr;
 }
 
-// scratch: [views n x 6 int32 | groups n x 4 int32 | list n int32 | lse2 rows x heads fp32 | delta rows x heads fp32], each part a multiple of 256 bytes
-struct TaLayout { size_t views, groups, list, tables_bytes, lse2, delta, total; };   // tables_bytes: the three tables, one upload
-static TaLayout ta_layout(int n, long long q_rows, int heads) {
+// scratch: [views n x 6 int32 | groups n x 4 int32 | list n int32 | (masked: mask rows n int32) | lse2 rows x heads fp32 | delta rows x heads fp32], each part a
+// multiple of 256 bytes
+struct TaLayout { size_t views, groups, list, vmask, tables_bytes, lse2, delta, total; };   // tables_bytes: the tables, one upload
+static TaLayout ta_layout(int n, long long q_rows, int heads, bool masked = false) {
     TaLayout L{};
     ScratchCursor c;
     L.views = c.take((size_t)n * 24);
     L.groups = c.take((size_t)n * 16);
     L.list = c.take((size_t)n * 4);
+    L.vmask = c.take(masked ? (size_t)n * 4 : 0);
     L.tables_bytes = c.off;
     L.lse2 = c.take((size_t)q_rows * heads * 4);
     L.delta = c.take((size_t)q_rows * heads * 4);
     L.total = c.off;
     return L;
 }
+
+// the key masks of a call: nullptr bits, the unmasked call
+struct TaMask { const uint32_t* bits; const int32_t* view_mask; int rows, ld; };
 
 // The tables travel through a ring of pinned buffers per calling thread (as resample's, image.hip); a slot's event says when the copy out of it has left it, and
 // the slot is reused only then.  With ONE buffer the second upload of a call waited for the first, which is queued behind everything the stream still has to do:
@@ -469,8 +522,8 @@ constexpr int kTaPinSlots = 4;
 static thread_local TaPin ta_pins[kTaPinSlots];
 static thread_local int ta_pin_next = 0;
 
-static int ta_upload(const TaPlan& P, const int32_t* views, int n, bool want_groups, char* scratch, hipStream_t s, const char* who) {
-    const TaLayout L = ta_layout(n, 0, 0);
+static int ta_upload(const TaPlan& P, const int32_t* views, int n, bool want_groups, const int32_t* view_mask, char* scratch, hipStream_t s, const char* who) {
+    const TaLayout L = ta_layout(n, 0, 0, view_mask != nullptr);
     const size_t bytes = L.tables_bytes;
     TaPin& pin = ta_pins[ta_pin_next];
     ta_pin_next = (ta_pin_next + 1) % kTaPinSlots;
@@ -492,6 +545,7 @@ static int ta_upload(const TaPlan& P, const int32_t* views, int n, bool want_gro
         memcpy(h + L.groups, P.groups.data(), P.groups.size() * sizeof(TaGroup));
         memcpy(h + L.list, P.list.data(), (size_t)n * 4);
     }
+    if (view_mask) memcpy(h + L.vmask, view_mask, (size_t)n * 4);
     if (hipMemcpyAsync(scratch, h, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return fail("%s: the table upload failed", who);
     if (hipEventCreateWithFlags(&pin.ev, hipEventDisableTiming) != hipSuccess) { pin.ev = nullptr; return fail("%s: no event", who); }
     if (hipEventRecord(pin.ev, s) != hipSuccess) return fail("%s: no event", who);
@@ -514,28 +568,106 @@ static const char* ta_args_error(const must3r_hip_attn_train_args* a, bool grad)
     return nullptr;
 }
 
-static TaArgs ta_kernel_args(const must3r_hip_attn_train_args* a, const TaPlan& P, char* scratch) {
+// nullptr, or why the key masks of a call are refused; the table has passed ta_plan.  Nothing is read through mask_bits.
+static const char* ta_mask_error(const TaMask& m, const int32_t* views, int n) {
+    if (!m.bits != !m.view_mask) return "mask_bits and view_mask come together (both NULL: no masks)";
+    if (!m.bits) return nullptr;
+    if (m.ld <= 0 || m.ld % 2) return "mask_ld must be positive and even";
+    if (m.rows < 0) return "mask_rows must not be negative";
+    if ((size_t)m.bits & 7) return "mask_bits must be 8-byte aligned";
+    for (int i = 0; i < n; ++i) {
+        const int r = m.view_mask[i];
+        if (r < -1 || r >= m.rows) return "a view_mask entry outside [-1, mask_rows)";
+        if (r >= 0 && 32LL * m.ld < views[6 * (size_t)i + 3]) return "a mask row is shorter than the nk of a view that names it (32 mask_ld < nk)";
+    }
+    return nullptr;
+}
+
+static TaArgs ta_kernel_args(const must3r_hip_attn_train_args* a, const TaPlan& P, const TaMask& m, char* scratch) {
     TaArgs k{};
     k.Q = a->q; k.K = a->k; k.V = a->v; k.dO = a->dO;
     k.ldq = a->ldq; k.ldk = a->ldk; k.ldv = a->ldv; k.lddo = a->lddo; k.heads = a->heads;
-    const TaLayout L = ta_layout(a->n_views, P.total_q_rows, a->heads);
+    const TaLayout L = ta_layout(a->n_views, P.total_q_rows, a->heads, m.bits != nullptr);
     k.views = reinterpret_cast<const AttnView*>(scratch + L.views);
     k.groups = reinterpret_cast<const TaGroup*>(scratch + L.groups);
     k.list = reinterpret_cast<const int*>(scratch + L.list);
     k.lse2 = reinterpret_cast<float*>(scratch + L.lse2);
     k.delta = reinterpret_cast<float*>(scratch + L.delta);
+    if (m.bits) { k.mask = m.bits; k.vmask = reinterpret_cast<const int*>(scratch + L.vmask); k.mask_ld = m.ld; }
     return k;
+}
+
+// the two entry points of each kind, behind their argument checks: m.bits == nullptr launches the unmasked instantiations over the unmasked scratch layout
+static int ta_forward(const char* who, const must3r_hip_attn_train_args* a, const TaMask& m, void* scratch, size_t scratch_bytes, hipStream_t s) {
+    if (const char* e = ta_args_error(a, false)) return fail("%s: %s", who, e);
+    if (a->heads > 65535) return fail("%s: more than 65535 heads", who);
+    TaPlan P;
+    if (const char* e = ta_plan(a->views, a->n_views, false, P)) return fail("%s: %s", who, e);
+    if (const char* e = ta_mask_error(m, a->views, a->n_views)) return fail("%s: %s", who, e);
+    const bool masked = m.bits != nullptr;
+    if (!scratch || misaligned(scratch) || scratch_bytes < ta_layout(a->n_views, P.total_q_rows, a->heads, masked).total) return fail("%s: scratch too small", who);
+    if (P.max_nq == 0) return 0;
+    if (ta_upload(P, a->views, a->n_views, false, m.view_mask, reinterpret_cast<char*>(scratch), s, who)) return 1;
+    TaArgs k = ta_kernel_args(a, P, m, reinterpret_cast<char*>(scratch));
+    k.dO = nullptr; k.lse2 = nullptr; k.delta = nullptr;
+    k.O = a->O; k.ldo = a->ldo; k.lse = a->lse;
+    const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views);
+    if (masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<true>), qgrid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<false>), qgrid, dim3(256), 0, s, k);
+    if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
+    return 0;
+}
+
+static int ta_grad(const char* who, const must3r_hip_attn_train_args* a, const TaMask& m, void* scratch, size_t scratch_bytes, hipStream_t s) {
+    if (const char* e = ta_args_error(a, true)) return fail("%s: %s", who, e);
+    if (a->heads > 65535) return fail("%s: more than 65535 heads", who);
+    TaPlan P;
+    if (const char* e = ta_plan(a->views, a->n_views, true, P)) return fail("%s: %s", who, e);
+    if (const char* e = ta_mask_error(m, a->views, a->n_views)) return fail("%s: %s", who, e);
+    const bool masked = m.bits != nullptr;
+    if (!scratch || misaligned(scratch) || scratch_bytes < ta_layout(a->n_views, P.total_q_rows, a->heads, masked).total) return fail("%s: scratch too small", who);
+    const bool want_kv = a->dK || a->dV;
+    if (!a->dQ && !want_kv) return 0;
+    if (ta_upload(P, a->views, a->n_views, true, m.view_mask, reinterpret_cast<char*>(scratch), s, who)) return 1;
+    TaArgs k = ta_kernel_args(a, P, m, reinterpret_cast<char*>(scratch));
+    k.dQ = a->dQ; k.dK = a->dK; k.dV = a->dV; k.lddq = a->lddq; k.lddk = a->lddk; k.lddv = a->lddv;
+    const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views), kgrid((P.max_extent + TA_T - 1) / TA_T, a->heads, (unsigned)P.groups.size());
+    const bool run_q = P.max_nq > 0, run_kv = want_kv && P.max_extent > 0;
+    // lse2 and delta into scratch, then dK | dV, then dQ
+    if (masked) {
+        if (run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<true>), qgrid, dim3(256), 0, s, k);
+        if (run_kv) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dkv_f32<true>), kgrid, dim3(256), 0, s, k);
+        if (a->dQ && run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dq_f32<true>), qgrid, dim3(256), 0, s, k);
+    } else {
+        if (run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<false>), qgrid, dim3(256), 0, s, k);
+        if (run_kv) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dkv_f32<false>), kgrid, dim3(256), 0, s, k);
+        if (a->dQ && run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dq_f32<false>), qgrid, dim3(256), 0, s, k);
+    }
+    if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
+    return 0;
 }
 
 }  // namespace m3r
 using namespace m3r;
 
+static bool ta_scratch_shape_ok(int n_views, int total_q_rows, int total_kv_rows, int heads) {
+    return !(n_views <= 0 || n_views > 65535 || total_q_rows < 0 || total_kv_rows < 0 || heads <= 0 || heads > 65535);
+}
+
 extern "C" size_t must3r_hip_attn_train_scratch_bytes(int n_views, int total_q_rows, int total_kv_rows, int heads) {
-    if (n_views <= 0 || n_views > 65535 || total_q_rows < 0 || total_kv_rows < 0 || heads <= 0 || heads > 65535) {
+    if (!ta_scratch_shape_ok(n_views, total_q_rows, total_kv_rows, heads)) {
         fail("attn_train_scratch_bytes: n_views in [1, 65535], non-negative row counts and heads in [1, 65535] are required");
         return 0;
     }
     return ta_layout(n_views, total_q_rows, heads).total;
+}
+
+extern "C" size_t must3r_hip_attn_masked_scratch_bytes(int n_views, int total_q_rows, int total_kv_rows, int heads) {
+    if (!ta_scratch_shape_ok(n_views, total_q_rows, total_kv_rows, heads)) {
+        fail("attn_masked_scratch_bytes: n_views in [1, 65535], non-negative row counts and heads in [1, 65535] are required");
+        return 0;
+    }
+    return ta_layout(n_views, total_q_rows, heads, true).total;
 }
 
 extern "C" int must3r_hip_attn_train_groups(const int32_t* views_host, int n_views) {
@@ -546,40 +678,22 @@ extern "C" int must3r_hip_attn_train_groups(const int32_t* views_host, int n_vie
 
 extern "C" int must3r_hip_attn_forward_f32(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream) {
     if (!a) return fail("attn_forward_f32: null argument");
-    if (const char* e = ta_args_error(a, false)) return fail("attn_forward_f32: %s", e);
-    if (a->heads > 65535) return fail("attn_forward_f32: more than 65535 heads");
-    TaPlan P;
-    if (const char* e = ta_plan(a->views, a->n_views, false, P)) return fail("attn_forward_f32: %s", e);
-    if (!scratch || misaligned(scratch) || scratch_bytes < ta_layout(a->n_views, P.total_q_rows, a->heads).total) return fail("attn_forward_f32: scratch too small");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (P.max_nq == 0) return 0;
-    if (ta_upload(P, a->views, a->n_views, false, reinterpret_cast<char*>(scratch), s, "attn_forward_f32")) return 1;
-    TaArgs k = ta_kernel_args(a, P, reinterpret_cast<char*>(scratch));
-    k.dO = nullptr; k.lse2 = nullptr; k.delta = nullptr;
-    k.O = a->O; k.ldo = a->ldo; k.lse = a->lse;
-    hipLaunchKernelGGL(attn_fwd_f32, dim3((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views), dim3(256), 0, s, k);
-    if (hipGetLastError() != hipSuccess) return fail("attn_forward_f32: launch failed");
-    return 0;
+    return ta_forward("attn_forward_f32", a, TaMask{}, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int must3r_hip_attn_grad(const must3r_hip_attn_train_args* a, void* scratch, size_t scratch_bytes, void* stream) {
     if (!a) return fail("attn_grad: null argument");
-    if (const char* e = ta_args_error(a, true)) return fail("attn_grad: %s", e);
-    if (a->heads > 65535) return fail("attn_grad: more than 65535 heads");
-    TaPlan P;
-    if (const char* e = ta_plan(a->views, a->n_views, true, P)) return fail("attn_grad: %s", e);
-    if (!scratch || misaligned(scratch) || scratch_bytes < ta_layout(a->n_views, P.total_q_rows, a->heads).total) return fail("attn_grad: scratch too small");
-    const bool want_kv = a->dK || a->dV;
-    if (!a->dQ && !want_kv) return 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (ta_upload(P, a->views, a->n_views, true, reinterpret_cast<char*>(scratch), s, "attn_grad")) return 1;
-    TaArgs k = ta_kernel_args(a, P, reinterpret_cast<char*>(scratch));
-    k.dQ = a->dQ; k.dK = a->dK; k.dV = a->dV; k.lddq = a->lddq; k.lddk = a->lddk; k.lddv = a->lddv;
-    const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views);
-    if (P.max_nq > 0) hipLaunchKernelGGL(attn_fwd_f32, qgrid, dim3(256), 0, s, k);   // lse2 and delta into scratch
-    if (want_kv && P.max_extent > 0)
-        hipLaunchKernelGGL(attn_dkv_f32, dim3((P.max_extent + TA_T - 1) / TA_T, a->heads, (unsigned)P.groups.size()), dim3(256), 0, s, k);
-    if (a->dQ && P.max_nq > 0) hipLaunchKernelGGL(attn_dq_f32, qgrid, dim3(256), 0, s, k);
-    if (hipGetLastError() != hipSuccess) return fail("attn_grad: launch failed");
-    return 0;
+    return ta_grad("attn_grad", a, TaMask{}, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int must3r_hip_attn_masked_forward(const must3r_hip_attn_masked_args* a, void* scratch, size_t scratch_bytes) {
+    if (!a) return fail("attn_masked_forward: null argument");
+    return ta_forward("attn_masked_forward", &a->core, TaMask{a->mask_bits, a->view_mask, a->mask_rows, a->mask_ld}, scratch, scratch_bytes,
+                      reinterpret_cast<hipStream_t>(a->stream));
+}
+
+extern "C" int must3r_hip_attn_masked_grad(const must3r_hip_attn_masked_args* a, void* scratch, size_t scratch_bytes) {
+    if (!a) return fail("attn_masked_grad: null argument");
+    return ta_grad("attn_masked_grad", &a->core, TaMask{a->mask_bits, a->view_mask, a->mask_rows, a->mask_ld}, scratch, scratch_bytes,
+                   reinterpret_cast<hipStream_t>(a->stream));
 }

@@ -12,6 +12,11 @@ native inference forward (``must3r_hip_op_attention``) on cast operands instead,
 backward is the same fp32 one.  Only the gradients ``needs_input_grad`` asks for are computed.  dK and dV sum over every view that reads a key row:
 views that share key rows must share ``kv_row0`` (one key group; the decoder's tables do), and overlapping groups are refused.  A query row without a
 valid key has O = 0 and zero gradients (the reference would give NaN).  First order only (``once_differentiable``); CPU tensors raise.
+
+Key masks (memory dropout): ``attention(..., key_mask=bits, view_mask=rows)`` hides further keys from a view.  ``bits`` is a packed GPU tensor ``[rows, ld]``
+(``pack_key_mask(keep)`` from a bool ``[rows, nk]``: bit ``j % 32`` of word ``j // 32`` set where key j is kept, ``ld`` even), ``view_mask`` names each view's
+row of it, -1 for none; rows are shared freely among views.  The fp32 kernels test the bits on top of the table (``must3r_hip_attn_masked_forward`` /
+``_grad``, ABI 21, additive) and skip a key tile whose 64 bits are all zero; the 16-bit inference forward has no masks.
 """
 import ctypes as C
 
@@ -104,6 +109,55 @@ def _check_table(tab, Rq, Rk):
         raise ValueError("attention: a skip range needs skip_lo <= skip_hi <= nk")
 
 
+def pack_key_mask(keep):
+    """bool ``[rows, nk]`` (True: the key is kept) -> int32 ``[rows, ld]`` on the same device, bit ``j % 32`` of word ``j // 32`` for key j, ``ld`` the even
+    number of words that covers nk (at least 2); the bits past nk are zero.  Torch ops on the tensor's device, no host synchronisation."""
+    if keep.ndim != 2 or keep.dtype != torch.bool:
+        raise ValueError(f"pack_key_mask: a {keep.dtype} tensor of shape {tuple(keep.shape)}, expected bool [rows, nk]")
+    rows, nk = int(keep.shape[0]), int(keep.shape[1])
+    ld = max(2, (nk + 63) // 64 * 2)
+    bits = torch.zeros((rows, ld * 32), dtype=torch.int64, device=keep.device)
+    bits[:, :nk] = keep
+    weights = torch.ones(32, dtype=torch.int64, device=keep.device) << torch.arange(32, dtype=torch.int64, device=keep.device)
+    words = (bits.view(rows, ld, 32) * weights).sum(dim=2)                       # in [0, 2^32)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)   # the same 32 bits as an int32
+
+
+def _mask(key_mask, view_mask, tab, dev):
+    """``(bits, rows)`` checked against the table -- an int32 / uint32 GPU tensor ``[rows, ld]`` with ld even and an int32 CPU tensor ``[n_views]`` -- or
+    ``None`` without masks."""
+    if key_mask is None and view_mask is None:
+        return None
+    if key_mask is None or view_mask is None:
+        raise ValueError("attention: key_mask and view_mask come together")
+    if not isinstance(key_mask, torch.Tensor) or key_mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or key_mask.ndim != 2:
+        raise ValueError("attention: key_mask must be a packed int32 or uint32 tensor [rows, ld] (pack_key_mask)")
+    if key_mask.device != dev:
+        raise ValueError(f"attention: key_mask on {key_mask.device}, the operands on {dev}")
+    rows, ld = int(key_mask.shape[0]), int(key_mask.shape[1])
+    if ld <= 0 or ld % 2:
+        raise ValueError(f"attention: key_mask of {ld} words per row, expected a positive even number")
+    vm = torch.as_tensor(view_mask, dtype=torch.int32).cpu().contiguous()
+    if vm.ndim != 1 or int(vm.shape[0]) != int(tab.shape[0]):
+        raise ValueError(f"attention: view_mask of shape {tuple(vm.shape)} for a table of {int(tab.shape[0])} views")
+    r = vm.numpy()
+    if (r < -1).any() or (r >= rows).any():
+        raise ValueError(f"attention: a view_mask entry outside [-1, {rows})")
+    if (tab.numpy()[:, 3][r >= 0] > 32 * ld).any():
+        raise ValueError(f"attention: a mask row of {32 * ld} bits is shorter than the nk of a view that names it")
+    return key_mask.contiguous(), vm
+
+
+def _masked_args(a, mask, dev):
+    m = _lib.AttnMaskedArgs()
+    m.core = a
+    bits, vm = mask
+    m.mask_bits, m.view_mask = _ptr(bits), C.c_void_p(vm.data_ptr())
+    m.mask_rows, m.mask_ld = int(bits.shape[0]), int(bits.shape[1])
+    m.stream = _stream(dev)
+    return m
+
+
 def _args(q, k, v, tab, heads):
     a = _lib.AttnTrainArgs()
     a.q, a.k, a.v = _ptr(q), _ptr(k), _ptr(v)
@@ -112,10 +166,10 @@ def _args(q, k, v, tab, heads):
     return a
 
 
-def _scratch(tab, heads, dev):
+def _scratch(tab, heads, dev, masked=False):
     lib = _lib.load()
     v = tab.to(torch.int64)
-    nbytes = lib.must3r_hip_attn_train_scratch_bytes(int(tab.shape[0]), int((v[:, 0] + v[:, 1]).max()), int((v[:, 2] + v[:, 3]).max()), heads)
+    nbytes = (lib.must3r_hip_attn_masked_scratch_bytes if masked else lib.must3r_hip_attn_train_scratch_bytes)(int(tab.shape[0]), int((v[:, 0] + v[:, 1]).max()), int((v[:, 2] + v[:, 3]).max()), heads)
     if not nbytes:
         raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
     return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
@@ -125,9 +179,9 @@ def _new(rows, cols, dev, covered):
     return (torch.empty if covered else torch.zeros)((rows, cols), dtype=torch.float32, device=dev)
 
 
-def attention_forward(q, k, v, tab, heads, want_lse=False):
+def attention_forward(q, k, v, tab, heads, want_lse=False, mask=None):
     """``must3r_hip_attn_forward_f32`` on fp32 row-strided tensors and an int32 CPU table: O [Rq, heads * 64] (zeros in rows of no view), and lse
-    [Rq, heads] (natural log) with ``want_lse``."""
+    [Rq, heads] (natural log) with ``want_lse``.  ``mask``: ``(bits, rows)`` of ``_mask``, through ``must3r_hip_attn_masked_forward``."""
     lib = _lib.load()
     dev, Rq = q.device, int(q.shape[0])
     covered = _covers(q_spans(tab), Rq)
@@ -136,8 +190,11 @@ def attention_forward(q, k, v, tab, heads, want_lse=False):
     a = _args(q, k, v, tab, heads)
     a.O, a.ldo, a.lse = _ptr(o), heads * HEAD, _ptr(lse)
     with torch.cuda.device(dev):
-        scratch, nbytes = _scratch(tab, heads, dev)
-        _lib.check(lib.must3r_hip_attn_forward_f32(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
+        scratch, nbytes = _scratch(tab, heads, dev, mask is not None)
+        if mask is None:
+            _lib.check(lib.must3r_hip_attn_forward_f32(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
+        else:
+            _lib.check(lib.must3r_hip_attn_masked_forward(C.byref(_masked_args(a, mask, dev)), _ptr(scratch), nbytes))
     return (o, lse) if want_lse else o
 
 
@@ -158,8 +215,9 @@ def attention_forward16(q, k, v, tab, heads, dtype):
     return o16.to(torch.float32)
 
 
-def attention_grad(q, k, v, dO, tab, heads, want=(True, True, True)):
-    """``must3r_hip_attn_grad`` on fp32 row-strided tensors: ``(dQ, dK, dV)``, ``None`` where ``want`` says so; zeros in rows the table leaves out."""
+def attention_grad(q, k, v, dO, tab, heads, want=(True, True, True), mask=None):
+    """``must3r_hip_attn_grad`` on fp32 row-strided tensors: ``(dQ, dK, dV)``, ``None`` where ``want`` says so; zeros in rows the table leaves out.
+    ``mask``: ``(bits, rows)`` of ``_mask``, through ``must3r_hip_attn_masked_grad``."""
     lib = _lib.load()
     dev, D = q.device, heads * HEAD
     dq = _new(int(q.shape[0]), D, dev, _covers(q_spans(tab), int(q.shape[0]))) if want[0] else None
@@ -172,17 +230,20 @@ def attention_grad(q, k, v, dO, tab, heads, want=(True, True, True)):
     a.dO, a.lddo = _ptr(dO), _ld(dO)
     a.dQ, a.dK, a.dV, a.lddq, a.lddk, a.lddv = _ptr(dq), _ptr(dk), _ptr(dv), D, D, D
     with torch.cuda.device(dev):
-        scratch, nbytes = _scratch(tab, heads, dev)
-        _lib.check(lib.must3r_hip_attn_grad(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
+        scratch, nbytes = _scratch(tab, heads, dev, mask is not None)
+        if mask is None:
+            _lib.check(lib.must3r_hip_attn_grad(C.byref(a), _ptr(scratch), nbytes, _stream(dev)))
+        else:
+            _lib.check(lib.must3r_hip_attn_masked_grad(C.byref(_masked_args(a, mask, dev)), _ptr(scratch), nbytes))
     return dq, dk, dv
 
 
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, tab, heads, dtype):
+    def forward(ctx, q, k, v, tab, heads, dtype, mask=None):
         ctx.save_for_backward(q, k, v)
-        ctx.tab, ctx.heads = tab, heads
-        return _forward(q, k, v, tab, heads, dtype)
+        ctx.tab, ctx.heads, ctx.mask = tab, heads, mask
+        return _forward(q, k, v, tab, heads, dtype, mask)
 
     @staticmethod
     @once_differentiable
@@ -190,20 +251,22 @@ class _Attention(torch.autograd.Function):
         q, k, v = ctx.saved_tensors
         heads = ctx.heads
         f = [_fp32_rows(t, n, heads) for t, n in ((q, "q"), (k, "k"), (v, "v"), (grad_out, "the upstream gradient"))]
-        grads = attention_grad(*f, ctx.tab, heads, want=tuple(ctx.needs_input_grad[:3]))
+        grads = attention_grad(*f, ctx.tab, heads, want=tuple(ctx.needs_input_grad[:3]), mask=ctx.mask)
         out = [None if g is None else g.to(t.dtype) for g, t in zip(grads, (q, k, v))]
-        return (*out, None, None, None)
+        return (*out, None, None, None, None)
 
 
-def _forward(q, k, v, tab, heads, dtype):
+def _forward(q, k, v, tab, heads, dtype, mask=None):
     f = [_fp32_rows(t, n, heads) for t, n in ((q, "q"), (k, "k"), (v, "v"))]
-    return attention_forward(*f, tab, heads) if dtype is None else attention_forward16(*f, tab, heads, int(dtype))
+    return attention_forward(*f, tab, heads, mask=mask) if dtype is None else attention_forward16(*f, tab, heads, int(dtype))
 
 
-def attention(q, k, v, views, heads, dtype=None):
+def attention(q, k, v, views, heads, dtype=None, key_mask=None, view_mask=None):
     """O ``[Rq, heads * 64]`` fp32 from q ``[Rq, heads * 64]`` and k, v ``[Rk, heads * 64]`` (fp32 GPU tensors, possibly column slices of one packed tensor:
     the last dimension contiguous, the row stride is passed through) and ``views`` (int32 CPU tensor or list ``[n][6]``); differentiable at q, k and v.
-    ``dtype``: ``None`` for the fp32 forward, ``_lib.F16`` / ``_lib.BF16`` for the native inference forward on cast operands."""
+    ``dtype``: ``None`` for the fp32 forward, ``_lib.F16`` / ``_lib.BF16`` for the native inference forward on cast operands.  ``key_mask`` / ``view_mask``:
+    packed key masks ``[rows, ld]`` on the GPU (``pack_key_mask``) and each view's row of them (list or int32 CPU tensor, -1: none); they need ``dtype=None``
+    and are saved for the backward like the table."""
     heads = int(heads)
     if heads <= 0:
         raise ValueError("attention: heads must be positive")
@@ -217,7 +280,10 @@ def attention(q, k, v, views, heads, dtype=None):
         raise ValueError("attention: dtype must be None, _lib.F16 or _lib.BF16")
     tab = _table(views)
     _check_table(tab, int(q.shape[0]), int(k.shape[0]))
+    mask = _mask(key_mask, view_mask, tab, q.device)
+    if mask is not None and dtype is not None:
+        raise ValueError("attention: key masks need dtype=None (the native 16-bit inference forward has no masks)")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         n_groups(tab)   # a table the backward would refuse is refused here, before the forward runs
-        return _Attention.apply(q, k, v, tab, heads, dtype)
-    return _forward(q, k, v, tab, heads, dtype)
+        return _Attention.apply(q, k, v, tab, heads, dtype, mask)
+    return _forward(q, k, v, tab, heads, dtype, mask)

@@ -17,6 +17,10 @@ Everything runs in fp32 on the fp32 MFMA (``must3r_hip_cross_sublayer_forward`` 
 the descriptor).  A forward saves its inputs and nothing else; the backward recomputes the sublayer's forward into scratch and differentiates it.  Only the
 gradients ``needs_input_grad`` asks for are computed (a detached memory and frozen ``projk`` / ``projv``: no dK / dV launch; a frozen ``x``, ``norm2`` and
 ``projq``: no dQ launch).  First order only (``once_differentiable``); gradients come back in the shape and dtype of their inputs; CPU tensors raise.
+
+Key masks (memory dropout): ``cross_attention_sublayer(..., key_mask=bits, view_mask=rows)`` and ``CachedDecoderBlock.forward(..., key_mask=, view_mask=)``
+hand the packed masks of ``train_attention.pack_key_mask`` to the sublayer's attention core (``must3r_hip_cross_sublayer_masked_forward`` / ``_grad``); the
+mask bits index the key rows of a view like the table does.  Without them every call path is the one it was.
 """
 import ctypes as C
 
@@ -26,9 +30,9 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import train_block as TB
-from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _ld, _new, _Proj, _ptr, _rows, _stream
+from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _ld, _new, _Proj, _ptr, _rows, _scratch, _stream
 from ._train_common import _strided_rows as _mem_rows
-from .train_attention import _check_table, _table, n_groups
+from .train_attention import _check_table, _mask, _table, n_groups
 from .train_attention import self_views as _self_views
 from .train_block import ROPE_NPOS, _AttnParams, _MlpParams
 
@@ -46,17 +50,36 @@ def _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, 
     return a
 
 
-def cross_forward(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps=1e-6):
-    """``must3r_hip_cross_sublayer_forward`` on fp32 GPU tensors (x contiguous, mem row-strided) and an int32 CPU table; ``Wk = bk = Wv = bv = None``: mem holds k | v."""
+def _call_masked(entry, a, mask, nbytes, dev, **tensors):
+    """``_call_sublayer`` for the masked entry points: the filled descriptor ``a`` travels inside a ``CrossSublayerMaskedArgs`` with the masks ``(bits, rows)``
+    of ``train_attention._mask``; the stream is the one ``a`` carries."""
+    for n, t in tensors.items():
+        setattr(a, n, _ptr(t))
+    m = _lib.CrossSublayerMaskedArgs()
+    m.core = a
+    bits, vm = mask
+    m.mask_bits, m.view_mask, m.mask_rows, m.mask_ld = _ptr(bits), C.c_void_p(vm.data_ptr()), int(bits.shape[0]), int(bits.shape[1])
+    with torch.cuda.device(dev):
+        scratch = _scratch(nbytes, dev)
+        _lib.check(entry(C.byref(m), _ptr(scratch), nbytes))
+
+
+def cross_forward(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps=1e-6, mask=None):
+    """``must3r_hip_cross_sublayer_forward`` on fp32 GPU tensors (x contiguous, mem row-strided) and an int32 CPU table; ``Wk = bk = Wv = bv = None``: mem holds
+    k | v.  ``mask``: ``(bits, rows)`` of ``train_attention._mask``, through ``must3r_hip_cross_sublayer_masked_forward``."""
     lib = _lib.load()
     out = torch.empty_like(x)
     a = _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps)
-    nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(a.M, a.Rm, a.D, a.n_views, 1 if Wk is None else 0)
-    _call_sublayer(lib.must3r_hip_cross_sublayer_forward, a, nbytes, x.device, out=out)
+    if mask is None:
+        nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(a.M, a.Rm, a.D, a.n_views, 1 if Wk is None else 0)
+        _call_sublayer(lib.must3r_hip_cross_sublayer_forward, a, nbytes, x.device, out=out)
+    else:
+        nbytes = lib.must3r_hip_cross_sublayer_masked_scratch_bytes(a.M, a.Rm, a.D, a.n_views, 1 if Wk is None else 0)
+        _call_masked(lib.must3r_hip_cross_sublayer_masked_forward, a, mask, nbytes, x.device, out=out)
     return out
 
 
-def cross_grad(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, dy, eps=1e-6, want=(True,) * 12, dmem=None):
+def cross_grad(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, dy, eps=1e-6, want=(True,) * 12, dmem=None, mask=None):
     """``must3r_hip_cross_sublayer_grad``: the gradients of CROSS_OUTPUTS, ``None`` where ``want`` says so (and for Wk, bk, Wv, bv where mem holds k | v).
     ``dmem``: a row-strided fp32 buffer ``[Rm, D or 2 D]`` to write the memory's gradient into instead of a new tensor."""
     lib = _lib.load()
@@ -71,8 +94,12 @@ def cross_grad(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, d
         return outs
     a = _cross_args(x, mem, tab, gamma, beta, Wq, bq, Wk, bk, Wv, bv, Wproj, bproj, eps)
     a.lddmem = _ld(outs[1]) if outs[1] is not None else 0
-    nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(M, Rm, D, a.n_views, 1 if kv_ready else 0)
-    _call_sublayer(lib.must3r_hip_cross_sublayer_grad, a, nbytes, dev, dy=dy, **dict(zip(CROSS_OUTPUTS, outs)))
+    if mask is None:
+        nbytes = lib.must3r_hip_cross_sublayer_scratch_bytes(M, Rm, D, a.n_views, 1 if kv_ready else 0)
+        _call_sublayer(lib.must3r_hip_cross_sublayer_grad, a, nbytes, dev, dy=dy, **dict(zip(CROSS_OUTPUTS, outs)))
+    else:
+        nbytes = lib.must3r_hip_cross_sublayer_masked_scratch_bytes(M, Rm, D, a.n_views, 1 if kv_ready else 0)
+        _call_masked(lib.must3r_hip_cross_sublayer_masked_grad, a, mask, nbytes, dev, dy=dy, **dict(zip(CROSS_OUTPUTS, outs)))
     return outs
 
 
@@ -82,11 +109,12 @@ def _opt(t):
 
 class _Cross(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b, tab, eps):
+    def forward(ctx, x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b, tab, eps, mask=None):
         ctx.save_for_backward(x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)
-        ctx.tab, ctx.eps = tab, eps
+        ctx.tab, ctx.eps, ctx.mask = tab, eps, mask
         width = int(mem.shape[1])
-        return cross_forward(_rows(x), _mem_rows(mem, width), tab, *(_opt(t) for t in (norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)), eps).view(x.shape)
+        return cross_forward(_rows(x), _mem_rows(mem, width), tab, *(_opt(t) for t in (norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)), eps,
+                             mask).view(x.shape)
 
     @staticmethod
     @once_differentiable
@@ -94,16 +122,17 @@ class _Cross(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, mem = saved[0], saved[1]
         grads = cross_grad(_rows(x), _mem_rows(mem, int(mem.shape[1])), ctx.tab, *(_opt(t) for t in saved[2:]), _rows(grad_out), ctx.eps,
-                           want=tuple(ctx.needs_input_grad[:12]))
+                           want=tuple(ctx.needs_input_grad[:12]), mask=ctx.mask)
         # CROSS_OUTPUTS is in the order of the inputs
-        return (*_back(grads, [t if t is not None else x for t in saved]), None, None)
+        return (*_back(grads, [t if t is not None else x for t in saved]), None, None, None)
 
 
-def cross_attention_sublayer(x, mem, views, heads, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b, eps=1e-6):
+def cross_attention_sublayer(x, mem, views, heads, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b, eps=1e-6, key_mask=None, view_mask=None):
     """``x + proj(attn(projq(LN(x)), projk(mem), projv(mem)))``; x [..., D] with D = heads * 64 (flattened to rows), mem [Rm, D] -- or
     ``k_w = k_b = v_w = v_b = None`` with mem [Rm, 2 D] = k | v (the ``kv`` memory mode).  ``views``: the 6-int table of ``train_attention`` whose query rows
     index the rows of x and whose key rows index mem (``memory_views``; ragged tables are fine).  Differentiable at x, mem and the ten parameters.  mem may be
-    a row-strided view with a contiguous last dimension: the stride is passed through."""
+    a row-strided view with a contiguous last dimension: the stride is passed through.  ``key_mask`` / ``view_mask``: the packed key masks of
+    ``train_attention.attention`` over the key rows of each view, saved for the backward like the table."""
     D = _check_x(x, "cross_attention_sublayer: x")
     if int(heads) * HEAD != D:
         raise ValueError(f"cross_attention_sublayer: width {D} is not heads * 64 = {int(heads) * HEAD}")
@@ -121,11 +150,12 @@ def cross_attention_sublayer(x, mem, views, heads, norm_w, norm_b, q_w, q_b, k_w
     _check_params("cross_attention_sublayer", D, **shapes)
     tab = _table(views)
     _check_table(tab, x.numel() // D, int(mem.shape[0]))
+    mask = _mask(key_mask, view_mask, tab, x.device)
     inputs = (x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in inputs):
         n_groups(tab)   # a table the backward would refuse is refused here, before the forward runs
-        return _Cross.apply(*inputs, tab, float(eps))
-    return cross_forward(_rows(x), _mem_rows(mem, width), tab, *(_opt(t) for t in inputs[2:]), float(eps)).view(x.shape)
+        return _Cross.apply(*inputs, tab, float(eps), mask)
+    return cross_forward(_rows(x), _mem_rows(mem, width), tab, *(_opt(t) for t in inputs[2:]), float(eps), mask).view(x.shape)
 
 
 def memory_rows(current_mem, new_rows, n_scenes):
@@ -191,10 +221,11 @@ class CachedDecoderBlock(nn.Module):
         c = self.cross_attn
         return torch.cat([TB.linear(y_, c.projk.weight, c.projk.bias), TB.linear(y_, c.projv.weight, c.projv.bias)], dim=-1)
 
-    def forward(self, x, y, pos, self_views=None, mem_views=None):
+    def forward(self, x, y, pos, self_views=None, mem_views=None, key_mask=None, view_mask=None):
         """x ``[R, D]`` or ``[B, N, D]``, pos int64 ``[R, 2]`` / ``[B, N, 2]``, y the key rows in this block's memory mode, ``[Rk, W]`` or ``[B, Nk, W]``
         (W = 2 D in the ``kv`` mode, else D).  ``self_views`` / ``mem_views``: the tables of the self and the cross attention over the flattened rows of x
-        (and of y).  Without tables: one view per batch entry that attends all of that entry's y (the reference's own calling form), one view for 2-d x."""
+        (and of y).  Without tables: one view per batch entry that attends all of that entry's y (the reference's own calling form), one view for 2-d x.
+        ``key_mask`` / ``view_mask``: packed key masks of the cross attention (``train_attention.pack_key_mask``) and each view's row of them."""
         B, N = (int(x.shape[0]), int(x.shape[1])) if x.ndim == 3 else (1, int(x.shape[0]))
         if self_views is None:
             self_views = _self_views(1, B, N)
@@ -211,5 +242,5 @@ class CachedDecoderBlock(nn.Module):
             yk = TB.layer_norm(yk, self.norm_y.weight, self.norm_y.bias, self.eps)
         kv = (None,) * 4 if self.memory_mode == "kv" else (c.projk.weight, c.projk.bias, c.projv.weight, c.projv.bias)
         x = cross_attention_sublayer(x, yk, mem_views, self.num_heads, self.norm2.weight, self.norm2.bias, c.projq.weight, c.projq.bias, *kv, c.proj.weight,
-                                     c.proj.bias, self.eps)
+                                     c.proj.bias, self.eps, key_mask, view_mask)
         return TB.mlp_sublayer(x, self.norm3.weight, self.norm3.bias, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias, self.eps)

@@ -18,7 +18,8 @@ followed by the k | v Linears in the ``kv`` mode; the results are ``torch.cat``-
 ``prepare_y`` rows already computed for the keys: they are reused and nothing is launched.
 
 Everything runs in fp32; only the gradients ``needs_input_grad`` asks for are computed (frozen parts cost no launches); first order only; CPU tensors
-raise.  Memory dropout, list inputs (``forward_list``) and mixed aspect ratios are not built.  The memory is concatenated per call, not appended in place.
+raise.  List inputs (``forward_list``) and mixed aspect ratios are not built; memory dropout is ``train_dropout.CausalMUSt3R``, which hands the key masks of a
+call to this forward.  The memory is concatenated per call, not appended in place.
 """
 import ctypes as C
 
@@ -326,12 +327,14 @@ class MUSt3R(PredictionHead):
             out.append(torch.cat([TB.linear(y, c.projk.weight, c.projk.bias), TB.linear(y, c.projv.weight, c.projv.bias)], dim=-1))
         return out
 
-    def forward(self, x, pos, true_shape, current_mem=None, render=False, return_tokens=False):
-        """x ``[B, nimgs, N, Denc]``, pos int64 ``[B, nimgs, N, 2]``, true_shape ``[B, nimgs, 2]`` (all views of a call share (H, W)) ->
+    def forward(self, x, pos, true_shape, current_mem=None, render=False, return_tokens=False, key_mask=None, view_mask=None):
+        """x ``[B, nimgs, N, Denc]``, pos int64 ``[B, nimgs, N, 2]`` (or flattened ``[B nimgs N, 2]``: ``train_block.check_positions`` then recognises
+        the tensor from call to call and does not read it on the host again), true_shape ``[B, nimgs, 2]`` (all views of a call share (H, W)) ->
         ``(mem, pointmaps [B, nimgs, H, W, 7])``; ``mem`` is the reference's 5-tuple ``([L tensors [B, Nm, W]], labels int64 [B, Nm], mem_nimgs,
         protected_imgs, protected_tokens)`` whose tensors stay in the autograd graph (a detached memory, or one made under ``torch.no_grad()``, is fine).
         ``render``: the memory is read, not updated, and comes back as it was given.  ``return_tokens``: also the last layer's tokens ``[B, nimgs, N, D]``
-        (before ``norm_dec``)."""
+        (before ``norm_dec``).  ``key_mask`` / ``view_mask``: packed key masks over the key rows of the call's cross attention and each view's row of them
+        (``train_attention.pack_key_mask``; ``train_dropout``), the same for every layer."""
         if isinstance(x, (list, tuple)) or isinstance(pos, (list, tuple)):
             raise TypeError("train_decoder.MUSt3R.forward takes tensors [B, nimgs, N, Denc]: list inputs (forward_list, mixed aspect ratios) are not built")
         _dev(x, "x")
@@ -345,7 +348,7 @@ class MUSt3R(PredictionHead):
         W = 2 * D if self.memory_mode == "kv" else D
         if pos.numel() != 2 * M:
             raise ValueError(f"MUSt3R: pos of shape {tuple(pos.shape)} for x of shape {tuple(x.shape)}")
-        pos = pos.reshape(M, 2)
+        pos = pos if tuple(pos.shape) == (M, 2) else pos.reshape(M, 2)     # flattened already: the same object reaches check_positions again
         if current_mem is None:
             mem_vals, labels, n_imgs, prot_imgs, prot_tokens, Nm = [None] * L, torch.zeros((B, 0), dtype=torch.int64, device=x.device), 0, 0, 0, 0
         else:
@@ -381,7 +384,7 @@ class MUSt3R(PredictionHead):
                 new.append(xr)
                 pre.append(blk.prepare_y(xr))
                 keys = memory_rows(mem_l, pre[-1], B)
-            xr = blk(xr, keys, pos, sv, cross)
+            xr = blk(xr, keys, pos, sv, cross, key_mask, view_mask)
         if render:
             out = current_mem
         else:
