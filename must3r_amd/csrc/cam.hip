@@ -9,8 +9,19 @@
 // reference pays 11 full passes over H*W for; here a view is spread over G persistent blocks (cooperative launch, all
 // co-resident), every block keeps the (x/z, y/z) of its <= 16 x 1024 pixels in LDS (128 KB), and an iteration costs one
 // block reduction + one per-view barrier (arrive counter + partials through agent-scope atomics) + a fixed-order sum of G partials
-// (deterministic; no floating-point atomics).  All sums are accumulated in fp64 -- the reference's are fp32 -- the
-// per-pixel terms are the reference's fp32 expressions.  The 3x3 Procrustes problem is solved by one thread per view
+// (deterministic; no floating-point atomics).  All sums are accumulated in fp64 -- the reference's are fp32.  The
+// per-pixel terms of the focal iteration are the reference's fp32 expressions.  Those of the registration are NOT:
+// the reference centres x and y before it forms M = sum w (y - ybar)(x - xbar)^T; here the data pass (which cannot
+// know the means yet) accumulates the uncentred moments sum fl(w y_i) x_j and subtracts ybar xbar^T in the solve.
+// The fp32 rounding of w * y_i therefore scales with |y|, not with |y - ybar|, and the centring does not take it
+// out again: the rotation's error grows linearly with the distance of the world points from the origin, in units
+// of the scene's extent.  Emulated at 64x96 and 384x512 (tests/cam_cases.py), rotation error against fp64:
+//   offset 0: 3e-8, the fp32 rounding of the stored R (fp32 reference 3e-7 .. 8e-7),
+//   offset 100 extents: 2e-8 .. 2.5e-7 (2e-7 .. 7e-7), offset 10 000 extents: 1.6e-6 .. 2.5e-5 (1e-7 .. 3e-7).
+// Up to some hundred extents this is inside the fp32 reference's own error (tests/test_cam_gpu.py pins offset 100);
+// at 10 000 it is not.  The cure, should such scenes appear, is a per-view pilot point (e.g. the view's first y)
+// subtracted from every y before the products and added back to ybar: M is invariant under that shift.
+// The 3x3 Procrustes problem is solved by one thread per view
 // with Horn's quaternion form (largest eigenvector of a 4x4 symmetric matrix, cyclic Jacobi in fp64), which equals
 // U diag(1,1,det(UV^T)) V^T of the SVD form without the sign case analysis.
 #include "abi.hpp"
