@@ -965,6 +965,60 @@ size_t must3r_hip_feedback_prepare_scratch_bytes(int L, int R, int D);
 int must3r_hip_feedback_prepare_forward(const must3r_hip_feedback_prepare_args* a, void* scratch, size_t scratch_bytes);
 int must3r_hip_feedback_prepare_grad(const must3r_hip_feedback_prepare_args* a, void* scratch, size_t scratch_bytes);
 
+/* ABI 21, additive.  The optimizer step of the reference's training recipe (must3r/engine/train.py: torch.optim.AdamW under croco's
+ * NativeScalerWithGradNormCount): the global gradient norm with the non-finite test, the clip coefficient and GradScaler.update() in one pass over the
+ * gradients (optim_norm), and decoupled-decay Adam in one pass over parameters and moments (optim_adamw).  fp32 storage, no atomics, no host synchronisation.
+ * The table: HOST arrays of tensors {p, g, m, v, step, n, group} (DEVICE fp32 pointers, 16-byte aligned; step one fp32 scalar per tensor, as torch.optim.AdamW
+ * keeps it; n >= 1 elements, int64) and of groups {lr, weight_decay, beta1, beta2, eps} (fp64, as the host holds them; lr is the group's effective rate).  The
+ * library cuts every tensor into chunks of MUST3R_OPTIM_CHUNK elements and uploads tensors and chunk list in one copy into the caller's scratch through a ring of
+ * pinned buffers, so that a second call does not wait for the first.  Offsets are 64-bit: no limit of 2^31 on the total.  A tensor whose n is not a multiple of 4
+ * ends in a scalar tail.  The stream travels in the descriptor (`stream`, a hipStream_t): all work goes to it, the upload included.
+ * optim_norm reads g and n of the table alone (p, m, v, step, group and the group table are not looked at) and writes the control record, without the host:
+ *   total     = sum of g^2 over the table, in fp64: one partial per chunk, the partials added in a fixed order (bitwise repeatable)
+ *   inv_scale = 1 / *scale in fp32, read BEFORE the update below; 1 without a scaler state
+ *   norm      = sqrt(total) inv_scale, rounded to fp32 once
+ *   found_inf = total is not finite (some gradient element is not finite: squares of finite fp32 values cannot overflow fp64)
+ *   coef      = inv_scale (max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1)           torch.nn.utils.clip_grad_norm_'s rule, in fp32
+ * and, where a scaler state is given (DEVICE scale fp32 [1], growth_tracker int32 [1]), GradScaler.update(): on found_inf scale *= backoff_factor and
+ * tracker = 0; otherwise tracker += 1 and, at growth_interval, scale *= growth_factor and tracker = 0.
+ * optim_adamw: nothing at all where control is given and found_inf is set.  Otherwise step += 1 for every tensor of the table (t below), and per element
+ *   g' = g coef                 p = p (1 - lr wd)               coef = 1 with control == NULL (a plain optimizer step, never skipped)
+ *   m  = b1 m + (1 - b1) g'     v = b2 v + (1 - b2) g' g'
+ *   p  = p - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)         bc1 = 1 - b1^t, bc2 = 1 - b2^t
+ * in fp32; lr / bc1 and sqrt(bc2) are computed in fp64 and rounded once, and 1 - lr wd, b1, 1 - b1, b2, 1 - b2, eps are fp64 values rounded once.  g is never
+ * written: the unscale and the clip live in coef.  An element's new p, m, v depend on its own old values, g, coef and its tensor's numbers alone, not on the
+ * other tensors of the table or their order.  A tensor must not be named twice.
+ * Scratch (no device needed; 0 on a bad shape, the reason in the last error), each part rounded up to 256 bytes, with C = total_elems / MUST3R_OPTIM_CHUNK +
+ * n_tensors (the most chunks such a table can have):
+ *   optim_scratch_bytes(n_tensors, total_elems) = 96 n_tensors + 16 C + 8 C + 8 n_tensors       [tensors | chunks | fp64 partials | lr / bc1, sqrt(bc2)]
+ *   both calls take the same scratch (the same buffer may serve both: they are ordered by the stream).
+ * Refused with an error before anything on the device is read or launched: a NULL descriptor, tensors (adamw: groups) NULL, n_tensors < 1 (adamw: n_groups < 1),
+ * a NULL g (adamw: p, m, v, step), pointers not 16-byte aligned, n <= 0, a total above 2^46; adamw: a group index outside the table, a beta outside [0, 1),
+ * eps < 0, lr < 0, weight_decay < 0; norm: control NULL, a scaler state with only one of its two pointers, factors <= 0 or growth_interval < 1 with a scaler
+ * state, max_norm NaN; scratch NULL, misaligned or too small. */
+#define MUST3R_OPTIM_CHUNK 32768
+typedef struct must3r_hip_optim_tensor {
+    float* p; const float* g; float* m; float* v; float* step;   /* DEVICE */
+    int64_t n;
+    int32_t group, reserved;
+} must3r_hip_optim_tensor;
+typedef struct must3r_hip_optim_group { double lr, weight_decay, beta1, beta2, eps; } must3r_hip_optim_group;
+typedef struct must3r_hip_optim_control { float norm, coef; int32_t found_inf, reserved; } must3r_hip_optim_control;
+typedef struct must3r_hip_optim_args {
+    const must3r_hip_optim_tensor* tensors;      /* HOST [n_tensors] */
+    const must3r_hip_optim_group* groups;        /* HOST [n_groups]; optim_adamw only */
+    int32_t n_tensors, n_groups;
+    must3r_hip_optim_control* control;           /* DEVICE, 16-byte aligned; optim_norm writes it, optim_adamw reads it (optional there) */
+    float* scale; int32_t* growth_tracker;       /* DEVICE, optim_norm only, both or neither */
+    float max_norm;                              /* optim_norm only; <= 0: no clip */
+    float growth_factor, backoff_factor;
+    int32_t growth_interval;
+    void* stream;                                /* hipStream_t */
+} must3r_hip_optim_args;
+size_t must3r_hip_optim_scratch_bytes(int64_t n_tensors, int64_t total_elems);
+int must3r_hip_optim_norm(const must3r_hip_optim_args* a, void* scratch, size_t scratch_bytes);
+int must3r_hip_optim_adamw(const must3r_hip_optim_args* a, void* scratch, size_t scratch_bytes);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

@@ -198,6 +198,34 @@ class FeedbackPrepareArgs(C.Structure):
         ("eps", C.c_float), ("reserved", C.c_int32), ("stream", C.c_void_p)]
 
 
+OPTIM_CHUNK = 32768   # MUST3R_OPTIM_CHUNK: elements of one chunk of the optimizer's tensor table
+
+
+class OptimTensor(C.Structure):
+    """must3r_hip_optim_tensor: one parameter tensor of the optimizer's table, DEVICE pointers (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("step", C.c_void_p), ("n", C.c_int64),
+                ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimGroup(C.Structure):
+    """must3r_hip_optim_group: the numbers of one parameter group, ``lr`` the effective rate (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("lr", C.c_double), ("weight_decay", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+class OptimControl(C.Structure):
+    """must3r_hip_optim_control: the device record optim_norm writes and optim_adamw reads (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("found_inf", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptimArgs(C.Structure):
+    """must3r_hip_optim_args: the HOST tables, the control record, the (optional) scaler state and the stream of the optimizer's two passes
+    (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("tensors", C.POINTER(OptimTensor)), ("groups", C.POINTER(OptimGroup)), ("n_tensors", C.c_int32), ("n_groups", C.c_int32),
+                ("control", C.c_void_p), ("scale", C.c_void_p), ("growth_tracker", C.c_void_p),
+                ("max_norm", C.c_float), ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32),
+                ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -308,6 +336,9 @@ PROTOTYPES = {
     "must3r_hip_feedback_prepare_scratch_bytes": (sz, [i32, i32, i32]),
     "must3r_hip_feedback_prepare_forward": (i32, [P(FeedbackPrepareArgs), vp, sz]),
     "must3r_hip_feedback_prepare_grad": (i32, [P(FeedbackPrepareArgs), vp, sz]),
+    "must3r_hip_optim_scratch_bytes": (sz, [i64, i64]),
+    "must3r_hip_optim_norm": (i32, [P(OptimArgs), vp, sz]),
+    "must3r_hip_optim_adamw": (i32, [P(OptimArgs), vp, sz]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -4,7 +4,7 @@ two of the three of ``CachedDecoderBlock``) under ``torch.autograd``::
     blk = Block.from_params(encoder.blocks_enc[3])                    # fp32 copies under the reference's state-dict keys
     y = blk(x, pos)                                                   # x [B, N, D] or [R, D], pos int64 [.., 2]; views default to one per batch entry
     loss(y).backward()                                                # x.grad, blk.*.grad
-    torch.optim.AdamW(blk.parameters()).step()
+    train_optim.AdamW(blk.parameters()).step()                        # the native step (must3r_amd/train_optim.py); torch.optim.AdamW works too
 
     attention sublayer   x + proj(attn(rope(qkv(norm1 x))))           ``attention_sublayer``
     MLP sublayer         x + fc2(gelu(fc1(norm2 x)))                  ``mlp_sublayer``

@@ -6,7 +6,7 @@ decoder's last-layer tokens and ``must3r_amd.train_losses``::
     raw = head(tokens, true_shape)                                    # tokens.requires_grad or not
     loss, details = criterion(gt, train_losses.postprocess(raw, 'norm_exp'))
     loss.backward()                                                   # tokens.grad, head.*.grad
-    torch.optim.AdamW(head.parameters()).step()
+    train_optim.AdamW(head.parameters()).step()                       # the native step (must3r_amd/train_optim.py); torch.optim.AdamW works too
 
 The forward is the native decoder's own head (the same two launches, ``must3r_hip_head_forward``) on operands packed from the fp32 parameters of the
 call, so that an optimizer step is seen by the next forward.  The backward (``must3r_hip_head_grad``, include/must3r_hip.h ABI 19) runs fp32 operands on
