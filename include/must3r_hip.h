@@ -1019,6 +1019,27 @@ size_t must3r_hip_optim_scratch_bytes(int64_t n_tensors, int64_t total_elems);
 int must3r_hip_optim_norm(const must3r_hip_optim_args* a, void* scratch, size_t scratch_bytes);
 int must3r_hip_optim_adamw(const must3r_hip_optim_args* a, void* scratch, size_t scratch_bytes);
 
+/* ABI 21, additive.  The matrix products of the training Linears on the 16-bit MFMA (v_mfma_f32_16x16x32_bf16, fp32 accumulation), switched the way
+ * torch.autocast switches: by a mode of the calling host thread, not by an argument (the reference's recipe trains under --amp bf16).
+ *   In MUST3R_TRAIN_LINEAR_BF16 mode must3r_hip_op_linear_f32, must3r_hip_op_linear_dgrad_f32, must3r_hip_op_linear_wgrad_f32 and the two-parameter data
+ *   gradient of the cross sublayer (dmem = dK Wk + dV Wv) round both operands of their product to bf16 (nearest even, NaN and inf kept: Tensor.to(bfloat16))
+ *   as they stage them, multiply on the 16-bit MFMA and accumulate in fp32.  Every training entry point built on them follows: the MLP, attention and cross
+ *   sublayers (masked forms included) and the decoder's embedding and feedback Linears.  The `_f32` in these names is the STORAGE type: every tensor in memory
+ *   -- activations, master weights, outputs, gradients, scratch -- is fp32 in either mode; there is no cast pass and no 16-bit copy of a weight.  Shapes,
+ *   alignment rules, descriptors, scratch queries and stream order are the same in both modes.
+ *   What stays fp32 arithmetic in either mode: the bias, residual and GELU epilogues (on the fp32 accumulator), the bias gradient (column sums of the unrounded
+ *   dZ), the reduction of the weight-gradient partials, LayerNorm forward and backward, the attention core (scores, softmax, P V and their gradients), RoPE, the
+ *   residual stream, the head (must3r_hip_head_forward / _head_grad / _op_head_linear: its own split-precision forms and the fp32 gather forms), the loss family
+ *   and the optimizer.  bf16 attention and bf16 storage of activations are not built.
+ *   In MUST3R_TRAIN_LINEAR_F32 mode (the default of every thread) the four functions launch exactly the kernels of ABI 21 before this entry point existed.
+ *   The bf16 kernels use no atomics either: one writer per element, a fixed order of additions, a row of out / dX independent of the other rows.
+ * A backward pass that recomputes a sublayer's forward must run in the mode its forward ran in (must3r_amd records it per autograd node). */
+#define MUST3R_TRAIN_LINEAR_F32  0
+#define MUST3R_TRAIN_LINEAR_BF16 1
+/* Per host thread; default F32.  Sets the mode in which must3r_hip_op_linear_f32, _dgrad_f32, _wgrad_f32 and every training entry point
+   built on them multiply; returns the previous mode.  mode = -1 only queries.  Any other value: returns -1, last error set, nothing changed. */
+int must3r_hip_train_linear_mode(int mode);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

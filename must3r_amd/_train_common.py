@@ -1,6 +1,8 @@
 """What the training modules (``train_head``, ``train_attention``, ``train_block``, ``train_cross``, ``train_decoder``) share on the host: the checks that a tensor is on the GPU
 and has the expected shape, the fp32 views handed to the library, scratch and output allocation, the one calling pattern of the sublayer entry points, and
-the two parameter holders.  Everything here is private to the package."""
+the two parameter holders, and the precision switch of the training Linears (``linear_precision`` / ``current_precision``, re-exported by ``train_block``).
+Everything else here is private to the package."""
+import contextlib
 import ctypes as C
 
 import torch
@@ -9,6 +11,42 @@ import torch.nn as nn
 from . import _lib
 
 HEAD = 64
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the precision of the training Linears' products (must3r_hip_train_linear_mode, include/must3r_hip.h "ABI 21, additive")
+# ---------------------------------------------------------------------------------------------------------------------------------------
+PRECISIONS = {"fp32": _lib.TRAIN_LINEAR_F32, "bf16": _lib.TRAIN_LINEAR_BF16}
+_PRECISION_NAMES = {v: k for k, v in PRECISIONS.items()}
+
+
+def current_precision():
+    """``"fp32"`` or ``"bf16"``: the mode in which the calling thread's training Linears multiply."""
+    return _PRECISION_NAMES[_lib.load().must3r_hip_train_linear_mode(-1)]
+
+
+@contextlib.contextmanager
+def linear_precision(mode):
+    """``with linear_precision("bf16"):`` -- inside, every Linear of the training path (``linear``, the MLP, attention and cross sublayers, the decoder's
+    embedding and feedback Linears) rounds the two operands of its product to bf16 as it stages them, multiplies on the 16-bit MFMA and accumulates in fp32,
+    like ``torch.autocast(dtype=torch.bfloat16)`` does for ``nn.Linear``; ``"fp32"`` is the default of every thread; ``None`` leaves the mode alone.  The mode
+    belongs to the calling thread and is restored on exit, also after an exception.  Every training ``Function`` records the mode of its forward and runs its
+    backward in it, whichever thread autograd uses and whether or not the ``with`` block has ended: a backward recomputes the forward it differentiates.
+
+    Narrower than autocast: everything in memory stays fp32 (activations, weights, gradients, scratch), and LayerNorm, the attention core (scores, softmax,
+    P V), RoPE, GELU, the bias and residual additions, bias gradients, the head (``train_head``), the losses and the optimizer compute in fp32 in either mode."""
+    if mode is None:
+        yield
+        return
+    if mode not in PRECISIONS:
+        raise ValueError(f"linear_precision: mode {mode!r}, expected one of {sorted(PRECISIONS)} or None")
+    lib = _lib.load()
+    prev = lib.must3r_hip_train_linear_mode(PRECISIONS[mode])
+    if prev < 0:
+        raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
+    try:
+        yield
+    finally:
+        lib.must3r_hip_train_linear_mode(prev)
 
 
 def _dev(t, what):

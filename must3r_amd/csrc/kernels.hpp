@@ -233,6 +233,19 @@ int head_linear(must3r_hip_ctx* c, DType dt, const void* hcat, const void* wcat,
 // must3r_hip_op_linear_dgrad_f32 on a packed copy of W0 over W1.  Used by must3r_hip_cross_sublayer_grad (dmem = dK Wk + dV Wv); fails with the ABI's error text.
 int launch_dgrad_seg_f32(const float* dZ, int ldz, const float* W0, const float* W1, int O0, float* out, int ldo, int M, int O, int K, hipStream_t s);
 
+// The training Linears on v_mfma_f32_16x16x32_bf16 (train_lin16.hip; must3r_hip_train_linear_mode, ABI 21 additive).  Storage stays fp32 everywhere; the operands
+// are rounded to bf16 (nearest even) on their way into LDS, the accumulator and the epilogues are fp32.  train_linear_bf16(): the calling thread's mode is
+// MUST3R_TRAIN_LINEAR_BF16.  The callers have checked their arguments by the fp32 forms' rules, which are these kernels' rules; the launchers only launch.
+//   launch_linear_bf16       run_linear of train_block.hip: out = A W^T + bias with the epilogue `epi` (train_lin.hpp)
+//   launch_dgrad_bf16        out[M][K] (ldo) = dZ[M][O] (ldz) [W0 [O0][K] ; W1 [O - O0][K]]; W1 = nullptr, O0 = O: one parameter
+//   launch_wgrad_parts_bf16  the partials of run_wgrad (train_head.hip): part [S][O][K], pdb [S][O] (column sums of the unrounded dZ), rows_per_split rows per split
+struct LinArgs;
+bool train_linear_bf16();
+int launch_linear_bf16(const char* who, int epi, const LinArgs& p, hipStream_t s);
+int launch_dgrad_bf16(const char* who, const float* dZ, int ldz, const float* W0, const float* W1, int O0, float* out, int ldo, int M, int O, int K, hipStream_t s);
+int launch_wgrad_parts_bf16(const float* dZ, int ldz, const float* A, int lda, int M, int O, int K, int rows_per_split, int S, int want_dw, float* part,
+                            float* pdb, hipStream_t s);
+
 // debug: mapping of ds_read_b64_tr_b16 (out: 256 shorts)
 int launch_tr_probe(short* out, hipStream_t s);
 

@@ -10,7 +10,8 @@
 //   linear_fwd_f32<EPI>   out[M, N] = A[M, K] W[N, K]^T + bias on v_mfma_f32_16x16x4_f32: the NT sibling of dgrad_kernel -- 128 x 128 tiles, 16-deep steps
 //                         over K through LDS, 4 waves of 64 x 64, the next K-tile fetched into registers under the products of the current one.  Both
 //                         operands are K-contiguous: both LDS tiles are [128][20] (rows padded to 20 floats: conflict-free).  Epilogues: bias; bias +
-//                         residual; bias + GELU (gelu(z), and z itself where a second pointer is given).
+//                         residual; bias + GELU (gelu(z), and z itself where a second pointer is given).  In MUST3R_TRAIN_LINEAR_BF16 mode run_linear
+//                         launches linear_fwd_bf16 of train_lin16.hip instead (same arguments, tiles and epilogues; train_lin.hpp holds what the two share).
 //   ln_fwd_f32            y = (x - mu) rstd gamma + beta, one wave per row, 16-byte accesses, the row in registers; its own two-pass statistics (the
 //                         formulas of row_stats_kernel in another summation order: the backward's statistics differ from these by rounding only).
 //   gelu_grad_f32         dz = dh gelu'(z), 16-byte accesses, in place over dh.
@@ -22,29 +23,21 @@
 
 #include "abi.hpp"
 #include "common.hpp"
+#include "kernels.hpp"
 #include "train_common.hpp"
+#include "train_lin.hpp"
 #include "train_ln.hpp"
 
 namespace m3r {
 
 constexpr int BM = 128, BN = 128, BK = 16, BP = 20;   // BP: LDS row stride (floats) of a [128][16] tile
-enum { LIN_BIAS = 0, LIN_BIAS_RES = 1, LIN_BIAS_GELU = 2 };
 
-__device__ __forceinline__ float gelu_cdf(float z) { return 0.5f * erfcf(-0.70710678118654752440f * z); }
-__device__ __forceinline__ float gelu_f32(float z) { return z * gelu_cdf(z); }
+// LinArgs, the epilogue names and gelu_cdf / gelu_f32: train_lin.hpp, shared with the bf16 form
 // exp(-z^2 / 2) is 0 from |z| = 14.6 on (fp32 underflow), so that the derivative is exactly Phi there: 1 or 0 beyond |z| = 40
 __device__ __forceinline__ float gelu_deriv_f32(float z) {
     const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
     return pdf > 0.f ? fmaf(z, pdf, gelu_cdf(z)) : gelu_cdf(z);
 }
-
-struct LinArgs {
-    const float* A; const float* W; const float* bias;
-    const float* res;   // LIN_BIAS_RES; may alias out
-    float* out;
-    float* zout;        // LIN_BIAS_GELU, optional: the pre-activation
-    int M, N, K, lda, ldc, ldres, ldz, n_tiles;
-};
 
 // K % 16 == 0; tail rows of A and W are zero-filled on load, tail rows and columns of the tile are not stored
 template <int EPI>
@@ -220,6 +213,7 @@ static int run_linear(const char* who, int epi, const float* A, int lda, const f
     const long long blocks = (long long)((M + BM - 1) / BM) * n_tiles;
     if (blocks > 0x7fffffffLL) return fail("%s: too many rows", who);
     const LinArgs p{A, W, bias, res, out, epi == LIN_BIAS_GELU ? zout : nullptr, M, N, K, lda, ldc, ldres, ldz, n_tiles};
+    if (train_linear_bf16()) return launch_linear_bf16(who, epi, p, s);   // must3r_hip_train_linear_mode: the same tiles on the 16-bit MFMA
     const dim3 grid((unsigned)blocks);
     if (epi == LIN_BIAS) hipLaunchKernelGGL(linear_fwd_f32<LIN_BIAS>, grid, dim3(256), 0, s, p);
     else if (epi == LIN_BIAS_RES) hipLaunchKernelGGL(linear_fwd_f32<LIN_BIAS_RES>, grid, dim3(256), 0, s, p);

@@ -20,6 +20,8 @@
 //                         per-lane column sums of dY x^ and dY, one partial per block.
 //                         <ADD> (ABI 21): dx = add + that, the residual of a pre-norm sublayer (train_block.hip); <false> is the kernel as it was.
 //   ln_grad_reduce_kernel sums the block partials in a fixed two-level order (16 interleaved slices, then the slices): dgamma, dbeta.
+// In MUST3R_TRAIN_LINEAR_BF16 mode (must3r_hip_train_linear_mode) the plain forms -- run_dgrad and run_wgrad without GATHER and without statistics, and
+// launch_dgrad_seg_f32 -- launch dgrad_bf16 / wgrad_bf16 of train_lin16.hip after the same checks; the gather forms (the head's own) stay fp32.
 // The split count of the weight gradient and the block count of the LayerNorm backward are functions of the row count alone.  No atomics:
 // every output element has one writer and a fixed order of operations.
 #include "abi.hpp"
@@ -412,6 +414,7 @@ static int run_dgrad(bool gather, const DzSrc& z, const float* W, float* out, in
     const int n_tiles = (K + HN - 1) / HN;
     const long long blocks = (long long)((M + HM - 1) / HM) * n_tiles;
     if (blocks > 0x7fffffffLL) return fail("linear_dgrad: too many rows");
+    if (!gather && train_linear_bf16()) return launch_dgrad_bf16("linear_dgrad", z.p, (int)z.ld, W, nullptr, O, out, K, M, O, K, s);
     if (gather) hipLaunchKernelGGL((dgrad_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
     else hipLaunchKernelGGL((dgrad_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
     if (hipGetLastError() != hipSuccess) return fail("linear_dgrad: launch failed");
@@ -426,7 +429,8 @@ static int run_wgrad(bool gather, const DzSrc& z, const float* A, int lda, const
     float* part = reinterpret_cast<float*>(scratch);
     float* pdb = reinterpret_cast<float*>(scratch + up256((size_t)S * O * K * 4));
     const dim3 grid((unsigned)(o_tiles * n_tiles * S));
-    if (gather) hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
+    if (!gather && !stats && train_linear_bf16()) M3R_RUN(launch_wgrad_parts_bf16(z.p, (int)z.ld, A, lda, M, O, K, rps, S, want_dw, part, pdb, s));
+    else if (gather) hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
     else hipLaunchKernelGGL(wgrad_kernel<false>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(O), dim3(256), 0, s, part, pdb, S, O, K, gamma, beta, gather ? 1 : 0, dW, db);
     if (hipGetLastError() != hipSuccess) return fail("linear_wgrad: launch failed");
@@ -501,6 +505,7 @@ int launch_dgrad_seg_f32(const float* dZ, int ldz, const float* W0, const float*
     const int n_tiles = (K + HN - 1) / HN;
     const long long blocks = (long long)((M + HM - 1) / HM) * n_tiles;
     if (blocks > 0x7fffffffLL) return fail("linear_dgrad (two segments): too many rows");
+    if (train_linear_bf16()) return launch_dgrad_bf16("linear_dgrad (two segments)", dZ, ldz, W0, W1, O0, out, ldo, M, O, K, s);
     const DzSrc z{dZ, ldz, 0, 0, 0, 0};
     hipLaunchKernelGGL((dgrad_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, z, W0, out, M, O, K, n_tiles, DgSeg{W1, O0, ldo});
     if (hipGetLastError() != hipSuccess) return fail("linear_dgrad (two segments): launch failed");

@@ -9,7 +9,11 @@ two of the three of ``CachedDecoderBlock``) under ``torch.autograd``::
     attention sublayer   x + proj(attn(rope(qkv(norm1 x))))           ``attention_sublayer``
     MLP sublayer         x + fc2(gelu(fc1(norm2 x)))                  ``mlp_sublayer``
 
-Everything runs in fp32 on the fp32 MFMA (``must3r_hip_*_sublayer_forward`` / ``_grad``, include/must3r_hip.h ABI 21).  A forward saves its inputs and
+Everything is stored in fp32 and, by default, runs on the fp32 MFMA (``must3r_hip_*_sublayer_forward`` / ``_grad``, include/must3r_hip.h ABI 21).  Inside
+``with linear_precision("bf16"):`` the products of the Linears (``linear``, qkv, proj, fc1, fc2 and their data and weight gradients) round their operands to
+bf16 and run on the 16-bit MFMA with fp32 accumulation, as ``--amp bf16`` does for ``nn.Linear``; LayerNorm, the attention core and its softmax, RoPE, GELU,
+the bias and residual additions and the bias gradients stay fp32 in either mode.  Each Function records ``current_precision()`` in its forward and runs its
+backward in that mode, wherever and whenever ``backward()`` is called.  A forward saves its inputs and
 nothing else; the backward recomputes the sublayer's forward into scratch and differentiates it.  Only the gradients ``needs_input_grad`` asks for are
 computed (frozen weights: no weight-gradient launch; frozen norms: no column sums; a frozen ``x`` and frozen norms: no LayerNorm backward).  ``linear`` and
 ``layer_norm`` are the pieces on their own.  First order only (``once_differentiable``); gradients come back in the shape and dtype of their inputs; CPU
@@ -24,6 +28,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _new, _Proj, _ptr, _rows, _scratch, _stream
+from ._train_common import current_precision, linear_precision   # noqa: F401  (re-exported: ``with train_block.linear_precision("bf16"):``)
 from .train_attention import _check_table, _table, n_groups, self_views
 
 ROPE_NPOS = 256          # positions of the default table (a 4096-pixel side), as the native model's
@@ -208,13 +213,15 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight, bias)
+        ctx.precision = current_precision()
         return linear_forward(_rows(x), _f32(weight), _f32(bias)).view(*x.shape[:-1], weight.shape[0])
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         x, weight, bias = ctx.saved_tensors
-        grads = linear_grad(_rows(x), _f32(weight), _rows(grad_out), want=tuple(ctx.needs_input_grad[:3]))
+        with linear_precision(ctx.precision):
+            grads = linear_grad(_rows(x), _f32(weight), _rows(grad_out), want=tuple(ctx.needs_input_grad[:3]))
         return tuple(_back(grads, (x, weight, bias)))
 
 
@@ -237,14 +244,15 @@ class _Mlp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b, eps):
         ctx.save_for_backward(x, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b)
-        ctx.eps = eps
+        ctx.eps, ctx.precision = eps, current_precision()
         return mlp_forward(_rows(x), *(_f32(t) for t in (norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b)), eps).view(x.shape)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         saved = ctx.saved_tensors
-        grads = mlp_grad(_rows(saved[0]), *(_f32(t) for t in saved[1:]), _rows(grad_out), ctx.eps, want=tuple(ctx.needs_input_grad[:7]))
+        with linear_precision(ctx.precision):
+            grads = mlp_grad(_rows(saved[0]), *(_f32(t) for t in saved[1:]), _rows(grad_out), ctx.eps, want=tuple(ctx.needs_input_grad[:7]))
         return (*_back(grads, saved), None)
 
 
@@ -252,20 +260,21 @@ class _Attn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, pos, tab, rope_tab, eps):
         ctx.save_for_backward(x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, pos)
-        ctx.tab, ctx.rope_tab, ctx.eps = tab, rope_tab, eps
+        ctx.tab, ctx.rope_tab, ctx.eps, ctx.precision = tab, rope_tab, eps, current_precision()
         return attn_forward(_rows(x), pos, tab, rope_tab, *(_f32(t) for t in (norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b)), eps).view(x.shape)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         *saved, pos = ctx.saved_tensors
-        grads = attn_grad(_rows(saved[0]), pos, ctx.tab, ctx.rope_tab, *(_f32(t) for t in saved[1:]), _rows(grad_out), ctx.eps,
-                          want=tuple(ctx.needs_input_grad[:7]))
+        with linear_precision(ctx.precision):
+            grads = attn_grad(_rows(saved[0]), pos, ctx.tab, ctx.rope_tab, *(_f32(t) for t in saved[1:]), _rows(grad_out), ctx.eps,
+                              want=tuple(ctx.needs_input_grad[:7]))
         return (*_back(grads, saved), None, None, None, None)
 
 
 def linear(x, weight, bias):
-    """``x @ weight.T + bias`` in fp32 on the fp32 MFMA; x [..., K] with K % 16 == 0, weight [N, K] with N % 4 == 0, bias [N]."""
+    """``x @ weight.T + bias`` in fp32 on the fp32 MFMA (under ``linear_precision("bf16")``: bf16 operands, fp32 accumulation and bias); x [..., K] with K % 16 == 0, weight [N, K] with N % 4 == 0, bias [N]."""
     K = _check_x(x, "linear: x")
     _check_params("linear", K, weight=(weight, (int(weight.shape[0]), K)), bias=(bias, (int(weight.shape[0]),)))
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, weight, bias)):

@@ -17,7 +17,9 @@ in one launch each way (``feedback_prepare``: ``must3r_hip_feedback_prepare_forw
 followed by the k | v Linears in the ``kv`` mode; the results are ``torch.cat``-ed behind the old memory.  Without feedback the post-feedback rows are the
 ``prepare_y`` rows already computed for the keys: they are reused and nothing is launched.
 
-Everything runs in fp32; only the gradients ``needs_input_grad`` asks for are computed (frozen parts cost no launches); first order only; CPU tensors
+Everything runs in fp32 -- or, inside ``with train_block.linear_precision("bf16"):``, with the products of every Linear but the head's on the 16-bit MFMA
+(bf16 operands, fp32 accumulation; the norms, the attention cores, the feedback add, the head and all storage stay fp32; ``backward()`` may be called after
+the block has ended: each Function runs its backward in the mode of its forward).  Only the gradients ``needs_input_grad`` asks for are computed (frozen parts cost no launches); first order only; CPU tensors
 raise.  List inputs (``forward_list``) and mixed aspect ratios are not built; memory dropout is ``train_dropout.CausalMUSt3R``, which hands the key masks of a
 call to this forward.  The memory is concatenated per call, not appended in place.
 """
@@ -30,6 +32,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from . import train_block as TB
 from ._train_common import HEAD, _Affine, _back, _check_params, _check_x, _dev, _f32, _new, _Proj, _rows, _scratch, _stream
+from ._train_common import current_precision, linear_precision
 from .train_attention import _table, memory_views, self_views
 from .train_block import ROPE_NPOS, _MlpParams
 from .train_cross import MEMORY_MODES, CachedDecoderBlock, memory_rows
@@ -180,12 +183,17 @@ class _FeedbackOffset(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, w1, b1, w2, b2, eps):
         ctx.save_for_backward(x, norm_w, norm_b, w1, b1, *([w2, b2] if w2 is not None else []))
-        ctx.eps, ctx.mlp = eps, w2 is not None
+        ctx.eps, ctx.mlp, ctx.precision = eps, w2 is not None, current_precision()
         return _offset_forward(x, norm_w, norm_b, w1, b1, w2, b2, eps)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
+        with linear_precision(ctx.precision):   # the Linears recomputed and differentiated below multiply as the forward's did
+            return _FeedbackOffset._backward(ctx, grad_out)
+
+    @staticmethod
+    def _backward(ctx, grad_out):
         saved = ctx.saved_tensors
         x, g, b, w1, b1 = (_f32(t) for t in saved[:5])
         need = ctx.needs_input_grad
