@@ -1030,7 +1030,7 @@ int must3r_hip_optim_adamw(const must3r_hip_optim_args* a, void* scratch, size_t
  *   What stays fp32 arithmetic in either mode: the bias, residual and GELU epilogues (on the fp32 accumulator), the bias gradient (column sums of the unrounded
  *   dZ), the reduction of the weight-gradient partials, LayerNorm forward and backward, the attention core (scores, softmax, P V and their gradients), RoPE, the
  *   residual stream, the head (must3r_hip_head_forward / _head_grad / _op_head_linear: its own split-precision forms and the fp32 gather forms), the loss family
- *   and the optimizer.  bf16 attention and bf16 storage of activations are not built.
+ *   and the optimizer.  The attention core has a mode of its own (must3r_hip_train_attention_mode below); bf16 storage of activations is not built.
  *   In MUST3R_TRAIN_LINEAR_F32 mode (the default of every thread) the four functions launch exactly the kernels of ABI 21 before this entry point existed.
  *   The bf16 kernels use no atomics either: one writer per element, a fixed order of additions, a row of out / dX independent of the other rows.
  * A backward pass that recomputes a sublayer's forward must run in the mode its forward ran in (must3r_amd records it per autograd node). */
@@ -1039,6 +1039,27 @@ int must3r_hip_optim_adamw(const must3r_hip_optim_args* a, void* scratch, size_t
 /* Per host thread; default F32.  Sets the mode in which must3r_hip_op_linear_f32, _dgrad_f32, _wgrad_f32 and every training entry point
    built on them multiply; returns the previous mode.  mode = -1 only queries.  Any other value: returns -1, last error set, nothing changed. */
 int must3r_hip_train_linear_mode(int mode);
+
+/* ABI 21, additive.  The matrix products of the training attention core on the 16-bit MFMA, switched like the Linears above: by a mode of the calling host
+ * thread (the reference trains under torch.autocast(bfloat16), where the attention products run in bf16).
+ *   In MUST3R_TRAIN_ATTENTION_BF16 mode must3r_hip_attn_forward_f32, must3r_hip_attn_grad, must3r_hip_attn_masked_forward and must3r_hip_attn_masked_grad, and
+ *   through them the attention sublayer and the cross sublayer (masked forms included), launch the bf16 siblings of their three kernels: the same view table,
+ *   key groups, skip ranges, mask bits, scratch layout (lse2 and delta fp32), grids and launch order; no descriptor, scratch query or stream rule changes.
+ *   Everything in memory stays fp32 (the `_f32` in the names is the storage type).  With s = 1/8 and ^ = rounded to bf16 (nearest even, NaN and inf kept) in
+ *   registers, fp32 accumulation throughout:
+ *     S = s (Q^ K^T^), scale and log2 e applied in fp32 after the product; online softmax in fp32, the row sum l adds the unrounded p;
+ *     O = (sum P^ V^) / l;  lse as in fp32 mode;  delta = dO . O with the unrounded dO;
+ *     P = exp2(S c - lse2) (0 for an invalid key);  dV = P^T^ dO^;  dP = dO^ V^T^;  dS = P (dP - delta) in fp32;  dQ = s dS^ K^;  dK = s dS^T^ Q^.
+ *   Rows without a valid key keep their rules (O = 0, lse = -inf, no contribution, dQ = 0).  No atomics, one writer per element, a fixed order of additions;
+ *   a view's O and dQ and a scene's dK and dV are the same bits alone and in a batch.
+ *   In MUST3R_TRAIN_ATTENTION_F32 mode (the default of every thread) the four functions launch exactly the kernels they launched before this entry point
+ *   existed.  The two modes are independent: must3r_hip_train_linear_mode does not touch the attention core and this mode does not touch a Linear.
+ *   bf16 storage of activations is not built; the 16-bit inference forward (must3r_hip_attention) is a different kernel and takes no masks.
+ * A backward pass must run in the mode its forward ran in (must3r_amd records it per autograd node). */
+#define MUST3R_TRAIN_ATTENTION_F32  0
+#define MUST3R_TRAIN_ATTENTION_BF16 1
+/* Per host thread; default F32.  Returns the previous mode.  mode = -1 only queries.  Any other value: returns -1, last error set, nothing changed. */
+int must3r_hip_train_attention_mode(int mode);
 
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);

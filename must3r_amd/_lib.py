@@ -24,6 +24,7 @@ RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEARE
 IMG_U8_HWC, IMG_F32_CHW = 0, 1
 LIN_BIAS, LIN_BIAS_RES, LIN_BIAS_GELU = range(3)
 TRAIN_LINEAR_F32, TRAIN_LINEAR_BF16 = 0, 1   # must3r_hip_train_linear_mode
+TRAIN_ATTENTION_F32, TRAIN_ATTENTION_BF16 = 0, 1   # must3r_hip_train_attention_mode
 
 class Config(C.Structure):
     _fields_ = [("img_size", C.c_int32), ("patch_size", C.c_int32),
@@ -341,6 +342,7 @@ PROTOTYPES = {
     "must3r_hip_optim_norm": (i32, [P(OptimArgs), vp, sz]),
     "must3r_hip_optim_adamw": (i32, [P(OptimArgs), vp, sz]),
     "must3r_hip_train_linear_mode": (i32, [i32]),
+    "must3r_hip_train_attention_mode": (i32, [i32]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -1,6 +1,7 @@
 """What the training modules (``train_head``, ``train_attention``, ``train_block``, ``train_cross``, ``train_decoder``) share on the host: the checks that a tensor is on the GPU
 and has the expected shape, the fp32 views handed to the library, scratch and output allocation, the one calling pattern of the sublayer entry points, and
-the two parameter holders, and the precision switch of the training Linears (``linear_precision`` / ``current_precision``, re-exported by ``train_block``).
+the two parameter holders, and the precision switches of the training Linears and of the attention core (``linear_precision`` / ``current_precision``,
+``attention_precision`` / ``current_attention_precision`` and ``amp``, re-exported by ``train_block``).
 Everything else here is private to the package."""
 import contextlib
 import ctypes as C
@@ -47,6 +48,52 @@ def linear_precision(mode):
         yield
     finally:
         lib.must3r_hip_train_linear_mode(prev)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the precision of the attention core's products (must3r_hip_train_attention_mode), independent of the Linears' mode above
+# ---------------------------------------------------------------------------------------------------------------------------------------
+ATTENTION_PRECISIONS = {"fp32": _lib.TRAIN_ATTENTION_F32, "bf16": _lib.TRAIN_ATTENTION_BF16}
+_ATTENTION_PRECISION_NAMES = {v: k for k, v in ATTENTION_PRECISIONS.items()}
+
+
+def current_attention_precision():
+    """``"fp32"`` or ``"bf16"``: the mode in which the calling thread's training attention core multiplies."""
+    return _ATTENTION_PRECISION_NAMES[_lib.load().must3r_hip_train_attention_mode(-1)]
+
+
+@contextlib.contextmanager
+def attention_precision(mode):
+    """``with attention_precision("bf16"):`` -- inside, the attention core of the training path (``train_attention.attention``, the attention and cross
+    sublayers, masked forms included, and everything composed of them) rounds Q, K, V and dO, and P and dS as operands of the products that follow them, to
+    bf16 in registers and multiplies on the 16-bit MFMA with fp32 accumulation, as the core does under ``torch.autocast(dtype=torch.bfloat16)``; the scores,
+    the softmax, its row sum, lse, delta and dS are computed in fp32 and all storage stays fp32.  ``"fp32"`` is the default of every thread; ``None`` leaves the
+    mode alone.  The contract is ``linear_precision``'s: the mode belongs to the calling thread, is restored on exit (also after an exception), and every
+    ``Function`` whose backward reaches the core records the mode of its forward and runs its backward in it.  The two modes do not touch each other;
+    ``amp`` enters both."""
+    if mode is None:
+        yield
+        return
+    if mode not in ATTENTION_PRECISIONS:
+        raise ValueError(f"attention_precision: mode {mode!r}, expected one of {sorted(ATTENTION_PRECISIONS)} or None")
+    lib = _lib.load()
+    prev = lib.must3r_hip_train_attention_mode(ATTENTION_PRECISIONS[mode])
+    if prev < 0:
+        raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
+    try:
+        yield
+    finally:
+        lib.must3r_hip_train_attention_mode(prev)
+
+
+@contextlib.contextmanager
+def amp(mode):
+    """``with amp("bf16"):`` -- the recipe's ``--amp bf16`` for the training path: ``linear_precision(mode)`` and ``attention_precision(mode)`` together
+    (``"fp32"``, ``"bf16"``, or ``None`` for no change)."""
+    if mode is not None and mode not in PRECISIONS:
+        raise ValueError(f"amp: mode {mode!r}, expected one of {sorted(PRECISIONS)} or None")
+    with linear_precision(mode), attention_precision(mode):
+        yield
 
 
 def _dev(t, what):

@@ -35,41 +35,14 @@
 #include "abi.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
+#include "train_attn.hpp"
 #include "train_common.hpp"
 
 namespace m3r {
 
-constexpr int TA_T = 64, TA_LD = 68;             // tile rows / head size, LDS row stride in floats
-constexpr float TA_SCALE = 0.125f;
-constexpr float TA_C = 0.125f * 1.4426950408889634f;   // scale * log2(e)
-constexpr float TA_LN2 = 0.6931471805599453f;
+constexpr int TA_LD = 68;   // LDS row stride in floats (TA_T, the constants, TaArgs, the tile fetch and the key rules: train_attn.hpp, shared with train_attn16.hip)
 
-struct TaGroup { int kv_row0, extent, first, count; };   // views list[first .. first + count) read key rows [kv_row0, kv_row0 + extent)
-
-struct TaArgs {
-    const float* Q; const float* K; const float* V; const float* dO;
-    int ldq, ldk, ldv, lddo, heads;
-    const AttnView* views;
-    const TaGroup* groups; const int* list;
-    float* O; int ldo;
-    float* lse;                  // [rows][heads], natural log (public)
-    float* lse2; float* delta;   // [rows][heads], scratch of the backward
-    float* dQ; float* dK; float* dV;
-    int lddq, lddk, lddv;
-    // MASK instantiations only: the packed key masks [mask_rows][mask_ld], and per view of the table its row (-1: none)
-    const uint32_t* mask; const int* vmask; int mask_ld;
-};
-
-// rows [0, rows_valid) of a [.][64] slab at src (row stride ld) -> registers (4 float4 per thread), the rest zero; then registers -> dst [64][TA_LD].
-// The next tile is fetched while the current one is multiplied, so that its global-memory latency hides under the MFMAs.
-__device__ __forceinline__ void ta_fetch_tile(f32x4 (&x)[4], const float* __restrict__ src, int ld, int rows_valid, int tid) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int idx = e * 256 + tid, r = idx >> 4, c = (idx & 15) * 4;
-        x[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (r < rows_valid) x[e] = *reinterpret_cast<const f32x4*>(src + (size_t)r * ld + c);
-    }
-}
+// registers (ta_fetch_tile) -> dst [64][TA_LD]
 __device__ __forceinline__ void ta_put_tile(float* dst, const f32x4 (&x)[4], int tid) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -121,40 +94,6 @@ __device__ __forceinline__ float ta_sum16(float v) {
 #pragma unroll
     for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);
     return v;
-}
-__device__ __forceinline__ bool ta_valid(const AttnView& v, int j) { return j < v.nk && !(j >= v.skip_lo && j < v.skip_hi); }
-__device__ __forceinline__ bool ta_tile_skipped(const AttnView& v, int k0) { return k0 >= v.nk || (k0 >= v.skip_lo && k0 + TA_T <= v.skip_hi); }
-// the first key tile at or after k0 that the view reads (>= nk: none)
-__device__ __forceinline__ int ta_next_tile(const AttnView& v, int k0) {
-    while (k0 < v.nk && ta_tile_skipped(v, k0)) k0 += TA_T;
-    return k0;
-}
-
-// MASK: the mask row of a view of the table, nullptr where it names none
-template <bool MASK>
-__device__ __forceinline__ const uint32_t* ta_mask_row(const TaArgs& a, int view) {
-    if (!MASK) return nullptr;
-    const int r = a.vmask[view];
-    return r >= 0 ? a.mask + (size_t)r * a.mask_ld : nullptr;
-}
-// bit t: key k0 + t of the tile at k0 < nk passes the mask row (all ones without a row); the bits of keys at or past nk are cleared.  k0 is a multiple of 64 and
-// 32 mask_ld >= nk with mask_ld even, so that the two words are inside the row and 8-byte aligned.
-__device__ __forceinline__ uint64_t ta_tile_bits(const uint32_t* mrow, int k0, int nk) {
-    if (!mrow) return ~0ull;
-    const uint2 w = *reinterpret_cast<const uint2*>(mrow + (k0 >> 5));
-    const uint64_t b = (uint64_t)w.y << 32 | w.x;
-    const int left = nk - k0;
-    return left >= 64 ? b : b & ((1ull << left) - 1);
-}
-template <bool MASK>
-__device__ __forceinline__ bool ta_tile_skipped_m(const AttnView& v, int k0, const uint32_t* mrow) {
-    if (ta_tile_skipped(v, k0)) return true;
-    return MASK && ta_tile_bits(mrow, k0, v.nk) == 0;
-}
-template <bool MASK>
-__device__ __forceinline__ int ta_next_tile_m(const AttnView& v, int k0, const uint32_t* mrow) {
-    while (k0 < v.nk && ta_tile_skipped_m<MASK>(v, k0, mrow)) k0 += TA_T;
-    return k0;
 }
 
 template <bool MASK>
@@ -612,7 +551,8 @@ static int ta_forward(const char* who, const must3r_hip_attn_train_args* a, cons
     k.dO = nullptr; k.lse2 = nullptr; k.delta = nullptr;
     k.O = a->O; k.ldo = a->ldo; k.lse = a->lse;
     const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views);
-    if (masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<true>), qgrid, dim3(256), 0, s, k);
+    if (train_attention_bf16()) launch_attn_fwd_bf16(masked, qgrid, k, s);   // must3r_hip_train_attention_mode: the same launch on the 16-bit MFMA
+    else if (masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<true>), qgrid, dim3(256), 0, s, k);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<false>), qgrid, dim3(256), 0, s, k);
     if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
     return 0;
@@ -634,7 +574,11 @@ static int ta_grad(const char* who, const must3r_hip_attn_train_args* a, const T
     const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views), kgrid((P.max_extent + TA_T - 1) / TA_T, a->heads, (unsigned)P.groups.size());
     const bool run_q = P.max_nq > 0, run_kv = want_kv && P.max_extent > 0;
     // lse2 and delta into scratch, then dK | dV, then dQ
-    if (masked) {
+    if (train_attention_bf16()) {   // must3r_hip_train_attention_mode: the same three launches on the 16-bit MFMA
+        if (run_q) launch_attn_fwd_bf16(masked, qgrid, k, s);
+        if (run_kv) launch_attn_dkv_bf16(masked, kgrid, k, s);
+        if (a->dQ && run_q) launch_attn_dq_bf16(masked, qgrid, k, s);
+    } else if (masked) {
         if (run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<true>), qgrid, dim3(256), 0, s, k);
         if (run_kv) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dkv_f32<true>), kgrid, dim3(256), 0, s, k);
         if (a->dQ && run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dq_f32<true>), qgrid, dim3(256), 0, s, k);

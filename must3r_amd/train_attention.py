@@ -9,7 +9,9 @@
 The fp32 forward (``must3r_hip_attn_forward_f32``) and the backward (``must3r_hip_attn_grad``, include/must3r_hip.h ABI 20) run fp32 operands on the fp32
 MFMA; the forward saves q, k, v and the host table and nothing else, the backward recomputes the scores.  ``dtype=_lib.F16`` / ``_lib.BF16`` runs the
 native inference forward (``must3r_hip_op_attention``) on cast operands instead, so that a fine-tuned model sees the arithmetic it will be served with; the
-backward is the same fp32 one.  Only the gradients ``needs_input_grad`` asks for are computed.  dK and dV sum over every view that reads a key row:
+backward is the same fp32 one.  Inside ``with attention_precision("bf16"):`` (``must3r_hip_train_attention_mode``, a mode of the calling thread) both
+entry points, masked forms included, run their bf16 siblings on the 16-bit MFMA (csrc/train_attn16.hip): Q, K, V, dO, and P and dS as operands, rounded to
+bf16 in registers, fp32 softmax, accumulation and storage; a backward runs in the mode of its forward.  Only the gradients ``needs_input_grad`` asks for are computed.  dK and dV sum over every view that reads a key row:
 views that share key rows must share ``kv_row0`` (one key group; the decoder's tables do), and overlapping groups are refused.  A query row without a
 valid key has O = 0 and zero gradients (the reference would give NaN).  First order only (``once_differentiable``); CPU tensors raise.
 
@@ -26,6 +28,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._train_common import HEAD, _dev, _ld, _ptr, _stream, _strided_rows
+from ._train_common import attention_precision, current_attention_precision   # noqa: F401  (re-exported: ``with train_attention.attention_precision("bf16"):``)
 
 
 def self_views(n_scenes, views_per_scene, n):
@@ -242,7 +245,7 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, tab, heads, dtype, mask=None):
         ctx.save_for_backward(q, k, v)
-        ctx.tab, ctx.heads, ctx.mask = tab, heads, mask
+        ctx.tab, ctx.heads, ctx.mask, ctx.attn_precision = tab, heads, mask, current_attention_precision()
         return _forward(q, k, v, tab, heads, dtype, mask)
 
     @staticmethod
@@ -251,7 +254,8 @@ class _Attention(torch.autograd.Function):
         q, k, v = ctx.saved_tensors
         heads = ctx.heads
         f = [_fp32_rows(t, n, heads) for t, n in ((q, "q"), (k, "k"), (v, "v"), (grad_out, "the upstream gradient"))]
-        grads = attention_grad(*f, ctx.tab, heads, want=tuple(ctx.needs_input_grad[:3]), mask=ctx.mask)
+        with attention_precision(ctx.attn_precision):   # autograd's thread starts in the default mode, and backward() may run after the block has ended
+            grads = attention_grad(*f, ctx.tab, heads, want=tuple(ctx.needs_input_grad[:3]), mask=ctx.mask)
         out = [None if g is None else g.to(t.dtype) for g, t in zip(grads, (q, k, v))]
         return (*out, None, None, None, None)
 

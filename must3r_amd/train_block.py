@@ -12,8 +12,9 @@ two of the three of ``CachedDecoderBlock``) under ``torch.autograd``::
 Everything is stored in fp32 and, by default, runs on the fp32 MFMA (``must3r_hip_*_sublayer_forward`` / ``_grad``, include/must3r_hip.h ABI 21).  Inside
 ``with linear_precision("bf16"):`` the products of the Linears (``linear``, qkv, proj, fc1, fc2 and their data and weight gradients) round their operands to
 bf16 and run on the 16-bit MFMA with fp32 accumulation, as ``--amp bf16`` does for ``nn.Linear``; LayerNorm, the attention core and its softmax, RoPE, GELU,
-the bias and residual additions and the bias gradients stay fp32 in either mode.  Each Function records ``current_precision()`` in its forward and runs its
-backward in that mode, wherever and whenever ``backward()`` is called.  A forward saves its inputs and
+the bias and residual additions and the bias gradients stay fp32 in either mode.  ``with attention_precision("bf16"):`` does the same for the products of
+the attention core (csrc/train_attn16.hip; the softmax stays fp32), and ``with amp("bf16"):`` enters both.  Each Function records ``current_precision()``
+(and, where its backward reaches the core, ``current_attention_precision()``) in its forward and runs its backward in that mode, wherever and whenever ``backward()`` is called.  A forward saves its inputs and
 nothing else; the backward recomputes the sublayer's forward into scratch and differentiates it.  Only the gradients ``needs_input_grad`` asks for are
 computed (frozen weights: no weight-gradient launch; frozen norms: no column sums; a frozen ``x`` and frozen norms: no LayerNorm backward).  ``linear`` and
 ``layer_norm`` are the pieces on their own.  First order only (``once_differentiable``); gradients come back in the shape and dtype of their inputs; CPU
@@ -29,6 +30,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _new, _Proj, _ptr, _rows, _scratch, _stream
 from ._train_common import current_precision, linear_precision   # noqa: F401  (re-exported: ``with train_block.linear_precision("bf16"):``)
+from ._train_common import amp, attention_precision, current_attention_precision   # noqa: F401  (re-exported: ``with train_block.amp("bf16"):``)
 from .train_attention import _check_table, _table, n_groups, self_views
 
 ROPE_NPOS = 256          # positions of the default table (a 4096-pixel side), as the native model's
@@ -260,14 +262,14 @@ class _Attn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, pos, tab, rope_tab, eps):
         ctx.save_for_backward(x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, pos)
-        ctx.tab, ctx.rope_tab, ctx.eps, ctx.precision = tab, rope_tab, eps, current_precision()
+        ctx.tab, ctx.rope_tab, ctx.eps, ctx.precision, ctx.attn_precision = tab, rope_tab, eps, current_precision(), current_attention_precision()
         return attn_forward(_rows(x), pos, tab, rope_tab, *(_f32(t) for t in (norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b)), eps).view(x.shape)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         *saved, pos = ctx.saved_tensors
-        with linear_precision(ctx.precision):
+        with linear_precision(ctx.precision), attention_precision(ctx.attn_precision):
             grads = attn_grad(_rows(saved[0]), pos, ctx.tab, ctx.rope_tab, *(_f32(t) for t in saved[1:]), _rows(grad_out), ctx.eps,
                               want=tuple(ctx.needs_input_grad[:7]))
         return (*_back(grads, saved), None, None, None, None)

@@ -15,7 +15,8 @@ reference's: ``norm_y`` (the memory holds ``norm_y`` of the tokens), ``raw`` (th
 
 Everything runs in fp32 on the fp32 MFMA (``must3r_hip_cross_sublayer_forward`` / ``_grad``, include/must3r_hip.h "ABI 21, additive"; the stream travels in
 the descriptor).  Under ``train_block.linear_precision("bf16")`` the products of projq, projk, projv and proj and of their gradients (``dmem = dK Wk + dV Wv``
-included) take bf16 operands on the 16-bit MFMA; ``norm2``, ``norm_y``, the attention core, the biases and the residual stay fp32, and so does all storage.  A forward saves its inputs and nothing else; the backward recomputes the sublayer's forward into scratch and differentiates it.  Only the
+included) take bf16 operands on the 16-bit MFMA; ``norm2``, ``norm_y``, the attention core, the biases and the residual stay fp32, and so does all storage;
+under ``train_block.attention_precision("bf16")`` (or ``train_block.amp``) the products of the attention core do the same, its softmax staying fp32.  A forward saves its inputs and nothing else; the backward recomputes the sublayer's forward into scratch and differentiates it.  Only the
 gradients ``needs_input_grad`` asks for are computed (a detached memory and frozen ``projk`` / ``projv``: no dK / dV launch; a frozen ``x``, ``norm2`` and
 ``projq``: no dQ launch).  First order only (``once_differentiable``); gradients come back in the shape and dtype of their inputs; CPU tensors raise.
 
@@ -33,7 +34,7 @@ from . import _lib
 from . import train_block as TB
 from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _ld, _new, _Proj, _ptr, _rows, _scratch, _stream
 from ._train_common import _strided_rows as _mem_rows
-from ._train_common import current_precision, linear_precision
+from ._train_common import attention_precision, current_attention_precision, current_precision, linear_precision
 from .train_attention import _check_table, _mask, _table, n_groups
 from .train_attention import self_views as _self_views
 from .train_block import ROPE_NPOS, _AttnParams, _MlpParams
@@ -113,7 +114,7 @@ class _Cross(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b, tab, eps, mask=None):
         ctx.save_for_backward(x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)
-        ctx.tab, ctx.eps, ctx.mask, ctx.precision = tab, eps, mask, current_precision()
+        ctx.tab, ctx.eps, ctx.mask, ctx.precision, ctx.attn_precision = tab, eps, mask, current_precision(), current_attention_precision()
         width = int(mem.shape[1])
         return cross_forward(_rows(x), _mem_rows(mem, width), tab, *(_opt(t) for t in (norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)), eps,
                              mask).view(x.shape)
@@ -123,7 +124,7 @@ class _Cross(torch.autograd.Function):
     def backward(ctx, grad_out):
         saved = ctx.saved_tensors
         x, mem = saved[0], saved[1]
-        with linear_precision(ctx.precision):
+        with linear_precision(ctx.precision), attention_precision(ctx.attn_precision):
             grads = cross_grad(_rows(x), _mem_rows(mem, int(mem.shape[1])), ctx.tab, *(_opt(t) for t in saved[2:]), _rows(grad_out), ctx.eps,
                                want=tuple(ctx.needs_input_grad[:12]), mask=ctx.mask)
         # CROSS_OUTPUTS is in the order of the inputs

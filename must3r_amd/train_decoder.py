@@ -19,7 +19,8 @@ followed by the k | v Linears in the ``kv`` mode; the results are ``torch.cat``-
 
 Everything runs in fp32 -- or, inside ``with train_block.linear_precision("bf16"):``, with the products of every Linear but the head's on the 16-bit MFMA
 (bf16 operands, fp32 accumulation; the norms, the attention cores, the feedback add, the head and all storage stay fp32; ``backward()`` may be called after
-the block has ended: each Function runs its backward in the mode of its forward).  Only the gradients ``needs_input_grad`` asks for are computed (frozen parts cost no launches); first order only; CPU tensors
+the block has ended: each Function runs its backward in the mode of its forward); ``train_block.attention_precision("bf16")`` moves the products of the
+attention cores there as well, and ``train_block.amp("bf16")`` is both.  Only the gradients ``needs_input_grad`` asks for are computed (frozen parts cost no launches); first order only; CPU tensors
 raise.  List inputs (``forward_list``) and mixed aspect ratios are not built; memory dropout is ``train_dropout.CausalMUSt3R``, which hands the key masks of a
 call to this forward.  The memory is concatenated per call, not appended in place.
 """
