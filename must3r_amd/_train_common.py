@@ -14,19 +14,43 @@ from . import _lib
 HEAD = 64
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# the precision of the training Linears' products (must3r_hip_train_linear_mode, include/must3r_hip.h "ABI 21, additive")
+# the two per-thread precision switches (include/must3r_hip.h "ABI 21, additive"), independent of each other: the training Linears' products
+# (must3r_hip_train_linear_mode) and the attention core's (must3r_hip_train_attention_mode)
 # ---------------------------------------------------------------------------------------------------------------------------------------
+def _precision_switch(name, entry, modes, current_doc, doc):
+    """``(current, switch)`` of the per-thread mode behind the library's ``entry``: ``current()`` names the calling thread's mode, ``switch(mode)`` is the context
+    manager ``name`` that enters one of ``modes`` (``None``: leaves the mode alone, and calls nothing) and restores the previous mode on exit."""
+    names = {v: k for k, v in modes.items()}
+
+    def current():
+        return names[getattr(_lib.load(), entry)(-1)]
+
+    @contextlib.contextmanager
+    def switch(mode):
+        if mode is None:
+            yield
+            return
+        if mode not in modes:
+            raise ValueError(f"{name}: mode {mode!r}, expected one of {sorted(modes)} or None")
+        lib = _lib.load()
+        swap = getattr(lib, entry)
+        prev = swap(modes[mode])
+        if prev < 0:
+            raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
+        try:
+            yield
+        finally:
+            swap(prev)
+
+    current.__doc__, switch.__doc__ = current_doc, doc
+    switch.__name__ = switch.__qualname__ = name
+    return current, switch
+
+
 PRECISIONS = {"fp32": _lib.TRAIN_LINEAR_F32, "bf16": _lib.TRAIN_LINEAR_BF16}
-_PRECISION_NAMES = {v: k for k, v in PRECISIONS.items()}
-
-
-def current_precision():
-    """``"fp32"`` or ``"bf16"``: the mode in which the calling thread's training Linears multiply."""
-    return _PRECISION_NAMES[_lib.load().must3r_hip_train_linear_mode(-1)]
-
-
-@contextlib.contextmanager
-def linear_precision(mode):
+current_precision, linear_precision = _precision_switch(
+    "linear_precision", "must3r_hip_train_linear_mode", PRECISIONS,
+    """``"fp32"`` or ``"bf16"``: the mode in which the calling thread's training Linears multiply.""",
     """``with linear_precision("bf16"):`` -- inside, every Linear of the training path (``linear``, the MLP, attention and cross sublayers, the decoder's
     embedding and feedback Linears) rounds the two operands of its product to bf16 as it stages them, multiplies on the 16-bit MFMA and accumulates in fp32,
     like ``torch.autocast(dtype=torch.bfloat16)`` does for ``nn.Linear``; ``"fp32"`` is the default of every thread; ``None`` leaves the mode alone.  The mode
@@ -34,56 +58,33 @@ def linear_precision(mode):
     backward in it, whichever thread autograd uses and whether or not the ``with`` block has ended: a backward recomputes the forward it differentiates.
 
     Narrower than autocast: everything in memory stays fp32 (activations, weights, gradients, scratch), and LayerNorm, the attention core (scores, softmax,
-    P V), RoPE, GELU, the bias and residual additions, bias gradients, the head (``train_head``), the losses and the optimizer compute in fp32 in either mode."""
-    if mode is None:
-        yield
-        return
-    if mode not in PRECISIONS:
-        raise ValueError(f"linear_precision: mode {mode!r}, expected one of {sorted(PRECISIONS)} or None")
-    lib = _lib.load()
-    prev = lib.must3r_hip_train_linear_mode(PRECISIONS[mode])
-    if prev < 0:
-        raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
-    try:
-        yield
-    finally:
-        lib.must3r_hip_train_linear_mode(prev)
+    P V), RoPE, GELU, the bias and residual additions, bias gradients, the head (``train_head``), the losses and the optimizer compute in fp32 in either mode.""")
 
-
-# ---------------------------------------------------------------------------------------------------------------------------------------
-# the precision of the attention core's products (must3r_hip_train_attention_mode), independent of the Linears' mode above
-# ---------------------------------------------------------------------------------------------------------------------------------------
 ATTENTION_PRECISIONS = {"fp32": _lib.TRAIN_ATTENTION_F32, "bf16": _lib.TRAIN_ATTENTION_BF16}
-_ATTENTION_PRECISION_NAMES = {v: k for k, v in ATTENTION_PRECISIONS.items()}
-
-
-def current_attention_precision():
-    """``"fp32"`` or ``"bf16"``: the mode in which the calling thread's training attention core multiplies."""
-    return _ATTENTION_PRECISION_NAMES[_lib.load().must3r_hip_train_attention_mode(-1)]
-
-
-@contextlib.contextmanager
-def attention_precision(mode):
+current_attention_precision, attention_precision = _precision_switch(
+    "attention_precision", "must3r_hip_train_attention_mode", ATTENTION_PRECISIONS,
+    """``"fp32"`` or ``"bf16"``: the mode in which the calling thread's training attention core multiplies.""",
     """``with attention_precision("bf16"):`` -- inside, the attention core of the training path (``train_attention.attention``, the attention and cross
     sublayers, masked forms included, and everything composed of them) rounds Q, K, V and dO, and P and dS as operands of the products that follow them, to
     bf16 in registers and multiplies on the 16-bit MFMA with fp32 accumulation, as the core does under ``torch.autocast(dtype=torch.bfloat16)``; the scores,
     the softmax, its row sum, lse, delta and dS are computed in fp32 and all storage stays fp32.  ``"fp32"`` is the default of every thread; ``None`` leaves the
     mode alone.  The contract is ``linear_precision``'s: the mode belongs to the calling thread, is restored on exit (also after an exception), and every
     ``Function`` whose backward reaches the core records the mode of its forward and runs its backward in it.  The two modes do not touch each other;
-    ``amp`` enters both."""
-    if mode is None:
+    ``amp`` enters both.""")
+
+
+def _record_modes(ctx, linear=False, attention=False):
+    """A ``Function``'s forward: note on ``ctx`` the calling thread's mode of each switch that its backward reaches (``None`` for one it does not)."""
+    ctx.modes = (current_precision() if linear else None, current_attention_precision() if attention else None)
+
+
+@contextlib.contextmanager
+def _recorded_modes(ctx):
+    """The ``Function``'s backward runs inside this: the modes ``_record_modes`` noted in its forward, whichever thread autograd uses and whether or not the
+    caller's ``with`` block has ended -- a backward recomputes the forward it differentiates."""
+    linear, attention = ctx.modes
+    with linear_precision(linear), attention_precision(attention):
         yield
-        return
-    if mode not in ATTENTION_PRECISIONS:
-        raise ValueError(f"attention_precision: mode {mode!r}, expected one of {sorted(ATTENTION_PRECISIONS)} or None")
-    lib = _lib.load()
-    prev = lib.must3r_hip_train_attention_mode(ATTENTION_PRECISIONS[mode])
-    if prev < 0:
-        raise _lib.HipError(lib.must3r_hip_last_error().decode("utf-8", "replace"))
-    try:
-        yield
-    finally:
-        lib.must3r_hip_train_attention_mode(prev)
 
 
 @contextlib.contextmanager

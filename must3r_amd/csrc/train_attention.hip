@@ -37,10 +37,11 @@
 #include "kernels.hpp"
 #include "train_attn.hpp"
 #include "train_common.hpp"
+#include "train_tile.hpp"
 
 namespace m3r {
 
-constexpr int TA_LD = 68;   // LDS row stride in floats (TA_T, the constants, TaArgs, the tile fetch and the key rules: train_attn.hpp, shared with train_attn16.hip)
+constexpr int TA_LD = 68;   // LDS row stride in floats (TA_T, the constants, TaArgs, the tile fetches, the key rules and the walk: train_attn.hpp, shared with train_attn16.hip)
 
 // registers (ta_fetch_tile) -> dst [64][TA_LD]
 __device__ __forceinline__ void ta_put_tile(float* dst, const f32x4 (&x)[4], int tid) {
@@ -116,13 +117,9 @@ __global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
     f32x4 o[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) { m[r] = -inf; l[r] = 0.f; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(o);
     f32x4 rk[4], rv[4];
-    auto fetch = [&](int k) {
-        ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
-        ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
-    };
+    auto fetch = [&](int k) { ta_fetch_kv(rk, rv, a, v, k, h, tid); };   // bound once: see ta_fetch_kv
     int k0 = ta_next_tile_m<MASK>(v, 0, mrow);
     if (k0 < v.nk) fetch(k0);
     while (k0 < v.nk) {
@@ -134,8 +131,7 @@ __global__ void __launch_bounds__(256) attn_fwd_f32(TaArgs a) {
         const uint64_t mb = MASK ? ta_tile_bits(mrow, k0, v.nk) : ~0ull;
         if (k_next < v.nk) fetch(k_next);
         f32x4 s[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(s);
         ta_mm_reg<true>(s, qa, Ks, fr, fk);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -215,13 +211,9 @@ __global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
         dl[r] = qr < v.nq ? a.delta[i] : 0.f;
     }
     f32x4 dq[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dq[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(dq);
     f32x4 rk[4], rv[4];
-    auto fetch = [&](int k) {
-        ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
-        ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
-    };
+    auto fetch = [&](int k) { ta_fetch_kv(rk, rv, a, v, k, h, tid); };   // bound once: see ta_fetch_kv
     int k0 = ta_next_tile_m<MASK>(v, 0, mrow);
     if (k0 < v.nk) fetch(k0);
     while (k0 < v.nk) {
@@ -233,8 +225,8 @@ __global__ void __launch_bounds__(256) attn_dq_f32(TaArgs a) {
         const uint64_t mb = MASK ? ta_tile_bits(mrow, k0, v.nk) : ~0ull;
         if (k_next < v.nk) fetch(k_next);
         f32x4 s[4], dp[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        zero_acc(s);
+        zero_acc(dp);
         ta_mm_reg<true>(s, qa, Ks, fr, fk);
         ta_mm_reg<true>(dp, da, Vs, fr, fk);
 #pragma unroll
@@ -277,33 +269,15 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
         ta_load_frag(va, a.V + (size_t)(g.kv_row0 + kr) * a.ldv + h * TA_T, kr < g.extent, fk);
     }
     f32x4 dk[4], dv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { dk[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    // the walk over (view in table order, query tile in row order), one step ahead of the products: vi == g.count at the end
-    // mb: the view's mask bits of this key tile (MASK); a view that dropped the whole tile is passed over before any of its Q / dO tiles is fetched
-    auto advance = [&](int& vi, int& q0, AttnView& v, uint64_t& mb) {
-        if (vi >= 0 && q0 + TA_T < v.nq) { q0 += TA_T; return; }
-        q0 = 0;
-        for (++vi; vi < g.count; ++vi) {
-            const int id = a.list[g.first + vi];
-            v = a.views[id];
-            if (v.nq > 0 && !ta_tile_skipped(v, k0)) {
-                if (!MASK) return;
-                mb = ta_tile_bits(ta_mask_row<MASK>(a, id), k0, v.nk);
-                if (mb) return;
-            }
-        }
-    };
+    zero_acc(dk);
+    zero_acc(dv);
     f32x4 rq[4], rd[4];
-    auto fetch = [&](const AttnView& v, int q0) {
-        ta_fetch_tile(rq, a.Q + (size_t)(v.q_row0 + q0) * a.ldq + h * TA_T, a.ldq, v.nq - q0, tid);
-        ta_fetch_tile(rd, a.dO + (size_t)(v.q_row0 + q0) * a.lddo + h * TA_T, a.lddo, v.nq - q0, tid);
-    };
     int vi = -1, q0 = 0;
     AttnView v{};
     uint64_t mb = ~0ull;
-    advance(vi, q0, v, mb);
-    if (vi < g.count) fetch(v, q0);
+    // the walk (train_attn.hpp ta_walk_next) runs one step ahead of the products
+    ta_walk_next<MASK>(a, g, k0, vi, q0, v, mb);
+    if (vi < g.count) ta_fetch_qdo(rq, rd, a, v, q0, h, tid);
     while (vi < g.count) {
         __syncthreads();
         ta_put_tile(Qs, rq, tid);
@@ -312,8 +286,8 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
         int vi_next = vi, q_next = q0;
         AttnView v_next = v;
         uint64_t mb_next = mb;
-        advance(vi_next, q_next, v_next, mb_next);
-        if (vi_next < g.count) fetch(v_next, q_next);
+        ta_walk_next<MASK>(a, g, k0, vi_next, q_next, v_next, mb_next);
+        if (vi_next < g.count) ta_fetch_qdo(rq, rd, a, v_next, q_next, h, tid);
         bool kok[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) kok[r] = ta_valid(v, k0 + w * 16 + fk * 4 + r) && (!MASK || (mb >> (w * 16 + fk * 4 + r) & 1));
@@ -326,8 +300,8 @@ __global__ void __launch_bounds__(256) attn_dkv_f32(TaArgs a) {
             dc[j] = qi < v.nq ? a.delta[i] : 0.f;
         }
         f32x4 st[4], dpt[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { st[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dpt[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        zero_acc(st);
+        zero_acc(dpt);
         ta_mm_reg<true>(st, ka, Qs, fr, fk);
         ta_mm_reg<true>(dpt, va, Ds, fr, fk);
 #pragma unroll
@@ -536,6 +510,13 @@ static TaArgs ta_kernel_args(const must3r_hip_attn_train_args* a, const TaPlan& 
     return k;
 }
 
+// the kernels of a call, chosen once: the calling thread's mode (must3r_hip_train_attention_mode) picks the family, `masked` the instantiation
+static TaKernels ta_kernels(bool masked) {
+    if (train_attention_bf16()) return ta_kernels_bf16(masked);
+    if (masked) return TaKernels{attn_fwd_f32<true>, attn_dkv_f32<true>, attn_dq_f32<true>};
+    return TaKernels{attn_fwd_f32<false>, attn_dkv_f32<false>, attn_dq_f32<false>};
+}
+
 // the two entry points of each kind, behind their argument checks: m.bits == nullptr launches the unmasked instantiations over the unmasked scratch layout
 static int ta_forward(const char* who, const must3r_hip_attn_train_args* a, const TaMask& m, void* scratch, size_t scratch_bytes, hipStream_t s) {
     if (const char* e = ta_args_error(a, false)) return fail("%s: %s", who, e);
@@ -551,9 +532,7 @@ static int ta_forward(const char* who, const must3r_hip_attn_train_args* a, cons
     k.dO = nullptr; k.lse2 = nullptr; k.delta = nullptr;
     k.O = a->O; k.ldo = a->ldo; k.lse = a->lse;
     const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views);
-    if (train_attention_bf16()) launch_attn_fwd_bf16(masked, qgrid, k, s);   // must3r_hip_train_attention_mode: the same launch on the 16-bit MFMA
-    else if (masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<true>), qgrid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<false>), qgrid, dim3(256), 0, s, k);
+    hipLaunchKernelGGL(ta_kernels(masked).fwd, qgrid, dim3(256), 0, s, k);
     if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
     return 0;
 }
@@ -574,19 +553,10 @@ static int ta_grad(const char* who, const must3r_hip_attn_train_args* a, const T
     const dim3 qgrid((P.max_nq + TA_T - 1) / TA_T, a->heads, a->n_views), kgrid((P.max_extent + TA_T - 1) / TA_T, a->heads, (unsigned)P.groups.size());
     const bool run_q = P.max_nq > 0, run_kv = want_kv && P.max_extent > 0;
     // lse2 and delta into scratch, then dK | dV, then dQ
-    if (train_attention_bf16()) {   // must3r_hip_train_attention_mode: the same three launches on the 16-bit MFMA
-        if (run_q) launch_attn_fwd_bf16(masked, qgrid, k, s);
-        if (run_kv) launch_attn_dkv_bf16(masked, kgrid, k, s);
-        if (a->dQ && run_q) launch_attn_dq_bf16(masked, qgrid, k, s);
-    } else if (masked) {
-        if (run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<true>), qgrid, dim3(256), 0, s, k);
-        if (run_kv) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dkv_f32<true>), kgrid, dim3(256), 0, s, k);
-        if (a->dQ && run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dq_f32<true>), qgrid, dim3(256), 0, s, k);
-    } else {
-        if (run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_f32<false>), qgrid, dim3(256), 0, s, k);
-        if (run_kv) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dkv_f32<false>), kgrid, dim3(256), 0, s, k);
-        if (a->dQ && run_q) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dq_f32<false>), qgrid, dim3(256), 0, s, k);
-    }
+    const TaKernels K = ta_kernels(masked);
+    if (run_q) hipLaunchKernelGGL(K.fwd, qgrid, dim3(256), 0, s, k);
+    if (run_kv) hipLaunchKernelGGL(K.dkv, kgrid, dim3(256), 0, s, k);
+    if (a->dQ && run_q) hipLaunchKernelGGL(K.dq, qgrid, dim3(256), 0, s, k);
     if (hipGetLastError() != hipSuccess) return fail("%s: launch failed", who);
     return 0;
 }

@@ -1,5 +1,6 @@
 // What the fp32 kernels of the training attention core (train_attention.hip) and their bf16 siblings (train_attn16.hip) share: the kernel arguments, the
-// key-group record, the tile fetch, and the rules that say which keys and which key tiles a view reads.  The host side (plan, scratch layout, upload, argument
+// key-group record, the tile fetches, the rules that say which keys and which key tiles a view reads, the walk of the backward over a key group, and the
+// record of kernel pointers by which the host launches either family.  The host side (plan, scratch layout, upload, argument
 // checks) lives in train_attention.hip alone: both kernel families are launched from ta_forward and ta_grad there, over the same tables, scratch and grids.
 #pragma once
 #include "common.hpp"
@@ -73,11 +74,47 @@ __device__ __forceinline__ int ta_next_tile_m(const AttnView& v, int k0, const u
     return k0;
 }
 
-// train_attn16.hip: the calling thread's mode is MUST3R_TRAIN_ATTENTION_BF16 (must3r_hip_train_attention_mode), and the launchers of the bf16 kernels.  They
-// take the grids and arguments ta_forward / ta_grad built for the fp32 kernels and only launch; `masked` picks the MASK instantiation.
+// the K | V tiles at key row k of view v, head h, into registers (attn_fwd_*, attn_dq_*), and the Q | dO tiles at query row q0 (attn_dkv_*).
+// attn_fwd_* and attn_dq_* bind ta_fetch_kv to their registers in one local lambda and call that before and inside the loop: with the two sites calling
+// it directly the compiler zeroed the 32 registers at each of them, 56 to 86 instructions more per kernel (profiles/train_shared_ab.txt).
+__device__ __forceinline__ void ta_fetch_kv(f32x4 (&rk)[4], f32x4 (&rv)[4], const TaArgs& a, const AttnView& v, int k, int h, int tid) {
+    ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
+    ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
+}
+__device__ __forceinline__ void ta_fetch_qdo(f32x4 (&rq)[4], f32x4 (&rd)[4], const TaArgs& a, const AttnView& v, int q0, int h, int tid) {
+    ta_fetch_tile(rq, a.Q + (size_t)(v.q_row0 + q0) * a.ldq + h * TA_T, a.ldq, v.nq - q0, tid);
+    ta_fetch_tile(rd, a.dO + (size_t)(v.q_row0 + q0) * a.lddo + h * TA_T, a.lddo, v.nq - q0, tid);
+}
+
+// The walk of attn_dkv_* over its key group g for the key tile at k0: views in table order, each view's query tiles in row order.  One call moves
+// (vi, q0, v, mb) to the next (view, query tile) pair; start from vi = -1, and vi == g.count is the end.  A view without queries, or whose key range or skip
+// range leaves nothing of the tile, is passed over; so is, with MASK, a view whose mask dropped the whole tile (mb, its mask bits of this key tile, is 0),
+// before any of its Q / dO tiles is fetched.  The kernels take their steps ahead of the products in this order and add in it: the fixed order of additions
+// of dK and dV, without atomics, is this function.
+template <bool MASK>
+__device__ __forceinline__ void ta_walk_next(const TaArgs& a, const TaGroup& g, int k0, int& vi, int& q0, AttnView& v, uint64_t& mb) {
+    if (vi >= 0 && q0 + TA_T < v.nq) { q0 += TA_T; return; }
+    q0 = 0;
+    for (++vi; vi < g.count; ++vi) {
+        const int id = a.list[g.first + vi];
+        v = a.views[id];
+        if (v.nq > 0 && !ta_tile_skipped(v, k0)) {
+            if (!MASK) return;
+            mb = ta_tile_bits(ta_mask_row<MASK>(a, id), k0, v.nk);
+            if (mb) return;
+        }
+    }
+}
+
+// The three kernels of one family and instantiation, as ta_forward / ta_grad launch them: over the same arguments, grids and 256-thread blocks.
+struct TaKernels {
+    void (*fwd)(TaArgs);
+    void (*dkv)(TaArgs);
+    void (*dq)(TaArgs);
+};
+// train_attn16.hip: the calling thread's mode is MUST3R_TRAIN_ATTENTION_BF16 (must3r_hip_train_attention_mode), and the bf16 kernels; `masked` picks the
+// MASK instantiations.
 bool train_attention_bf16();
-void launch_attn_fwd_bf16(bool masked, dim3 grid, const TaArgs& k, hipStream_t s);
-void launch_attn_dkv_bf16(bool masked, dim3 grid, const TaArgs& k, hipStream_t s);
-void launch_attn_dq_bf16(bool masked, dim3 grid, const TaArgs& k, hipStream_t s);
+TaKernels ta_kernels_bf16(bool masked);
 
 }  // namespace m3r

@@ -15,8 +15,8 @@
 //     the accumulator then holds, in lane l, own row l & 15 and walked rows 16 t + 4 (l >> 4) + r (t, r = 0..3);
 //   * rounded to bf16 these 16 values ARE the B fragments of the second product, (head dimension) x (own rows) = (walked tile)^T x P: for the 32-deep step ks,
 //     lane group g = l >> 4 holds the walked rows 32 ks + 4 g ... + 3 and 32 ks + 16 + 4 g ... + 3, and the A operand, the walked tile contracted along its slow
-//     dimension, is read transposed with two ds_read_b64_tr_b16 per fragment (common.hpp lds_read_tr4_x8) that name exactly those rows -- the same permutation of
-//     a step's 32 rows on both operands, as in dgrad_bf16 and wgrad_bf16.
+//     dimension, is read transposed with two ds_read_b64_tr_b16 per fragment that name exactly those rows (train_tile.hpp frag_tr4, the code and the
+//     row-permutation contract that dgrad_bf16 and wgrad_bf16 use): the same permutation of a step's 32 rows on both operands.
 // The outputs come out transposed as well: lane l holds own row l & 15 and head dimensions 16 t + 4 (l >> 4) ... + 3, one 16-byte store per t.  The softmax
 // statistics of a query are per lane in the query-owning kernels (the four lanes l, l ^ 16, l ^ 32, l ^ 48 share a query and combine with two VALU swaps), and
 // per accumulator row in attn_dkv_bf16, which reads lse2 and delta of the walked 64 queries through LDS.
@@ -31,6 +31,7 @@
 #include "kernels.hpp"
 #include "train_attn.hpp"
 #include "train_common.hpp"
+#include "train_tile.hpp"
 
 namespace m3r {
 
@@ -38,9 +39,6 @@ constexpr int TB_LD = 80;   // LDS row stride of a [64][64] bf16 tile, in elemen
 
 static thread_local int g_train_attention_mode = MUST3R_TRAIN_ATTENTION_F32;
 bool train_attention_bf16() { return g_train_attention_mode == MUST3R_TRAIN_ATTENTION_BF16; }
-
-__device__ __forceinline__ f32x4 tb_ld4(const float* p, bool ok) { return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ bf16x8 tb_cat(bf16x4 lo, bf16x4 hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
 
 // registers (ta_fetch_tile) -> dst [64][TB_LD], rounded: one 8-byte write per float4
 __device__ __forceinline__ void tb_put_tile(bf16_t* dst, const f32x4 (&x)[4], int tid) {
@@ -53,7 +51,7 @@ __device__ __forceinline__ void tb_put_tile(bf16_t* dst, const f32x4 (&x)[4], in
 // the B fragments of one of the wave's own rows: b[ks] = row[32 ks + 8 fk ... + 7], rounded
 __device__ __forceinline__ void tb_load_own(bf16x8 (&b)[2], const float* __restrict__ row, bool ok, int fk) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) b[ks] = tb_cat(cvt4<bf16_t>(tb_ld4(row + 32 * ks + 8 * fk, ok)), cvt4<bf16_t>(tb_ld4(row + 32 * ks + 8 * fk + 4, ok)));
+    for (int ks = 0; ks < 2; ++ks) b[ks] = cat8(cvt4<bf16_t>(ld4_or_zero(row + 32 * ks + 8 * fk, ok)), cvt4<bf16_t>(ld4_or_zero(row + 32 * ks + 8 * fk + 4, ok)));
 }
 // acc[t] (rows 16 t ... + 15 of the LDS tile x the wave's 16 own rows) += Ts[row][d] own[d]: the tile by rows
 __device__ __forceinline__ void tb_mm_rows(f32x4 (&acc)[4], const bf16_t* Ts, const bf16x8 (&b)[2], int fr, int fk) {
@@ -68,21 +66,16 @@ __device__ __forceinline__ void tb_mm_cols(f32x4 (&acc)[4], const bf16_t* Ts, co
     const bf16_t* base = Ts + (fk * 4 + (fr >> 2)) * TB_LD + (fr & 3) * 4;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-        const bf16_t* pt = base + ks * 32 * TB_LD;
-        bf16x4 h[8];
-        lds_read_tr4_x8<bf16_t>(pt, pt + 16 * TB_LD, pt + 16, pt + 16 * TB_LD + 16, pt + 32, pt + 16 * TB_LD + 32, pt + 48, pt + 16 * TB_LD + 48, h);
+        bf16x8 f[4];
+        frag_tr4<TB_LD>(base + ks * 32 * TB_LD, f);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = mfma16(tb_cat(h[2 * t], h[2 * t + 1]), p[ks], acc[t]);
+        for (int t = 0; t < 4; ++t) acc[t] = mfma16(f[t], p[ks], acc[t]);
     }
 }
 // the accumulators of a score (lane: walked rows 16 t + 4 fk + r) -> the B fragments of the second product, rounded
 __device__ __forceinline__ void tb_pack(bf16x8 (&p)[2], const f32x4 (&x)[4]) {
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) p[ks] = tb_cat(cvt4<bf16_t>(x[2 * ks]), cvt4<bf16_t>(x[2 * ks + 1]));
-}
-__device__ __forceinline__ void tb_zero(f32x4 (&x)[4]) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) x[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < 2; ++ks) p[ks] = cat8(cvt4<bf16_t>(x[2 * ks]), cvt4<bf16_t>(x[2 * ks + 1]));
 }
 
 template <bool MASK>
@@ -103,12 +96,9 @@ __global__ void __launch_bounds__(256) attn_fwd_bf16(TaArgs a) {
     tb_load_own(qb, a.Q + row * a.ldq + h * TA_T, qok, fk);
     float m = -inf, l = 0.f;
     f32x4 o[4];
-    tb_zero(o);
+    zero_acc(o);
     f32x4 rk[4], rv[4];
-    auto fetch = [&](int k) {
-        ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
-        ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
-    };
+    auto fetch = [&](int k) { ta_fetch_kv(rk, rv, a, v, k, h, tid); };   // bound once: see ta_fetch_kv
     int k0 = ta_next_tile_m<MASK>(v, 0, mrow);
     if (k0 < v.nk) fetch(k0);
     while (k0 < v.nk) {
@@ -120,7 +110,7 @@ __global__ void __launch_bounds__(256) attn_fwd_bf16(TaArgs a) {
         const uint64_t mb = (MASK ? ta_tile_bits(mrow, k0, v.nk) : ~0ull) >> (fk * 4);
         if (k_next < v.nk) fetch(k_next);
         f32x4 s[4];
-        tb_zero(s);
+        zero_acc(s);
         tb_mm_rows(s, Ks, qb, fr, fk);   // S^T: s[t][r] is key k0 + 16 t + 4 fk + r against the lane's query
         float mx = -inf;
 #pragma unroll
@@ -160,7 +150,7 @@ __global__ void __launch_bounds__(256) attn_fwd_bf16(TaArgs a) {
         const f32x4 x = o[t] * inv;
         if (qok && a.O) *reinterpret_cast<f32x4*>(a.O + row * a.ldo + col) = x;
         if (a.delta) {
-            const f32x4 g = tb_ld4(a.dO + row * a.lddo + col, qok);
+            const f32x4 g = ld4_or_zero(a.dO + row * a.lddo + col, qok);
 #pragma unroll
             for (int r = 0; r < 4; ++r) d += x[r] * g[r];
         }
@@ -194,12 +184,9 @@ __global__ void __launch_bounds__(256) attn_dq_bf16(TaArgs a) {
     const float lr = qok ? a.lse2[row * a.heads + h] : __builtin_inff();
     const float dl = qok ? a.delta[row * a.heads + h] : 0.f;
     f32x4 dq[4];
-    tb_zero(dq);
+    zero_acc(dq);
     f32x4 rk[4], rv[4];
-    auto fetch = [&](int k) {
-        ta_fetch_tile(rk, a.K + (size_t)(v.kv_row0 + k) * a.ldk + h * TA_T, a.ldk, v.nk - k, tid);
-        ta_fetch_tile(rv, a.V + (size_t)(v.kv_row0 + k) * a.ldv + h * TA_T, a.ldv, v.nk - k, tid);
-    };
+    auto fetch = [&](int k) { ta_fetch_kv(rk, rv, a, v, k, h, tid); };   // bound once: see ta_fetch_kv
     int k0 = ta_next_tile_m<MASK>(v, 0, mrow);
     if (k0 < v.nk) fetch(k0);
     while (k0 < v.nk) {
@@ -211,8 +198,8 @@ __global__ void __launch_bounds__(256) attn_dq_bf16(TaArgs a) {
         const uint64_t mb = (MASK ? ta_tile_bits(mrow, k0, v.nk) : ~0ull) >> (fk * 4);
         if (k_next < v.nk) fetch(k_next);
         f32x4 s[4], dp[4];
-        tb_zero(s);
-        tb_zero(dp);
+        zero_acc(s);
+        zero_acc(dp);
         tb_mm_rows(s, Ks, qb, fr, fk);    // S^T = K Q^T
         tb_mm_rows(dp, Vs, db, fr, fk);   // dP^T = V dO^T
 #pragma unroll
@@ -251,28 +238,12 @@ __global__ void __launch_bounds__(256) attn_dkv_bf16(TaArgs a) {
     tb_load_own(kb, a.K + krow * a.ldk + h * TA_T, kin, fk);
     tb_load_own(vb, a.V + krow * a.ldv + h * TA_T, kin, fk);
     f32x4 dk[4], dv[4];
-    tb_zero(dk);
-    tb_zero(dv);
-    // the walk over (view in table order, query tile in row order), one step ahead of the products: vi == g.count at the end
-    // mb: the view's mask bits of this key tile (MASK); a view that dropped the whole tile is passed over before any of its Q / dO tiles is fetched
-    auto advance = [&](int& vi, int& q0, AttnView& v, uint64_t& mb) {
-        if (vi >= 0 && q0 + TA_T < v.nq) { q0 += TA_T; return; }
-        q0 = 0;
-        for (++vi; vi < g.count; ++vi) {
-            const int id = a.list[g.first + vi];
-            v = a.views[id];
-            if (v.nq > 0 && !ta_tile_skipped(v, k0)) {
-                if (!MASK) return;
-                mb = ta_tile_bits(ta_mask_row<MASK>(a, id), k0, v.nk);
-                if (mb) return;
-            }
-        }
-    };
+    zero_acc(dk);
+    zero_acc(dv);
     f32x4 rq[4], rd[4];
     float rs = 0.f;   // threads 0..63: lse2 of query q0 + tid (+inf past nq); threads 64..127: delta of query q0 + tid - 64 (0 past nq)
     auto fetch = [&](const AttnView& v, int q0) {
-        ta_fetch_tile(rq, a.Q + (size_t)(v.q_row0 + q0) * a.ldq + h * TA_T, a.ldq, v.nq - q0, tid);
-        ta_fetch_tile(rd, a.dO + (size_t)(v.q_row0 + q0) * a.lddo + h * TA_T, a.lddo, v.nq - q0, tid);
+        ta_fetch_qdo(rq, rd, a, v, q0, h, tid);
         if (tid < 2 * TA_T) {
             const int qi = q0 + (tid & 63);
             const bool second = tid >= TA_T;
@@ -283,7 +254,8 @@ __global__ void __launch_bounds__(256) attn_dkv_bf16(TaArgs a) {
     int vi = -1, q0 = 0;
     AttnView v{};
     uint64_t mb = ~0ull;
-    advance(vi, q0, v, mb);
+    // the walk (train_attn.hpp ta_walk_next) runs one step ahead of the products
+    ta_walk_next<MASK>(a, g, k0, vi, q0, v, mb);
     if (vi < g.count) fetch(v, q0);
     while (vi < g.count) {
         __syncthreads();
@@ -294,12 +266,12 @@ __global__ void __launch_bounds__(256) attn_dkv_bf16(TaArgs a) {
         int vi_next = vi, q_next = q0;
         AttnView v_next = v;
         uint64_t mb_next = mb;
-        advance(vi_next, q_next, v_next, mb_next);
+        ta_walk_next<MASK>(a, g, k0, vi_next, q_next, v_next, mb_next);
         if (vi_next < g.count) fetch(v_next, q_next);
         const bool kok = ta_valid(v, kr) && (!MASK || (mb >> (w * 16 + fr) & 1));
         f32x4 s[4], dp[4];
-        tb_zero(s);
-        tb_zero(dp);
+        zero_acc(s);
+        zero_acc(dp);
         tb_mm_rows(s, Qs, kb, fr, fk);    // S = Q K^T: s[t][r] is query q0 + 16 t + 4 fk + r against the lane's key
         tb_mm_rows(dp, Ds, vb, fr, fk);   // dP = dO V^T
 #pragma unroll
@@ -329,29 +301,15 @@ __global__ void __launch_bounds__(256) attn_dkv_bf16(TaArgs a) {
     }
 }
 
-void launch_attn_fwd_bf16(bool masked, dim3 grid, const TaArgs& k, hipStream_t s) {
-    if (masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_bf16<true>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_bf16<false>), grid, dim3(256), 0, s, k);
-}
-void launch_attn_dkv_bf16(bool masked, dim3 grid, const TaArgs& k, hipStream_t s) {
-    if (masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dkv_bf16<true>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dkv_bf16<false>), grid, dim3(256), 0, s, k);
-}
-void launch_attn_dq_bf16(bool masked, dim3 grid, const TaArgs& k, hipStream_t s) {
-    if (masked) hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dq_bf16<true>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_dq_bf16<false>), grid, dim3(256), 0, s, k);
+TaKernels ta_kernels_bf16(bool masked) {
+    if (masked) return TaKernels{attn_fwd_bf16<true>, attn_dkv_bf16<true>, attn_dq_bf16<true>};
+    return TaKernels{attn_fwd_bf16<false>, attn_dkv_bf16<false>, attn_dq_bf16<false>};
 }
 
 }  // namespace m3r
 using namespace m3r;
 
 extern "C" int must3r_hip_train_attention_mode(int mode) {
-    if (mode == -1) return g_train_attention_mode;
-    if (mode != MUST3R_TRAIN_ATTENTION_F32 && mode != MUST3R_TRAIN_ATTENTION_BF16) {
-        fail("train_attention_mode: unknown mode %d (MUST3R_TRAIN_ATTENTION_F32 = 0, MUST3R_TRAIN_ATTENTION_BF16 = 1, -1 to query)", mode);
-        return -1;
-    }
-    const int prev = g_train_attention_mode;
-    g_train_attention_mode = mode;
-    return prev;
+    return swap_thread_mode(g_train_attention_mode, mode, MUST3R_TRAIN_ATTENTION_BF16,
+                            "train_attention_mode: unknown mode %d (MUST3R_TRAIN_ATTENTION_F32 = 0, MUST3R_TRAIN_ATTENTION_BF16 = 1, -1 to query)");
 }

@@ -11,7 +11,7 @@
 //                         over K through LDS, 4 waves of 64 x 64, the next K-tile fetched into registers under the products of the current one.  Both
 //                         operands are K-contiguous: both LDS tiles are [128][20] (rows padded to 20 floats: conflict-free).  Epilogues: bias; bias +
 //                         residual; bias + GELU (gelu(z), and z itself where a second pointer is given).  In MUST3R_TRAIN_LINEAR_BF16 mode run_linear
-//                         launches linear_fwd_bf16 of train_lin16.hip instead (same arguments, tiles and epilogues; train_lin.hpp holds what the two share).
+//                         launches linear_fwd_bf16 of train_lin16.hip instead (same arguments and tiles; the epilogue itself is train_lin.hpp's, one copy for both).
 //   ln_fwd_f32            y = (x - mu) rstd gamma + beta, one wave per row, 16-byte accesses, the row in registers; its own two-pass statistics (the
 //                         formulas of row_stats_kernel in another summation order: the backward's statistics differ from these by rounding only).
 //   gelu_grad_f32         dz = dh gelu'(z), 16-byte accesses, in place over dh.
@@ -27,12 +27,13 @@
 #include "train_common.hpp"
 #include "train_lin.hpp"
 #include "train_ln.hpp"
+#include "train_tile.hpp"
 
 namespace m3r {
 
 constexpr int BM = 128, BN = 128, BK = 16, BP = 20;   // BP: LDS row stride (floats) of a [128][16] tile
 
-// LinArgs, the epilogue names and gelu_cdf / gelu_f32: train_lin.hpp, shared with the bf16 form
+// LinArgs, the epilogue (lin_epilogue) and gelu_cdf / gelu_f32: train_lin.hpp, shared with the bf16 form
 // exp(-z^2 / 2) is 0 from |z| = 14.6 on (fp32 underflow), so that the derivative is exactly Phi there: 1 or 0 beyond |z| = 40
 __device__ __forceinline__ float gelu_deriv_f32(float z) {
     const float pdf = 0.39894228040143267794f * expf(-0.5f * z * z);
@@ -62,10 +63,7 @@ __global__ void __launch_bounds__(256) linear_fwd_f32(LinArgs p) {
         wp[e] = p.W + (wok[e] ? (size_t)(n0 + sr[e]) * p.K + sc[e] : 0);
     }
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     f32x4 ra[2], rb[2];
     auto fetch = [&](int k0) {
 #pragma unroll
@@ -97,32 +95,7 @@ __global__ void __launch_bounds__(256) linear_fwd_f32(LinArgs p) {
                 for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     }
-    // C/D map: row 4 (lane / 16) + r, column lane & 15
-    float bj[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + j * 16 + fr;
-        bj[j] = p.bias && n < p.N ? p.bias[n] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wm * 64 + i * 16 + fk * 4 + r;
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = n0 + wn * 64 + j * 16 + fr;
-                if (n >= p.N) continue;
-                const float z = acc[i][j][r] + bj[j];
-                if constexpr (EPI == LIN_BIAS) p.out[(size_t)m * p.ldc + n] = z;
-                if constexpr (EPI == LIN_BIAS_RES) p.out[(size_t)m * p.ldc + n] = p.res[(size_t)m * p.ldres + n] + z;
-                if constexpr (EPI == LIN_BIAS_GELU) {
-                    if (p.zout) p.zout[(size_t)m * p.ldz + n] = z;
-                    p.out[(size_t)m * p.ldc + n] = gelu_f32(z);
-                }
-            }
-        }
+    lin_epilogue<EPI>(p, acc, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
 // one wave per row, the row read once with 16-byte loads and kept in registers (D % 64 == 0, D <= 1024: four float4 per lane); two-pass statistics.

@@ -1,5 +1,5 @@
 // Host-side helpers of the four training sources (train_head.hip, train_attention.hip, train_block.hip, train_cross.hip), once each: the early-return macro,
-// the 256-byte scratch parts, the alignment test, the argument checks that more than one file makes, and the pieces every residual sublayer's backward shares:
+// the 256-byte scratch parts, the alignment test, the per-thread mode switch, the argument checks that more than one file makes, and the pieces every residual sublayer's backward shares:
 //   x -> y = LN(x) -> first Linear -> ... -> last Linear -> + x
 // The backward of all three sublayers opens with the same shortcut (last_bias_alone) and closes with the same tail (sublayer_grad_tail); the two attention
 // sublayers also share the forward of the core (sublayer_attend) and the gradients at proj (proj_grad).  The sublayer templates read the operands that the three
@@ -37,6 +37,18 @@ struct ScratchCursor {
         return at;
     }
 };
+
+// The one entry point of a per-thread mode (must3r_hip_train_linear_mode, must3r_hip_train_attention_mode) over the caller's own thread-local `cur`, whose
+// modes are 0 .. last: -1 answers the mode and changes nothing; a mode sets it and answers the one it replaces; anything else leaves `refusal` (a format
+// taking the refused mode) as the last error and answers -1.
+__attribute__((format(printf, 4, 0))) inline int swap_thread_mode(int& cur, int mode, int last, const char* refusal) {
+    if (mode == -1) return cur;
+    if (mode < 0 || mode > last) {
+        fail(refusal, mode);
+        return -1;
+    }
+    return std::exchange(cur, mode);
+}
 
 // M token rows of width D (and Rm rows of a second tensor, where there is one)
 inline const char* rows_width_error(int M, int D, int Rm = 1) {

@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "train_common.hpp"
+#include "train_tile.hpp"
 
 namespace m3r {
 
@@ -140,6 +141,8 @@ __global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __rest
         bok[e] = n0 + bc[e] < K;
     }
     f32x4 acc[4][4];
+    // spelled out, not zero_acc (train_tile.hpp): with the call the compiler put one more scalar instruction into the prologue, the loop moved by 4 bytes and
+    // the plain form was 4 to 5 % slower at K = 768 (profiles/train_shared_ab.txt)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -179,19 +182,8 @@ __global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __rest
                 for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     }
-    // C/D map: row 4 (lane / 16) + r, column lane & 15
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wm * 64 + i * 16 + fk * 4 + r;
-            if (m >= M) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = n0 + wn * 64 + j * 16 + fr;
-                if (n < K) out[(size_t)m * (SEG ? seg.ldo : K) + n] = acc[i][j][r];
-            }
-        }
+    const int ldo = SEG ? seg.ldo : K;
+    for_each_acc64(acc, m0 + wm * 64, n0 + wn * 64, M, K, fr, fk, [=](int m, int n, int, float x) { out[(size_t)m * ldo + n] = x; });
 }
 
 // part[split][O][K] = sum over the split's rows of dZ[r, o] a[r, k], a = (A - mu) rstd with `stats`, A itself without; pdb[split][O] = the
@@ -219,10 +211,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(DzSrc z, const float* __rest
         bok[e] = want_dw && n0 + sc[e] < K;
     }
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     f32x4 ra[2], rb[2];
     auto fetch = [&](int r0) {
 #pragma unroll
@@ -272,18 +261,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(DzSrc z, const float* __rest
     if (sum_cols && o0 + tid < O) pdb[(size_t)split * O + o0 + tid] = colsum;
     if (!want_dw) return;
     float* P = part + (size_t)split * O * K;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int o = o0 + wm * 64 + i * 16 + fk * 4 + r;
-            if (o >= O) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = n0 + wn * 64 + j * 16 + fr;
-                if (n < K) P[(size_t)o * K + n] = acc[i][j][r];
-            }
-        }
+    for_each_acc64(acc, o0 + wm * 64, n0 + wn * 64, O, K, fr, fk, [=](int o, int n, int, float x) { P[(size_t)o * K + n] = x; });
 }
 
 // one block per row o' of the partials; unperm: the row is written at (o' % 7) 256 + o' / 7.  gamma / beta NULL: dW = sum_s P_s.

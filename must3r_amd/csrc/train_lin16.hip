@@ -3,7 +3,7 @@
 // rounded to bf16 (nearest even, NaN and inf kept: the result of Tensor.to(torch.bfloat16)) in registers on their way into LDS.  There is no cast pass and no
 // 16-bit copy of a weight.  Products of two bf16 values are exact in fp32, so the only error beside the operand rounding is the fp32 summation.
 //
-//   linear_fwd_bf16<EPI>  NT: out[M, N] = bf16(A)[M, K] bf16(W)[N, K]^T + bias, the epilogues of linear_fwd_f32 (train_block.hip) in the same fp32 arithmetic.
+//   linear_fwd_bf16<EPI>  NT: out[M, N] = bf16(A)[M, K] bf16(W)[N, K]^T + bias, then the epilogue it shares with linear_fwd_f32 (train_lin.hpp lin_epilogue).
 //   dgrad_bf16            NN: out[M, K] = bf16(dZ)[M, O] bf16(W)[O, K]; the rows of W may live in two parameters (launch_dgrad_seg_f32): one kernel, the seam a
 //                         kernel argument, so that the segmented form has the bits of the plain one on a packed copy.
 //   wgrad_bf16            TN: P_s[O, K] = sum_{r in split s} bf16(dZ)[r, o] bf16(A)[r, k]; split rule, partial layout and reduce are wgrad_kernel's
@@ -14,7 +14,7 @@
 // W of the forward, dZ of dgrad) is staged as 8 floats -> one 16-byte write into a [128 free][32 contraction] bf16 tile with rows padded to 40 elements (80 bytes):
 // a lane's fragment, 8 consecutive contraction indices of one row, is one 16-byte read, and the 16 rows of a fragment start in 16 different groups of 4 banks.
 // An operand whose contraction index is its slow dimension (W of dgrad, both operands of wgrad) goes to LDS as it lies, [32 contraction][128 free] with rows
-// padded to 144 elements, one 8-byte write per thread and row, and is transposed by the read: a fragment is two ds_read_b64_tr_b16 (common.hpp lds_read_tr4_x8).
+// padded to 144 elements, one 8-byte write per thread and row, and is transposed by the read: a fragment is two ds_read_b64_tr_b16 (train_tile.hpp frag_tr4).
 // With 144-element rows the 8 rows a 32-lane half reads start 8 banks apart.  Transposing at the LDS write instead was built and timed for both kernels and was
 // 2 to 16 % slower (profiles/linear16_transpose_ab.txt).
 // Tails: a step that reaches past the contraction (K = 16, 48: half a step; the last rows of a split) and rows and columns past M, N, O are filled by a select
@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "train_common.hpp"
 #include "train_lin.hpp"
+#include "train_tile.hpp"
 
 namespace m3r {
 
@@ -34,12 +35,9 @@ constexpr int TRP = 144;                               // and of a [32][128] til
 static thread_local int g_train_linear_mode = MUST3R_TRAIN_LINEAR_F32;
 bool train_linear_bf16() { return g_train_linear_mode == MUST3R_TRAIN_LINEAR_BF16; }
 
-__device__ __forceinline__ f32x4 ld4_or_zero(const float* p, bool ok) { return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f}; }
-
 // 8 consecutive contraction indices of one row: one 16-byte LDS write
 __device__ __forceinline__ void put_row8(bf16_t* dst, f32x4 lo, f32x4 hi) {
-    const bf16x4 a = cvt4<bf16_t>(lo), b = cvt4<bf16_t>(hi);
-    *reinterpret_cast<bf16x8*>(dst) = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+    *reinterpret_cast<bf16x8*>(dst) = cat8(cvt4<bf16_t>(lo), cvt4<bf16_t>(hi));
 }
 // one 32-deep step of a wave's 64 x 64: A[row lane & 15][k = 8 (lane >> 4) + e], B[k][column lane & 15]; both tiles are [free][contraction] (the forward)
 __device__ __forceinline__ void mma_step(const bf16_t* As, const bf16_t* Bs, int wm, int wn, int fr, int fk, f32x4 (&acc)[4][4]) {
@@ -52,13 +50,6 @@ __device__ __forceinline__ void mma_step(const bf16_t* As, const bf16_t* Bs, int
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
-}
-
-__device__ __forceinline__ void zero_acc(f32x4 (&acc)[4][4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 // K % 16 == 0: a thread's 8 floats (columns 8 (tid & 3) ... + 7 of a step) lie inside the contraction or past it as a whole
@@ -108,38 +99,13 @@ __global__ void __launch_bounds__(256) linear_fwd_bf16(LinArgs p) {
         if (k0 + TK < p.K) fetch(k0 + TK);
         mma_step(As, Bs, wm, wn, fr, fk, acc);
     }
-    // C/D map: row 4 (lane / 16) + r, column lane & 15; the epilogues as linear_fwd_f32 writes them
-    float bj[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + j * 16 + fr;
-        bj[j] = p.bias && n < p.N ? p.bias[n] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wm * 64 + i * 16 + fk * 4 + r;
-            if (m >= p.M) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = n0 + wn * 64 + j * 16 + fr;
-                if (n >= p.N) continue;
-                const float z = acc[i][j][r] + bj[j];
-                if constexpr (EPI == LIN_BIAS) p.out[(size_t)m * p.ldc + n] = z;
-                if constexpr (EPI == LIN_BIAS_RES) p.out[(size_t)m * p.ldc + n] = p.res[(size_t)m * p.ldres + n] + z;
-                if constexpr (EPI == LIN_BIAS_GELU) {
-                    if (p.zout) p.zout[(size_t)m * p.ldz + n] = z;
-                    p.out[(size_t)m * p.ldc + n] = gelu_f32(z);
-                }
-            }
-        }
+    lin_epilogue<EPI>(p, acc, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
 // O % 16 == 0, O0 % 16 == 0, K % 4 == 0.  Rows [0, O0) of W come from W0, rows [O0, O) from W1 (O0 = O: W0 alone), chosen row by row.
 // dZ is staged like the forward's A; W, whose contraction index is its slow dimension, goes to LDS as it lies, [32 rows][128 columns] with rows of TRP elements,
-// and is transposed by the read (ds_read_b64_tr_b16, as in wgrad_bf16 below): lane group g takes the rows 4 g ... 4 g + 3 and 16 + 4 g ... 16 + 4 g + 3 of a step as its
-// 8 contraction indices, and reads the same 8 of dZ's step with two 8-byte reads.  (Transposing W at the LDS write instead was built and timed: 9 to 16 % slower.)
+// and is transposed by the read (train_tile.hpp frag_tr4, which states the row permutation): a lane group reads the same 8 contraction indices of dZ's step
+// with two 8-byte reads, at 4 fk and 16 + 4 fk.  (Transposing W at the LDS write instead was built and timed: 9 to 16 % slower.)
 __global__ void __launch_bounds__(256) dgrad_bf16(const float* __restrict__ dZ, int ldz, const float* __restrict__ W0, const float* __restrict__ W1, int O0,
                                                   float* __restrict__ out, int ldo, int M, int O, int K, int n_tiles) {
     __shared__ __attribute__((aligned(16))) bf16_t As[TM * TP];
@@ -188,41 +154,26 @@ __global__ void __launch_bounds__(256) dgrad_bf16(const float* __restrict__ dZ, 
         __syncthreads();
         if (k0 + TK < O) fetch(k0 + TK);
         // lane group g multiplies the contraction indices 4 g ... 4 g + 3 and 16 + 4 g ... 16 + 4 g + 3 of the step: A by two 8-byte reads, W by two transposing ones
-        bf16x4 hb[8];
-        const bf16_t* pb = Bs + trow * TRP + wn * 64 + tcol;
-        lds_read_tr4_x8<bf16_t>(pb, pb + 16 * TRP, pb + 16, pb + 16 * TRP + 16, pb + 32, pb + 16 * TRP + 32, pb + 48, pb + 16 * TRP + 48, hb);
         bf16x8 a[4], b[4];
+        frag_tr4<TRP>(Bs + trow * TRP + wn * 64 + tcol, b);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bf16_t* pa = As + (wm * 64 + i * 16 + fr) * TP + fk * 4;
-            a[i] = __builtin_shufflevector(*reinterpret_cast<const bf16x4*>(pa), *reinterpret_cast<const bf16x4*>(pa + 16), 0, 1, 2, 3, 4, 5, 6, 7);
-            b[i] = __builtin_shufflevector(hb[2 * i], hb[2 * i + 1], 0, 1, 2, 3, 4, 5, 6, 7);
+            a[i] = cat8(*reinterpret_cast<const bf16x4*>(pa), *reinterpret_cast<const bf16x4*>(pa + 16));
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wm * 64 + i * 16 + fk * 4 + r;
-            if (m >= M) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = n0 + wn * 64 + j * 16 + fr;
-                if (n < K) out[(size_t)m * ldo + n] = acc[i][j][r];
-            }
-        }
+    for_each_acc64(acc, m0 + wm * 64, n0 + wn * 64, M, K, fr, fk, [=](int m, int n, int, float x) { out[(size_t)m * ldo + n] = x; });
 }
 
 // part[split][O][K] and pdb[split][O] as wgrad_kernel leaves them (train_head.hip); O % 4 == 0, K % 4 == 0.  want_dw = 0: only the column sums (one column tile).
 // Both operands have the contraction (the rows) as their slow dimension, and the transpose is left to the LDS read: the tiles are [32 rows][128 columns] bf16 as
-// the operands lie in memory (rows padded to TRP elements), written with one 8-byte store per thread and row, and a fragment is two ds_read_b64_tr_b16
-// (common.hpp lds_read_tr4_x8).  Lane group g of a fragment takes the tile rows 4 g ... 4 g + 3 and 16 + 4 g ... 16 + 4 g + 3 as its 8 contraction indices -- the
-// same permutation of the 32 rows of a step for both operands, so the products that meet are those of equal rows; with TRP = 144 the 8 rows a 32-lane half
-// reads start 8 banks apart.  (Transposing at the LDS write instead was built and timed: 2 to 14 % slower.)
+// the operands lie in memory (rows padded to TRP elements), written with one 8-byte store per thread and row, and both are read with train_tile.hpp frag_tr4 -- the same permutation
+// of the 32 rows of a step for both operands, so the products that meet are those of equal rows; with TRP = 144 the 8 rows a 32-lane half reads start 8 banks
+// apart.  (Transposing at the LDS write instead was built and timed: 2 to 14 % slower.)
 // The column sums: a thread adds the fp32 dZ values it fetched, step after step in row order; the 8 threads of a column group are added in a fixed order.
 __global__ void __launch_bounds__(256) wgrad_bf16(const float* __restrict__ dZ, int ldz, const float* __restrict__ A, int lda, int M, int O, int K,
                                                      int rows_per_split, int o_tiles, int n_tiles, int want_dw, float* __restrict__ part,
@@ -265,17 +216,9 @@ __global__ void __launch_bounds__(256) wgrad_bf16(const float* __restrict__ dZ, 
         __syncthreads();
         if (r0 + TK < r_hi) fetch(r0 + TK);
         if (want_dw) {
-            bf16x4 ha[8], hb[8];
-            const bf16_t* pa = As + trow * TRP + wm * 64 + tcol;
-            const bf16_t* pb = Bs + trow * TRP + wn * 64 + tcol;
-            lds_read_tr4_x8<bf16_t>(pa, pa + 16 * TRP, pa + 16, pa + 16 * TRP + 16, pa + 32, pa + 16 * TRP + 32, pa + 48, pa + 16 * TRP + 48, ha);
-            lds_read_tr4_x8<bf16_t>(pb, pb + 16 * TRP, pb + 16, pb + 16 * TRP + 16, pb + 32, pb + 16 * TRP + 32, pb + 48, pb + 16 * TRP + 48, hb);
             bf16x8 a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                a[i] = __builtin_shufflevector(ha[2 * i], ha[2 * i + 1], 0, 1, 2, 3, 4, 5, 6, 7);
-                b[i] = __builtin_shufflevector(hb[2 * i], hb[2 * i + 1], 0, 1, 2, 3, 4, 5, 6, 7);
-            }
+            frag_tr4<TRP>(As + trow * TRP + wm * 64 + tcol, a);
+            frag_tr4<TRP>(Bs + trow * TRP + wn * 64 + tcol, b);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -294,18 +237,7 @@ __global__ void __launch_bounds__(256) wgrad_bf16(const float* __restrict__ dZ, 
     }
     if (!want_dw) return;
     float* P = part + (size_t)split * O * K;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int o = o0 + wm * 64 + i * 16 + fk * 4 + r;
-            if (o >= O) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = n0 + wn * 64 + j * 16 + fr;
-                if (n < K) P[(size_t)o * K + n] = acc[i][j][r];
-            }
-        }
+    for_each_acc64(acc, o0 + wm * 64, n0 + wn * 64, O, K, fr, fk, [=](int o, int n, int, float x) { P[(size_t)o * K + n] = x; });
 }
 
 int launch_linear_bf16(const char* who, int epi, const LinArgs& p, hipStream_t s) {
@@ -337,12 +269,6 @@ int launch_wgrad_parts_bf16(const float* dZ, int ldz, const float* A, int lda, i
 using namespace m3r;
 
 extern "C" int must3r_hip_train_linear_mode(int mode) {
-    if (mode == -1) return g_train_linear_mode;
-    if (mode != MUST3R_TRAIN_LINEAR_F32 && mode != MUST3R_TRAIN_LINEAR_BF16) {
-        fail("train_linear_mode: unknown mode %d (MUST3R_TRAIN_LINEAR_F32 = 0, MUST3R_TRAIN_LINEAR_BF16 = 1, -1 to query)", mode);
-        return -1;
-    }
-    const int prev = g_train_linear_mode;
-    g_train_linear_mode = mode;
-    return prev;
+    return swap_thread_mode(g_train_linear_mode, mode, MUST3R_TRAIN_LINEAR_BF16,
+                            "train_linear_mode: unknown mode %d (MUST3R_TRAIN_LINEAR_F32 = 0, MUST3R_TRAIN_LINEAR_BF16 = 1, -1 to query)");
 }

@@ -27,7 +27,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._train_common import HEAD, _dev, _ld, _ptr, _stream, _strided_rows
+from ._train_common import HEAD, _dev, _ld, _ptr, _record_modes, _recorded_modes, _stream, _strided_rows
 from ._train_common import attention_precision, current_attention_precision   # noqa: F401  (re-exported: ``with train_attention.attention_precision("bf16"):``)
 
 
@@ -245,7 +245,8 @@ class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, tab, heads, dtype, mask=None):
         ctx.save_for_backward(q, k, v)
-        ctx.tab, ctx.heads, ctx.mask, ctx.attn_precision = tab, heads, mask, current_attention_precision()
+        ctx.tab, ctx.heads, ctx.mask = tab, heads, mask
+        _record_modes(ctx, attention=True)
         return _forward(q, k, v, tab, heads, dtype, mask)
 
     @staticmethod
@@ -254,7 +255,7 @@ class _Attention(torch.autograd.Function):
         q, k, v = ctx.saved_tensors
         heads = ctx.heads
         f = [_fp32_rows(t, n, heads) for t, n in ((q, "q"), (k, "k"), (v, "v"), (grad_out, "the upstream gradient"))]
-        with attention_precision(ctx.attn_precision):   # autograd's thread starts in the default mode, and backward() may run after the block has ended
+        with _recorded_modes(ctx):   # autograd's thread starts in the default mode, and backward() may run after the block has ended
             grads = attention_grad(*f, ctx.tab, heads, want=tuple(ctx.needs_input_grad[:3]), mask=ctx.mask)
         out = [None if g is None else g.to(t.dtype) for g, t in zip(grads, (q, k, v))]
         return (*out, None, None, None, None)

@@ -28,7 +28,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _new, _Proj, _ptr, _rows, _scratch, _stream
+from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _new, _Proj, _ptr, _record_modes, _recorded_modes, _rows, _scratch, _stream
 from ._train_common import current_precision, linear_precision   # noqa: F401  (re-exported: ``with train_block.linear_precision("bf16"):``)
 from ._train_common import amp, attention_precision, current_attention_precision   # noqa: F401  (re-exported: ``with train_block.amp("bf16"):``)
 from .train_attention import _check_table, _table, n_groups, self_views
@@ -215,14 +215,14 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight, bias)
-        ctx.precision = current_precision()
+        _record_modes(ctx, linear=True)
         return linear_forward(_rows(x), _f32(weight), _f32(bias)).view(*x.shape[:-1], weight.shape[0])
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         x, weight, bias = ctx.saved_tensors
-        with linear_precision(ctx.precision):
+        with _recorded_modes(ctx):
             grads = linear_grad(_rows(x), _f32(weight), _rows(grad_out), want=tuple(ctx.needs_input_grad[:3]))
         return tuple(_back(grads, (x, weight, bias)))
 
@@ -246,14 +246,15 @@ class _Mlp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b, eps):
         ctx.save_for_backward(x, norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b)
-        ctx.eps, ctx.precision = eps, current_precision()
+        ctx.eps = eps
+        _record_modes(ctx, linear=True)
         return mlp_forward(_rows(x), *(_f32(t) for t in (norm_w, norm_b, fc1_w, fc1_b, fc2_w, fc2_b)), eps).view(x.shape)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         saved = ctx.saved_tensors
-        with linear_precision(ctx.precision):
+        with _recorded_modes(ctx):
             grads = mlp_grad(_rows(saved[0]), *(_f32(t) for t in saved[1:]), _rows(grad_out), ctx.eps, want=tuple(ctx.needs_input_grad[:7]))
         return (*_back(grads, saved), None)
 
@@ -262,14 +263,15 @@ class _Attn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, pos, tab, rope_tab, eps):
         ctx.save_for_backward(x, norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b, pos)
-        ctx.tab, ctx.rope_tab, ctx.eps, ctx.precision, ctx.attn_precision = tab, rope_tab, eps, current_precision(), current_attention_precision()
+        ctx.tab, ctx.rope_tab, ctx.eps = tab, rope_tab, eps
+        _record_modes(ctx, linear=True, attention=True)
         return attn_forward(_rows(x), pos, tab, rope_tab, *(_f32(t) for t in (norm_w, norm_b, qkv_w, qkv_b, proj_w, proj_b)), eps).view(x.shape)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         *saved, pos = ctx.saved_tensors
-        with linear_precision(ctx.precision), attention_precision(ctx.attn_precision):
+        with _recorded_modes(ctx):
             grads = attn_grad(_rows(saved[0]), pos, ctx.tab, ctx.rope_tab, *(_f32(t) for t in saved[1:]), _rows(grad_out), ctx.eps,
                               want=tuple(ctx.needs_input_grad[:7]))
         return (*_back(grads, saved), None, None, None, None)

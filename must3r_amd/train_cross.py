@@ -32,9 +32,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import train_block as TB
-from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _ld, _new, _Proj, _ptr, _rows, _scratch, _stream
+from ._train_common import HEAD, _Affine, _back, _call_sublayer, _check_params, _check_x, _dev, _f32, _ld, _new, _Proj, _ptr, _record_modes, _recorded_modes, _rows, _scratch, _stream
 from ._train_common import _strided_rows as _mem_rows
-from ._train_common import attention_precision, current_attention_precision, current_precision, linear_precision
 from .train_attention import _check_table, _mask, _table, n_groups
 from .train_attention import self_views as _self_views
 from .train_block import ROPE_NPOS, _AttnParams, _MlpParams
@@ -114,7 +113,8 @@ class _Cross(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b, tab, eps, mask=None):
         ctx.save_for_backward(x, mem, norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)
-        ctx.tab, ctx.eps, ctx.mask, ctx.precision, ctx.attn_precision = tab, eps, mask, current_precision(), current_attention_precision()
+        ctx.tab, ctx.eps, ctx.mask = tab, eps, mask
+        _record_modes(ctx, linear=True, attention=True)
         width = int(mem.shape[1])
         return cross_forward(_rows(x), _mem_rows(mem, width), tab, *(_opt(t) for t in (norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b)), eps,
                              mask).view(x.shape)
@@ -124,7 +124,7 @@ class _Cross(torch.autograd.Function):
     def backward(ctx, grad_out):
         saved = ctx.saved_tensors
         x, mem = saved[0], saved[1]
-        with linear_precision(ctx.precision), attention_precision(ctx.attn_precision):
+        with _recorded_modes(ctx):
             grads = cross_grad(_rows(x), _mem_rows(mem, int(mem.shape[1])), ctx.tab, *(_opt(t) for t in saved[2:]), _rows(grad_out), ctx.eps,
                                want=tuple(ctx.needs_input_grad[:12]), mask=ctx.mask)
         # CROSS_OUTPUTS is in the order of the inputs

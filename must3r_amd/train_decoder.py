@@ -32,8 +32,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import train_block as TB
-from ._train_common import HEAD, _Affine, _back, _check_params, _check_x, _dev, _f32, _new, _Proj, _rows, _scratch, _stream
-from ._train_common import current_precision, linear_precision
+from ._train_common import HEAD, _Affine, _back, _check_params, _check_x, _dev, _f32, _new, _Proj, _record_modes, _recorded_modes, _rows, _scratch, _stream
 from .train_attention import _table, memory_views, self_views
 from .train_block import ROPE_NPOS, _MlpParams
 from .train_cross import MEMORY_MODES, CachedDecoderBlock, memory_rows
@@ -184,13 +183,14 @@ class _FeedbackOffset(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, norm_w, norm_b, w1, b1, w2, b2, eps):
         ctx.save_for_backward(x, norm_w, norm_b, w1, b1, *([w2, b2] if w2 is not None else []))
-        ctx.eps, ctx.mlp, ctx.precision = eps, w2 is not None, current_precision()
+        ctx.eps, ctx.mlp = eps, w2 is not None
+        _record_modes(ctx, linear=True)
         return _offset_forward(x, norm_w, norm_b, w1, b1, w2, b2, eps)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        with linear_precision(ctx.precision):   # the Linears recomputed and differentiated below multiply as the forward's did
+        with _recorded_modes(ctx):   # the Linears recomputed and differentiated below multiply as the forward's did
             return _FeedbackOffset._backward(ctx, grad_out)
 
     @staticmethod
