@@ -228,10 +228,11 @@ int must3r_hip_postprocess_cam_act(const float* pointmaps, int activation, int n
  * must3r_hip_row_norm: attention = x.norm(dim=-1) (:130-131).
  * must3r_hip_l2_normalize: F.normalize(x, dim) of a contiguous fp32 tensor seen as [outer, L, inner] (eps 1e-12):
  *   Whitener(l2norm=dim) (:77-78).  out may alias x.
- * must3r_hip_layernorm_act_f32: nn.LayerNorm(C, eps) (+ nn.GELU, erf form, when gelu) on fp32 rows: the hidden layers of a
+ * must3r_hip_layernorm_act_f32: nn.LayerNorm(C, eps) (+ nn.GELU, exact form z Phi(z), when gelu) on fp32 rows: the hidden layers of a
  *   multi-layer projector (build_projector :139-151, Linear - LayerNorm - GELU stacks); gamma / beta may be NULL.
- * must3r_hip_topk_gather: how_select_local (:91-101): per image the k tokens of largest attention, sorted descending
- *   (ties: lower index first), their features, attentions and int64 indices.  N <= 4096.
+ * must3r_hip_topk_gather: how_select_local (:91-101): per image the k tokens of largest attention in the order of a
+ *   stable descending sort (NaN first, as torch.topk ranks it; ties and NaNs among themselves: lower index first), their
+ *   features, attentions and int64 indices.  k <= N <= 4096, C % 4 == 0.
  * must3r_hip_weighted_spoc: weighted_spoc (:82-88): normalize(sum_n attn[n] * feat[n,:]). */
 int must3r_hip_affine(int is_double, const float* A, const void* sub, const void* B, int b_transposed, const void* bias,
                       const float* resid, float* out, int M, int N, int K, void* stream);

@@ -7,8 +7,8 @@
 //                        v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32 (exact products, TC accumulation).
 //                        B is [K,N] row-major (Whitener.p) or the transposed view of an nn.Linear weight [N,K].
 //   row_norm_kernel      attn[r] = |x[r,:]|_2, wave per row
-//   topk_kernel          per image: bitonic sort of (attn, index) pairs in LDS (N <= 4096), descending, ties by lower
-//                        index; gathers the first k rows of the features
+//   topk_kernel          per image: bitonic sort of (attn, index) pairs in LDS (N <= 4096): a stable descending sort, NaN
+//                        first (as torch.topk ranks it), ties by lower index; gathers the first k rows of the features
 //   l2_normalize_*       F.normalize along any dimension of a contiguous tensor (Whitener(l2norm=dim))
 //   ln_act_f32_kernel    fp32 LayerNorm + erf GELU: the hidden layers of a multi-layer projector
 //   spoc_kernel          per image: out = normalize(sum_n attn[n] feat[n,:])  (fp32 sums in token order, F.normalize eps 1e-12)
@@ -125,7 +125,11 @@ __global__ void __launch_bounds__(256) row_norm_kernel(const float* __restrict__
     if (lane == 0) out[row] = sqrtf(s);
 }
 
-// one block per image; N <= 4096 keys.  Sort key: attention descending, then index ascending (deterministic ties).
+// one block per image; N <= 4096 keys.  Contract: a stable descending sort of the keys, as torch.topk / torch.sort(descending, stable) order them --
+// NaN ranks before every number, then the numbers descending; equal keys, and NaNs among themselves, by lower index.  The comparator below is a TOTAL
+// order on (key, index) pairs (a strict weak order is not enough: with `ka > kb || (ka == kb && ia < ib)` a NaN key ranks neither before nor after
+// anything, the bitonic network permutes without sorting, and a padding slot can land among the first k).  Padding (-inf, 0x7fffffff) ties with a real
+// -inf and loses to it by index, so it stays behind all N real pairs and every idx[j], j < k <= N, is below N by construction: the gather needs no clamp.
 __global__ void __launch_bounds__(1024) topk_kernel(const float* __restrict__ feat, const float* __restrict__ attn, int N, int C, int k,
                                                     float* __restrict__ out_feat, float* __restrict__ out_attn, long long* __restrict__ out_idx) {
     __shared__ float key[4096];
@@ -146,7 +150,8 @@ __global__ void __launch_bounds__(1024) topk_kernel(const float* __restrict__ fe
                 const bool desc = ((lo & size) == 0);              // first half of each bitonic block sorted descending
                 const float ka = key[lo], kb = key[hi];
                 const int ia = idx[lo], ib = idx[hi];
-                const bool a_first = (ka > kb) || (ka == kb && ia < ib);   // a ranks before b
+                const bool na = ka != ka, nb = kb != kb;
+                const bool a_first = (na && !nb) || (na == nb && (ka > kb || ((ka == kb || na) && ia < ib)));   // a ranks before b: NaN first, ties by index
                 if (a_first != desc) {
                     key[lo] = kb; key[hi] = ka;
                     idx[lo] = ib; idx[hi] = ia;
@@ -216,8 +221,9 @@ __global__ void __launch_bounds__(256) l2_normalize_rows_copy_kernel(const float
     for (int c = lane; c < C; c += 64) out[row * C + c] = x[row * C + c] * inv;
 }
 
-// nn.LayerNorm (two passes over the row held by one wave: mean, then centred variance) followed by nn.GELU (erf form, libm erff):
-// the hidden layers of a multi-layer projector (retrieval/model.py:139-151: Linear - LayerNorm - GELU stacks), all fp32.
+// nn.LayerNorm (two passes over the row held by one wave: mean, then centred variance -- corrected: the second pass also sums the residuals x - mu, whose mean
+// is what the fp32 sum of the first pass lost (it rounds at the size of C |mean|, the residuals at the size of the spread)) followed by nn.GELU
+// (exact form, z Phi(z) with Phi = erfc(-z / sqrt 2) / 2): the hidden layers of a multi-layer projector (retrieval/model.py:139-151: Linear - LayerNorm - GELU stacks), all fp32.
 __global__ void __launch_bounds__(256) ln_act_f32_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float eps, int M, int C, int gelu,
                                                           float* __restrict__ out) {
@@ -227,16 +233,18 @@ __global__ void __launch_bounds__(256) ln_act_f32_kernel(const float* __restrict
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += xr[c];
     const float mu = wave_sum(s) / (float)C;
-    float q = 0.f;
+    float q = 0.f, t = 0.f;
     for (int c = lane; c < C; c += 64) {
         const float d = xr[c] - mu;
+        t += d;
         q += d * d;
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
+    const float dm = wave_sum(t) / (float)C;     // mean = mu + dm
+    const float rstd = 1.0f / sqrtf(fmaxf(wave_sum(q) / (float)C - dm * dm, 0.f) + eps);
     for (int c = lane; c < C; c += 64) {
-        float v = (xr[c] - mu) * rstd;
+        float v = ((xr[c] - mu) - dm) * rstd;
         v = v * (gamma ? gamma[c] : 1.0f) + (beta ? beta[c] : 0.0f);
-        if (gelu) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+        if (gelu) v = v * (0.5f * erfcf(-0.70710678118654752440f * v));   // Phi through erfc: 1 + erf cancels in the negative tail (370 u at z = -3)
         out[(size_t)row * C + c] = v;
     }
 }

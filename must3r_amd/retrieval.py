@@ -108,7 +108,10 @@ def weighted_spoc(feat, attn):
 
 
 def how_select_local(feat, attn, nfeat):
-    """retrieval/model.py:91-101 -> (topk_features [B,k,C], topk_attn [B,k], topk_indices int64 [B,k])."""
+    """retrieval/model.py:91-101 -> (topk_features [B,k,C], topk_attn [B,k], topk_indices int64 [B,k]).
+
+    Order: a stable descending sort of ``attn`` -- NaN first (as ``torch.topk`` ranks it), then the numbers descending; equal values, and NaNs among
+    themselves, by lower index.  ``k = min(nfeat, N)``, with a negative ``nfeat`` a fraction of N."""
     feat, attn = _tokens(feat, "feat"), _tokens(attn, "attn")
     Bn, N, Cd = feat.shape
     if nfeat < 0:
