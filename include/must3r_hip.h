@@ -1062,6 +1062,28 @@ int must3r_hip_train_linear_mode(int mode);
 /* Per host thread; default F32.  Returns the previous mode.  mode = -1 only queries.  Any other value: returns -1, last error set, nothing changed. */
 int must3r_hip_train_attention_mode(int mode);
 
+/* ABI 21, additive.  The gather in front of the trainable encoder's patch embedding (dust3r's PatchEmbedDust3R and ManyAR_PatchEmbed as a Linear over
+ * rows; csrc/train_encoder.hip): the fp32 image batch img [V][3][H][W] becomes fp32 rows [V N][768], N = (H / 16)(W / 16), in the column order of the flattened
+ * conv weight, k = c 256 + dy 16 + dx (the order of must3r_hip_op_im2col, whose rows are 16-bit and know one orientation), and the int64 positions pos [V N][2].
+ * The orientation is per view and comes from a DEVICE array: transposed[v] != 0 marks a portrait view of a batch stored landscape; NULL means no view is.
+ *   landscape   grid H/16 x W/16   token t = (py, px) = (t / (W/16), t % (W/16))   rows[v N + t][k] = img[v][c][16 py + dy][16 px + dx]   pos = (py, px)
+ *   portrait    grid W/16 x H/16   token t = (py, px) = (t / (H/16), t % (H/16))   rows[v N + t][k] = img[v][c][16 px + dx][16 py + dy]   pos = (py, px)
+ * The portrait form is the reference's proj(img.swapaxes(-1, -2)) with the positions of the swapped grid; the host never learns which views are portrait.
+ * The Linear that follows is must3r_hip_op_linear_f32 on the rows: nothing is fused.  Either output may be NULL, costs nothing then and is not written
+ * (rows == NULL: positions alone).  The stream travels in the descriptor (`stream`, a hipStream_t): all work goes to it, nothing waits on the host.
+ * Determinism: a permutation -- one writer per element, no atomics, no arithmetic on the values; 64-bit offsets.
+ * Refused with an error before anything is read or launched: a NULL descriptor, a NULL img, both outputs NULL, V <= 0, H or W not a positive multiple of 16,
+ * img, rows or pos not 16-byte aligned, transposed not 4-byte aligned, more than 2^29 - 1 rows. */
+typedef struct must3r_hip_patch_rows_args {
+    const float*   img;          /* [V, 3, H, W] */
+    const int32_t* transposed;   /* [V] on the device, optional */
+    float*         rows;         /* [V * N, 768], optional */
+    int64_t*       pos;          /* [V * N, 2], optional */
+    int32_t V, H, W, reserved;
+    void* stream;                /* hipStream_t */
+} must3r_hip_patch_rows_args;
+int must3r_hip_patch_rows(const must3r_hip_patch_rows_args* a);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

@@ -228,6 +228,13 @@ class OptimArgs(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class PatchRowsArgs(C.Structure):
+    """must3r_hip_patch_rows_args: the image batch, the DEVICE orientation flags, the (optional) rows and positions and the stream of the gather in front
+    of the trainable patch embedding (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("img", C.c_void_p), ("transposed", C.c_void_p), ("rows", C.c_void_p), ("pos", C.c_void_p),
+                ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32), ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -343,6 +350,7 @@ PROTOTYPES = {
     "must3r_hip_optim_adamw": (i32, [P(OptimArgs), vp, sz]),
     "must3r_hip_train_linear_mode": (i32, [i32]),
     "must3r_hip_train_attention_mode": (i32, [i32]),
+    "must3r_hip_patch_rows": (i32, [P(PatchRowsArgs)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

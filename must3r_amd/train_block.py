@@ -64,6 +64,13 @@ def check_positions(pos, npos):
     return pos
 
 
+def _positions_checked(pos, npos):
+    """Registers ``pos`` as a tensor that passed ``check_positions(pos, npos)`` without reading it: for a producer whose positions lie in ``[0, npos)`` by
+    construction (``train_encoder``: a grid the host has compared with ``npos``), so that the blocks that follow do not copy its extremes to the host."""
+    _checked_positions[0] = (weakref.ref(pos), pos._version, int(npos))
+    return pos
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # the operator forms, on fp32 GPU tensors
 # ---------------------------------------------------------------------------------------------------------------------------------------
