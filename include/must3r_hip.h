@@ -704,6 +704,38 @@ int must3r_hip_op_head_linear(int dtype, const float* y, const float* W, const f
                               size_t scratch_bytes, void* stream);
 size_t must3r_hip_head_grad_scratch_bytes(int n_views, int H, int Wimg, int D);
 int must3r_hip_head_grad(const must3r_hip_head_grad_args* a, void* scratch, size_t scratch_bytes, void* stream);
+/* ABI 21, additive.  The head over a batch stored landscape (H <= Wimg) whose views may be portrait: the reference's transpose_to_landscape(head,
+ * activate=True) (blocks/head.py:24-60), with the orientation per view from a DEVICE array in the dtype and meaning of must3r_hip_patch_rows_args.transposed
+ * (int32 [n_views], non-zero = portrait), so that one tensor serves both calls and the host never learns the flags.  With gh = H/16, gw = Wimg/16:
+ *   landscape view   token t = gy gw + gx   pointmaps[v][16 gy + i][16 gx + j][c] = z[v N + t][c 256 + i 16 + j]           as must3r_hip_head_forward
+ *   portrait view    token t = py gh + px   pointmaps[v][16 px + j][16 py + i][c] = z[v N + t][c 256 + i 16 + j]           head(x, (Wimg, H)).swapaxes(1, 2)
+ * The backward is the adjoint: G is read through the same per-view map, dx follows the view's rows, dW / db / dgamma / dbeta sum over all views.
+ * Forward: the two launches of must3r_hip_head_forward write every view in place with the landscape geometry; then the 16 x 16 x 7 tiles of the flagged views
+ * are turned through LDS into the scratch and copied back (two launches whose blocks return at once in an unflagged view: those views pay no second pass, a
+ * flagged view's pixels are read and written twice more).  Backward: one launch turns the flagged views' tiles of G into the scratch in the slot order of their
+ * tokens, and the gather kernels of must3r_hip_head_grad take each row from G or from there by its view's flag -- the same 448-byte runs, the same k-ordered
+ * chain, the same split rule (the row count alone) and reduces; a 128-row tile may hold views of both kinds.  No atomics, one writer per element; repeated
+ * calls agree bit for bit.  transposed == NULL: exactly must3r_hip_head_forward / must3r_hip_head_grad, launch for launch.
+ * The descriptors embed the existing arguments plus the flag pointer and the stream (a hipStream_t: all work goes to it, nothing waits on the host).
+ * scratch: at least must3r_hip_head_*_many_ar_scratch_bytes -- the plain entry point's plus one copy of the pointmaps (0 on a bad shape), 16-byte aligned.
+ * Refused with an error before anything is launched: what the plain entry points refuse, H > Wimg with flags, transposed not 4-byte aligned. */
+typedef struct must3r_hip_head_forward_ar_args {
+    const float* x; const float* gamma; const float* beta; const float* W; const float* b;
+    int32_t dtype, n_views, H, Wimg, D;
+    float eps;
+    float* pointmaps;             /* [n_views, H, Wimg, 7] */
+    const int32_t* transposed;    /* [n_views] on the device, optional */
+    void* stream;                 /* hipStream_t */
+} must3r_hip_head_forward_ar_args;
+typedef struct must3r_hip_head_grad_ar_args {
+    must3r_hip_head_grad_args g;
+    const int32_t* transposed;    /* [n_views] on the device, optional */
+    void* stream;                 /* hipStream_t */
+} must3r_hip_head_grad_ar_args;
+size_t must3r_hip_head_forward_many_ar_scratch_bytes(int n_views, int H, int Wimg, int D);
+int must3r_hip_head_forward_many_ar(const must3r_hip_head_forward_ar_args* a, void* scratch, size_t scratch_bytes);
+size_t must3r_hip_head_grad_many_ar_scratch_bytes(int n_views, int H, int Wimg, int D);
+int must3r_hip_head_grad_many_ar(const must3r_hip_head_grad_ar_args* a, void* scratch, size_t scratch_bytes);
 /* the backward kernels one by one, in the plain forms a later Linear / LayerNorm backward calls (fp32, row-major):
  *   linear_dgrad_f32:  out[M][K] = dZ[M][O] (row stride ldz) W[O][K];  O % 16 == 0, K % 4 == 0, ldz % 4 == 0
  *   linear_wgrad_f32:  dW[O][K] = sum_r dZ[r][o] A[r][k] (row strides ldz, lda), db[O] = sum_r dZ[r][o]; either may be NULL; O, K, ldz, lda multiples of 4

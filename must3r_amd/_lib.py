@@ -138,6 +138,20 @@ class HeadGradArgs(C.Structure):
                 ("dx", C.c_void_p), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("dW", C.c_void_p), ("db", C.c_void_p)]
 
 
+class HeadForwardArArgs(C.Structure):
+    """must3r_hip_head_forward_ar_args: the arguments of must3r_hip_head_forward, the DEVICE orientation flags and the stream of the head's forward over a batch
+    stored landscape (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("W", C.c_void_p), ("b", C.c_void_p),
+                ("dtype", C.c_int32), ("n_views", C.c_int32), ("H", C.c_int32), ("Wimg", C.c_int32), ("D", C.c_int32), ("eps", C.c_float),
+                ("pointmaps", C.c_void_p), ("transposed", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class HeadGradArArgs(C.Structure):
+    """must3r_hip_head_grad_ar_args: the ABI 19 descriptor, the DEVICE orientation flags and the stream of the head's backward over a batch stored landscape
+    (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("g", HeadGradArgs), ("transposed", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class AttnTrainArgs(C.Structure):
     """must3r_hip_attn_train_args: operands, HOST view table and (optional) outputs of the attention training forward / backward (include/must3r_hip.h, ABI 20)."""
     _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("dO", C.c_void_p),
@@ -312,6 +326,10 @@ PROTOTYPES = {
     "must3r_hip_op_head_linear": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
     "must3r_hip_head_grad_scratch_bytes": (sz, [i32, i32, i32, i32]),
     "must3r_hip_head_grad": (i32, [P(HeadGradArgs), vp, sz, vp]),
+    "must3r_hip_head_forward_many_ar_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_head_forward_many_ar": (i32, [P(HeadForwardArArgs), vp, sz]),
+    "must3r_hip_head_grad_many_ar_scratch_bytes": (sz, [i32, i32, i32, i32]),
+    "must3r_hip_head_grad_many_ar": (i32, [P(HeadGradArArgs), vp, sz]),
     "must3r_hip_op_linear_dgrad_f32": (i32, [vp, i32, vp, vp, i32, i32, i32, vp]),
     "must3r_hip_op_linear_wgrad_scratch_bytes": (sz, [i32, i32, i32]),
     "must3r_hip_op_linear_wgrad_f32": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, sz, vp]),

@@ -20,6 +20,11 @@
 //                         per-lane column sums of dY x^ and dY, one partial per block.
 //                         <ADD> (ABI 21): dx = add + that, the residual of a pre-norm sublayer (train_block.hip); <false> is the kernel as it was.
 //   ln_grad_reduce_kernel sums the block partials in a fixed two-level order (16 interleaved slices, then the slices): dgamma, dbeta.
+//   head_turn_kernel, head_copy_flagged_kernel (ABI 21, additive: must3r_hip_head_forward_many_ar / _grad_many_ar) portrait views of a batch stored
+//                         landscape, flagged per view by a DEVICE array: the forward's tiles of those views are turned into their stored places after
+//                         the head's two launches, the backward's are laid out in the slot order of the tokens first, and dgrad_kernel<2> /
+//                         wgrad_kernel<2> pick each row's source by its view's flag (the comment above head_turn_kernel; DzSrc).  Without flags the
+//                         entry points launch what they launched.
 // In MUST3R_TRAIN_LINEAR_BF16 mode (must3r_hip_train_linear_mode) the plain forms -- run_dgrad and run_wgrad without GATHER and without statistics, and
 // launch_dgrad_seg_f32 -- launch dgrad_bf16 / wgrad_bf16 of train_lin16.hip after the same checks; the gather forms (the head's own) stay fp32.
 // The split count of the weight gradient and the block count of the LayerNorm backward are functions of the row count alone.  No atomics:
@@ -37,19 +42,26 @@ constexpr int HEAD_P2 = 256, HEAD_C = 7, HEAD_RUN = 16 * HEAD_C;  // 16 x 16 pat
 constexpr int WGRAD_MAX_SPLITS = 16, WGRAD_ROWS_PER_SPLIT = 128;
 constexpr int LNG_MAX_BLOCKS = 1024, LNG_MIN_ROWS = 16, LNG_MAX_T = 16;   // LayerNorm backward: D <= 64 * LNG_MAX_T
 
-// where the rows of dZ come from: a plain [M][ld] matrix, or the pixel-unshuffle of G [n_views][H][W][7]
+// where the rows of dZ come from: a plain [M][ld] matrix (DZ_PLAIN), the pixel-unshuffle of G [n_views][H][W][7] (DZ_GATHER), or that with a source
+// per view (DZ_GATHER_AR): the rows of a view with flags[v] != 0 are read at the same offsets from a second tensor, `alt` floats after p (head_turn_kernel
+// has laid the view's tiles out there in the slot order of its tokens).  A row's 16 runs of 448 bytes are the same in all three gather cases.
+constexpr int DZ_PLAIN = 0, DZ_GATHER = 1, DZ_GATHER_AR = 2;
 struct DzSrc {
     const float* p;
     long long ld;          // plain: row stride
     int ntok, gw, H, Wimg; // gather: tokens per view, patches per image row, image size
+    const int32_t* flags;  // DZ_GATHER_AR: [n_views] on the device
+    long long alt;         // DZ_GATHER_AR: the second tensor's distance from p, in floats
 };
-template <bool GATHER> __device__ __forceinline__ size_t dz_row(const DzSrc& z, int r) {
+template <int GATHER> __device__ __forceinline__ size_t dz_row(const DzSrc& z, int r) {
     if constexpr (!GATHER) return (size_t)r * (size_t)z.ld;
     const int v = r / z.ntok, t = r - v * z.ntok, gy = t / z.gw, gx = t - gy * z.gw;
-    return (((size_t)v * z.H + 16 * gy) * z.Wimg + 16 * gx) * HEAD_C;
+    const size_t at = (((size_t)v * z.H + 16 * gy) * z.Wimg + 16 * gx) * HEAD_C;
+    if constexpr (GATHER == DZ_GATHER_AR) return z.flags[v] != 0 ? at + (size_t)z.alt : at;
+    return at;
 }
 // column o' (a multiple of 4) of a row -> offset from the row's start
-template <bool GATHER> __device__ __forceinline__ size_t dz_col(const DzSrc& z, int o) {
+template <int GATHER> __device__ __forceinline__ size_t dz_col(const DzSrc& z, int o) {
     if constexpr (!GATHER) return (size_t)o;
     const int i = o / HEAD_RUN;
     return (size_t)i * z.Wimg * HEAD_C + (o - i * HEAD_RUN);
@@ -73,6 +85,84 @@ __global__ void __launch_bounds__(256) perm_w_kernel(const float* __restrict__ W
     const int o = blockIdx.x, src = (o % HEAD_C) * HEAD_P2 + o / HEAD_C;
     for (int k = threadIdx.x * 4; k < D; k += 1024)
         *reinterpret_cast<f32x4*>(Wp + (size_t)o * D + k) = *reinterpret_cast<const f32x4*>(W + (size_t)src * D + k);
+}
+
+// Portrait views of a batch stored landscape (the reference's transpose_to_landscape(head, activate=True), blocks/head.py:24-60).  A view is [H][Wimg][7]
+// with H <= Wimg, gh = H / 16, gw = Wimg / 16.  Token t of a portrait view is (py, px) = (t / gh, t % gh) of its own gw x gh grid, and its 16 x 16 x 7 tile
+// belongs, with i and j exchanged, at the stored slot (px, py); one launch over all rows with the landscape geometry puts (or expects) it unturned at the
+// token's slot (t / gw, t % gw).  head_turn_kernel moves the tiles of the flagged views between the two arrangements:
+//   to_slots = 0 (forward)   src [view][slot of t][i][j][c]  ->  dst [view][px][py][j][i][c]        the head's output -> the stored layout
+//   to_slots = 1 (backward)  src [view][px][py][j][i][c]     ->  dst [view][slot of t][i][j][c]     the upstream gradient -> what dz_row reads
+// A wave owns one tile: 7168 bytes, 16 pixel rows of 448 bytes (112 floats, 28 float4) at a stride of Wimg 28 bytes.  In each of 7 rounds lane l takes
+// float4 q = 64 n + l of the tile, (row, part) = (q / 28, q % 28): a 16-byte global load, and after the turn a 16-byte global store of float4 q of the
+// destination tile, so both sides move whole 448-byte runs.  A pixel is 28 bytes and does not fit the 16-byte grid, so the turn goes through the wave's own
+// part of the LDS, element (row i, float e = 7 j + c) of the source tile at dword
+//     A(i, e) = 116 i + e                                                            (HT_PITCH = 116, 1856 floats = 7424 bytes per wave)
+// written with one ds_write_b128 per round (A(i, 4 f .. 4 f + 3), 16-byte aligned as 116 % 4 == 0) and read with four ds_read_b32 per round: float k of the
+// destination's float4 (row j', part f) is element e' = 4 f + k of that row, pixel i = e' / 7, channel c = e' % 7, at A(e' / 7, 7 j' + e' % 7).
+// Bank conflicts by the rules for these widths (bank = dword address mod 32 for both; a ds_write_b128 is served in 8 groups of 8 consecutive lanes, a
+// ds_read_b32 in the two halves of the wave; each further distinct address on a bank of a group costs one cycle): over the 7 writes of a tile 8 extra cycles
+// (a group that crosses from row i to i + 1 skips 4 dwords), over its 28 reads 96 extra cycles on 56 conflict-free ones; 104 per tile.  Other pitches were
+// counted the same way: 112 gives 0 + 144, 124 gives 8 + 120, 128 gives 8 + 144, and an odd pitch loses the 16-byte write.
+// The blocks of an unflagged view return at once (a block's four tiles lie in one view, so the barrier is reached by all or none of its waves): those views
+// cost one flag read per block and no pass over their pixels.  One writer per element, no arithmetic on the values, 64-bit offsets.
+constexpr int HT_PITCH = 116, HT_TILE_LDS = 16 * HT_PITCH, HT_Q = 16 * HEAD_RUN / 4, HT_ROUNDS = HT_Q / 64, HT_RUN4 = HEAD_RUN / 4;
+
+struct HeadTurn {
+    const float* src;
+    float* dst;
+    const int32_t* transposed;   // [n_views] on the device
+    int H, Wimg, ntok, to_slots;
+};
+
+__global__ void __launch_bounds__(256) head_turn_kernel(HeadTurn p) {
+    __shared__ __attribute__((aligned(16))) float lds[4 * HT_TILE_LDS];
+    const int bpv = (p.ntok + 3) / 4, v = blockIdx.x / bpv;
+    if (p.transposed[v] == 0) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, t = (blockIdx.x - v * bpv) * 4 + wave;
+    const bool live = t < p.ntok;
+    const int gh = p.H / 16, gw = p.Wimg / 16;
+    float* tile = lds + wave * HT_TILE_LDS;
+    const size_t row = (size_t)p.Wimg * HEAD_C;
+    // the token's slot in the launch's landscape order and its slot in the stored layout
+    const int ly = t / gw, lx = t - ly * gw, sx = t / gh, sy = t - sx * gh;
+    const size_t at_l = (((size_t)v * p.H + 16 * ly) * p.Wimg + 16 * lx) * HEAD_C, at_s = (((size_t)v * p.H + 16 * sy) * p.Wimg + 16 * sx) * HEAD_C;
+    const float* src = p.src + (p.to_slots ? at_s : at_l);
+    float* dst = p.dst + (p.to_slots ? at_l : at_s);
+    if (live) {
+#pragma unroll
+        for (int n = 0; n < HT_ROUNDS; ++n) {
+            const int q = 64 * n + lane, i = q / HT_RUN4, f = q - i * HT_RUN4;
+            *reinterpret_cast<f32x4*>(tile + i * HT_PITCH + 4 * f) = *reinterpret_cast<const f32x4*>(src + i * row + 4 * f);
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+#pragma unroll
+    for (int n = 0; n < HT_ROUNDS; ++n) {
+        const int q = 64 * n + lane, j = q / HT_RUN4, f = q - j * HT_RUN4;
+        f32x4 val;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = 4 * f + k, i = e / HEAD_C;
+            val[k] = tile[i * HT_PITCH + HEAD_C * j + (e - i * HEAD_C)];
+        }
+        *reinterpret_cast<f32x4*>(dst + j * row + 4 * f) = val;
+    }
+}
+
+// the flagged views of src [n_views][n4 float4] over dst; HC_PER_BLOCK float4 (64 KB) per block, the blocks of an unflagged view return at once
+constexpr int HC_PER_BLOCK = 4096;
+__global__ void __launch_bounds__(256) head_copy_flagged_kernel(const f32x4* __restrict__ src, f32x4* __restrict__ dst, const int32_t* __restrict__ transposed,
+                                                                int n4, int bpv) {
+    const int v = blockIdx.x / bpv, c0 = (blockIdx.x - v * bpv) * HC_PER_BLOCK;
+    if (transposed[v] == 0) return;
+    const size_t base = (size_t)v * n4;
+#pragma unroll 4
+    for (int u = 0; u < HC_PER_BLOCK / 256; ++u) {
+        const int c = c0 + u * 256 + threadIdx.x;
+        if (c < n4) dst[base + c] = src[base + c];
+    }
 }
 
 // forward operands from the fp32 parameters: rows in pixel-shuffle order, [W_hi | W_hi | W_lo] (model.hip w3) and the permuted bias
@@ -119,7 +209,7 @@ struct DgSeg {
 // SEG: the rows of W live in two parameters, W [O0][K] and seg.W1 [O - O0][K] with O0 % 16 == 0 (a 16-deep step never straddles the seam), and out has
 // the row stride seg.ldo.  The steps and the k-ordered chain are the same: the bits of the plain kernel on a packed copy of W over W1.  The instantiations
 // without it are the kernel as it was.
-template <bool GATHER, bool SEG = false>
+template <int GATHER, bool SEG = false>
 __global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __restrict__ W, float* __restrict__ out, int M, int O, int K, int n_tiles,
                                                     DgSeg seg = DgSeg{nullptr, 0, 0}) {
     __shared__ __attribute__((aligned(16))) float As[HM * HAP];
@@ -188,7 +278,7 @@ __global__ void __launch_bounds__(256) dgrad_kernel(DzSrc z, const float* __rest
 
 // part[split][O][K] = sum over the split's rows of dZ[r, o] a[r, k], a = (A - mu) rstd with `stats`, A itself without; pdb[split][O] = the
 // column sums of the split's dZ rows (blocks of column tile 0).  want_dw = 0: only the column sums (grid of one column tile).
-template <bool GATHER>
+template <int GATHER>
 __global__ void __launch_bounds__(256) wgrad_kernel(DzSrc z, const float* __restrict__ A, int lda, const float2* __restrict__ stats, int M, int O, int K,
                                                     int rows_per_split, int o_tiles, int n_tiles, int want_dw, float* __restrict__ part,
                                                     float* __restrict__ pdb) {
@@ -213,12 +303,41 @@ __global__ void __launch_bounds__(256) wgrad_kernel(DzSrc z, const float* __rest
     f32x4 acc[4][4];
     zero_acc(acc);
     f32x4 ra[2], rb[2];
+    // DZ_GATHER_AR: a staged row's (view, slot row, slot column) and its view's flag are carried from fetch to fetch -- the row advances by HK, so the slot is
+    // stepped, not divided out again, and the flag is read again only where the view changes.  Read in every fetch, the flag put a dependent load and a
+    // third division in front of each row's address: 1.0 ms of this kernel's 18 ms at 430080 rows with no view flagged (kernel trace).
+    int cv[2] = {0, 0}, cgy[2] = {0, 0}, cgx[2] = {0, 0}, cfl[2] = {0, 0};
+    if constexpr (GATHER == DZ_GATHER_AR) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int r = r_lo + sr[e];
+            if (r < r_hi) {
+                cv[e] = r / z.ntok;
+                const int t = r - cv[e] * z.ntok;
+                cgy[e] = t / z.gw;
+                cgx[e] = t - cgy[e] * z.gw;
+                cfl[e] = z.flags[cv[e]];
+            }
+        }
+    }
     auto fetch = [&](int r0) {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const int r = r0 + sr[e];
             const bool in = r < r_hi;
-            ra[e] = in && zok[e] ? *reinterpret_cast<const f32x4*>(z.p + dz_row<GATHER>(z, r) + zcol[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
+            size_t at = 0;
+            if constexpr (GATHER == DZ_GATHER_AR) {
+                at = (((size_t)cv[e] * z.H + 16 * cgy[e]) * z.Wimg + 16 * cgx[e]) * HEAD_C + (cfl[e] != 0 ? (size_t)z.alt : 0);
+                // the row of the next fetch
+                const int gh = z.H / 16, view = cv[e];
+                cgx[e] += HK;
+                while (cgx[e] >= z.gw) { cgx[e] -= z.gw; ++cgy[e]; }
+                while (cgy[e] >= gh) { cgy[e] -= gh; ++cv[e]; }
+                if (cv[e] != view) cfl[e] = r + HK < r_hi ? z.flags[cv[e]] : 0;
+            } else {
+                at = in ? dz_row<GATHER>(z, r) : 0;
+            }
+            ra[e] = in && zok[e] ? *reinterpret_cast<const f32x4*>(z.p + at + zcol[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
             if (in && bok[e]) {
                 v = *reinterpret_cast<const f32x4*>(A + (size_t)r * lda + n0 + sc[e]);
@@ -388,19 +507,22 @@ static int lng_blocks(int R) { const int rpb = lng_rows_per_block(R); return (R 
 static size_t wgrad_scratch(int M, int O, int K) { return up256((size_t)wgrad_splits(M) * O * K * 4) + up256((size_t)wgrad_splits(M) * O * 4); }
 static size_t lng_scratch(int M, int D) { return up256((size_t)M * 8) + up256((size_t)lng_blocks(M) * 2 * D * 4); }
 
-static int run_dgrad(bool gather, const DzSrc& z, const float* W, float* out, int M, int O, int K, hipStream_t s) {
+// gather: DZ_PLAIN, DZ_GATHER or DZ_GATHER_AR
+static int run_dgrad(int gather, const DzSrc& z, const float* W, float* out, int M, int O, int K, hipStream_t s) {
     const int n_tiles = (K + HN - 1) / HN;
     const long long blocks = (long long)((M + HM - 1) / HM) * n_tiles;
     if (blocks > 0x7fffffffLL) return fail("linear_dgrad: too many rows");
     if (!gather && train_linear_bf16()) return launch_dgrad_bf16("linear_dgrad", z.p, (int)z.ld, W, nullptr, O, out, K, M, O, K, s);
-    if (gather) hipLaunchKernelGGL((dgrad_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
-    else hipLaunchKernelGGL((dgrad_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
+    if (gather == DZ_GATHER_AR)
+        hipLaunchKernelGGL((dgrad_kernel<DZ_GATHER_AR, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
+    else if (gather) hipLaunchKernelGGL((dgrad_kernel<DZ_GATHER, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
+    else hipLaunchKernelGGL((dgrad_kernel<DZ_PLAIN, false>), dim3((unsigned)blocks), dim3(256), 0, s, z, W, out, M, O, K, n_tiles, DgSeg{nullptr, 0, 0});
     if (hipGetLastError() != hipSuccess) return fail("linear_dgrad: launch failed");
     return 0;
 }
 
 // scratch: [partials S O K | column-sum partials S O]
-static int run_wgrad(bool gather, const DzSrc& z, const float* A, int lda, const float2* stats, int M, int O, int K, const float* gamma,
+static int run_wgrad(int gather, const DzSrc& z, const float* A, int lda, const float2* stats, int M, int O, int K, const float* gamma,
                      const float* beta, float* dW, float* db, char* scratch, hipStream_t s) {
     const int S = wgrad_splits(M), rps = wgrad_rows_per_split(M), want_dw = dW ? 1 : 0;
     const int o_tiles = (O + HM - 1) / HM, n_tiles = want_dw ? (K + HN - 1) / HN : 1;
@@ -408,8 +530,10 @@ static int run_wgrad(bool gather, const DzSrc& z, const float* A, int lda, const
     float* pdb = reinterpret_cast<float*>(scratch + up256((size_t)S * O * K * 4));
     const dim3 grid((unsigned)(o_tiles * n_tiles * S));
     if (!gather && !stats && train_linear_bf16()) M3R_RUN(launch_wgrad_parts_bf16(z.p, (int)z.ld, A, lda, M, O, K, rps, S, want_dw, part, pdb, s));
-    else if (gather) hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
-    else hipLaunchKernelGGL(wgrad_kernel<false>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
+    else if (gather == DZ_GATHER_AR)
+        hipLaunchKernelGGL(wgrad_kernel<DZ_GATHER_AR>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
+    else if (gather) hipLaunchKernelGGL(wgrad_kernel<DZ_GATHER>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
+    else hipLaunchKernelGGL(wgrad_kernel<DZ_PLAIN>, grid, dim3(256), 0, s, z, A, lda, stats, M, O, K, rps, o_tiles, n_tiles, want_dw, part, pdb);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(O), dim3(256), 0, s, part, pdb, S, O, K, gamma, beta, gather ? 1 : 0, dW, db);
     if (hipGetLastError() != hipSuccess) return fail("linear_wgrad: launch failed");
     return 0;
@@ -485,7 +609,7 @@ int launch_dgrad_seg_f32(const float* dZ, int ldz, const float* W0, const float*
     if (blocks > 0x7fffffffLL) return fail("linear_dgrad (two segments): too many rows");
     if (train_linear_bf16()) return launch_dgrad_bf16("linear_dgrad (two segments)", dZ, ldz, W0, W1, O0, out, ldo, M, O, K, s);
     const DzSrc z{dZ, ldz, 0, 0, 0, 0};
-    hipLaunchKernelGGL((dgrad_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, z, W0, out, M, O, K, n_tiles, DgSeg{W1, O0, ldo});
+    hipLaunchKernelGGL((dgrad_kernel<DZ_PLAIN, true>), dim3((unsigned)blocks), dim3(256), 0, s, z, W0, out, M, O, K, n_tiles, DgSeg{W1, O0, ldo});
     if (hipGetLastError() != hipSuccess) return fail("linear_dgrad (two segments): launch failed");
     return 0;
 }
@@ -513,42 +637,127 @@ extern "C" int must3r_hip_op_head_linear(int dtype, const float* y, const float*
 }
 
 // scratch of must3r_hip_head_grad: [statistics R x 2 | permuted W | weight-gradient partials and column sums | LayerNorm column partials]
-extern "C" size_t must3r_hip_head_grad_scratch_bytes(int n_views, int H, int Wimg, int D) {
-    if (const char* e = head_shape_error(n_views, H, Wimg, D)) { fail("head_grad_scratch_bytes: %s", e); return 0; }
-    const int R = n_views * (H / 16) * (Wimg / 16), O = HEAD_C * HEAD_P2;
+static size_t head_grad_scratch(int R, int D) {
+    const int O = HEAD_C * HEAD_P2;
     return up256((size_t)R * 8) + up256((size_t)O * D * 4) + wgrad_scratch(R, O, D) + up256((size_t)lng_blocks(R) * 2 * D * 4);
 }
+extern "C" size_t must3r_hip_head_grad_scratch_bytes(int n_views, int H, int Wimg, int D) {
+    if (const char* e = head_shape_error(n_views, H, Wimg, D)) { fail("head_grad_scratch_bytes: %s", e); return 0; }
+    return head_grad_scratch(n_views * (H / 16) * (Wimg / 16), D);
+}
 
-extern "C" int must3r_hip_head_grad(const must3r_hip_head_grad_args* a, void* scratch, size_t scratch_bytes, void* stream) {
-    if (!a) return fail("head_grad: null argument");
-    if (const char* e = head_shape_error(a->n_views, a->H, a->Wimg, a->D)) return fail("head_grad: %s", e);
+// what the per-view orientation adds to a head call: one copy of the pointmaps / of the upstream gradient, for the turned tiles of the flagged views
+static size_t head_ar_scratch(int n_views, int H, int Wimg) { return up256((size_t)n_views * H * Wimg * HEAD_C * 4); }
+static const char* head_ar_error(int H, int Wimg, const int32_t* transposed) {
+    if (H > Wimg) return "a batch with portrait flags is stored landscape (H <= W)";
+    if ((size_t)transposed & 3) return "transposed must be 4-byte aligned";
+    if ((long long)H * Wimg * HEAD_C / 4 > 0x7fffffffLL) return "a view is too large";
+    return nullptr;
+}
+static int run_head_turn(const float* src, float* dst, const int32_t* transposed, int n_views, int H, int Wimg, int to_slots, hipStream_t s) {
+    const int ntok = (H / 16) * (Wimg / 16), bpv = (ntok + 3) / 4;
+    hipLaunchKernelGGL(head_turn_kernel, dim3((unsigned)(n_views * bpv)), dim3(256), 0, s, HeadTurn{src, dst, transposed, H, Wimg, ntok, to_slots});
+    if (hipGetLastError() != hipSuccess) return fail("head (portrait views): the turn launch failed");
+    return 0;
+}
+
+// transposed == NULL: must3r_hip_head_grad as it was, launch for launch.  Otherwise `turned`, head_ar_scratch bytes, takes the flagged views' gradient tiles
+// in the slot order of their tokens and the gather forms pick their source per view.
+static int head_grad(const must3r_hip_head_grad_args* a, const int32_t* transposed, float* turned, char* p, hipStream_t s, const char* who) {
     const bool want_w = a->dW || a->db, want_x = a->dx || a->dgamma || a->dbeta;
-    if (!a->G) return fail("head_grad: null argument (G)");
-    if (a->dW && (!a->x || !a->gamma || !a->beta)) return fail("head_grad: null argument (dW needs x, gamma and beta)");
-    if (want_x && (!a->x || !a->gamma || !a->W)) return fail("head_grad: null argument (dx, dgamma and dbeta need x, gamma and W)");
-    if (misaligned(a->x) || misaligned(a->W) || misaligned(a->G) || misaligned(a->dx) || misaligned(a->dW))
-        return fail("head_grad: tensors must be 16-byte aligned");
-    if (!scratch || misaligned(scratch) || scratch_bytes < must3r_hip_head_grad_scratch_bytes(a->n_views, a->H, a->Wimg, a->D))
-        return fail("head_grad: scratch too small");
     const int D = a->D, ntok = (a->H / 16) * (a->Wimg / 16), R = a->n_views * ntok, O = HEAD_C * HEAD_P2;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    char* p = reinterpret_cast<char*>(scratch);
     float2* stats = reinterpret_cast<float2*>(p); p += up256((size_t)R * 8);
     float* Wp = reinterpret_cast<float*>(p); p += up256((size_t)O * D * 4);
     char* wscr = p; p += wgrad_scratch(R, O, D);
     float* lpart = reinterpret_cast<float*>(p);
-    const DzSrc z{a->G, 0, ntok, a->Wimg / 16, a->H, a->Wimg};
+    DzSrc z{a->G, 0, ntok, a->Wimg / 16, a->H, a->Wimg};
+    const int gather = transposed ? DZ_GATHER_AR : DZ_GATHER;
+    if (transposed && (want_w || want_x)) {
+        z.flags = transposed;
+        z.alt = (long long)((reinterpret_cast<intptr_t>(turned) - reinterpret_cast<intptr_t>(a->G)) / 4);
+        M3R_RUN(run_head_turn(a->G, turned, transposed, a->n_views, a->H, a->Wimg, 1, s));
+    }
     if (a->dW || want_x) M3R_RUN(run_stats(a->x, R, D, a->eps, stats, s));
-    if (want_w) M3R_RUN(run_wgrad(true, z, a->x, D, stats, R, O, D, a->gamma, a->beta, a->dW, a->db, wscr, s));
+    if (want_w) M3R_RUN(run_wgrad(gather, z, a->x, D, stats, R, O, D, a->gamma, a->beta, a->dW, a->db, wscr, s));
     if (want_x) {
         // dY goes where dx will be; without dx it needs a home of its own, which the caller did not give: the partials' space is free again
         // only after the reduce above has read it (stream order), and R D floats may not fit there -- so dgamma / dbeta alone still need dx
-        if (!a->dx) return fail("head_grad: dgamma / dbeta without dx is not provided for (dY lives in the dx buffer)");
+        if (!a->dx) return fail("%s: dgamma / dbeta without dx is not provided for (dY lives in the dx buffer)", who);
         hipLaunchKernelGGL(perm_w_kernel, dim3(O), dim3(256), 0, s, a->W, D, Wp);
-        M3R_RUN(run_dgrad(true, z, Wp, a->dx, R, O, D, s));
+        M3R_RUN(run_dgrad(gather, z, Wp, a->dx, R, O, D, s));
         M3R_RUN(run_ln_grad(a->x, a->gamma, stats, a->dx, nullptr, a->dx, a->dgamma, a->dbeta, R, D, lpart, s));
     }
     return 0;
+}
+// 0, or the descriptor is refused with the reason as the last error; nothing is read through a device pointer
+static int head_grad_check(const must3r_hip_head_grad_args* a, const char* who) {
+    if (const char* e = head_shape_error(a->n_views, a->H, a->Wimg, a->D)) return fail("%s: %s", who, e);
+    const bool want_x = a->dx || a->dgamma || a->dbeta;
+    if (!a->G) return fail("%s: null argument (G)", who);
+    if (a->dW && (!a->x || !a->gamma || !a->beta)) return fail("%s: null argument (dW needs x, gamma and beta)", who);
+    if (want_x && (!a->x || !a->gamma || !a->W)) return fail("%s: null argument (dx, dgamma and dbeta need x, gamma and W)", who);
+    if (misaligned(a->x) || misaligned(a->W) || misaligned(a->G) || misaligned(a->dx) || misaligned(a->dW))
+        return fail("%s: tensors must be 16-byte aligned", who);
+    return 0;
+}
+
+extern "C" int must3r_hip_head_grad(const must3r_hip_head_grad_args* a, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!a) return fail("head_grad: null argument");
+    M3R_RUN(head_grad_check(a, "head_grad"));
+    if (!scratch || misaligned(scratch) || scratch_bytes < must3r_hip_head_grad_scratch_bytes(a->n_views, a->H, a->Wimg, a->D))
+        return fail("head_grad: scratch too small");
+    return head_grad(a, nullptr, nullptr, reinterpret_cast<char*>(scratch), reinterpret_cast<hipStream_t>(stream), "head_grad");
+}
+
+// The head over a batch stored landscape whose views carry portrait flags (ABI 21, additive; the kernels' comment is above head_turn_kernel).
+// scratch: [the scratch of the plain entry point | one copy of the pointmaps / of the upstream gradient]; the second part is asked for with or without flags.
+extern "C" size_t must3r_hip_head_forward_many_ar_scratch_bytes(int n_views, int H, int Wimg, int D) {
+    if (const char* e = head_shape_error(n_views, H, Wimg, D)) { fail("head_forward_many_ar_scratch_bytes: %s", e); return 0; }
+    return head_forward_scratch(n_views * (H / 16) * (Wimg / 16), D) + head_ar_scratch(n_views, H, Wimg);
+}
+
+extern "C" int must3r_hip_head_forward_many_ar(const must3r_hip_head_forward_ar_args* a, void* scratch, size_t scratch_bytes) {
+    const char* who = "head_forward_many_ar";
+    if (!a) return fail("%s: null argument", who);
+    if (!a->x) return fail("%s: null argument", who);
+    if (const char* e = head_shape_error(a->n_views, a->H, a->Wimg, a->D)) return fail("%s: %s", who, e);
+    if (a->transposed) {
+        if (const char* e = head_ar_error(a->H, a->Wimg, a->transposed)) return fail("%s: %s", who, e);
+    }
+    const size_t plain = head_forward_scratch(a->n_views * (a->H / 16) * (a->Wimg / 16), a->D);
+    if (!scratch || misaligned(scratch) || scratch_bytes < plain + head_ar_scratch(a->n_views, a->H, a->Wimg)) return fail("%s: scratch too small", who);
+    // the head writes every view in place with the landscape geometry: an unflagged view is finished by that
+    M3R_RUN(head_forward(a->dtype, a->x, nullptr, a->gamma, a->beta, a->W, a->b, a->n_views, a->H, a->Wimg, a->D, a->eps, a->pointmaps, scratch, plain, a->stream, who));
+    if (!a->transposed) return 0;
+    // a flagged view's tiles change places among themselves, so they are turned into the scratch and copied back: two passes over those views alone
+    hipStream_t s = reinterpret_cast<hipStream_t>(a->stream);
+    float* turned = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + plain);
+    M3R_RUN(run_head_turn(a->pointmaps, turned, a->transposed, a->n_views, a->H, a->Wimg, 0, s));
+    const int n4 = a->H * a->Wimg * HEAD_C / 4, bpv = (n4 + HC_PER_BLOCK - 1) / HC_PER_BLOCK;
+    if ((long long)a->n_views * bpv > 0x7fffffffLL) return fail("%s: too many pixels", who);
+    hipLaunchKernelGGL(head_copy_flagged_kernel, dim3((unsigned)(a->n_views * bpv)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(turned),
+                       reinterpret_cast<f32x4*>(a->pointmaps), a->transposed, n4, bpv);
+    if (hipGetLastError() != hipSuccess) return fail("%s: the copy launch failed", who);
+    return 0;
+}
+
+extern "C" size_t must3r_hip_head_grad_many_ar_scratch_bytes(int n_views, int H, int Wimg, int D) {
+    if (const char* e = head_shape_error(n_views, H, Wimg, D)) { fail("head_grad_many_ar_scratch_bytes: %s", e); return 0; }
+    return head_grad_scratch(n_views * (H / 16) * (Wimg / 16), D) + head_ar_scratch(n_views, H, Wimg);
+}
+
+extern "C" int must3r_hip_head_grad_many_ar(const must3r_hip_head_grad_ar_args* a, void* scratch, size_t scratch_bytes) {
+    const char* who = "head_grad_many_ar";
+    if (!a) return fail("%s: null argument", who);
+    const must3r_hip_head_grad_args* g = &a->g;
+    M3R_RUN(head_grad_check(g, who));
+    if (a->transposed) {
+        if (const char* e = head_ar_error(g->H, g->Wimg, a->transposed)) return fail("%s: %s", who, e);
+    }
+    const size_t plain = head_grad_scratch(g->n_views * (g->H / 16) * (g->Wimg / 16), g->D);
+    if (!scratch || misaligned(scratch) || scratch_bytes < plain + head_ar_scratch(g->n_views, g->H, g->Wimg)) return fail("%s: scratch too small", who);
+    char* p = reinterpret_cast<char*>(scratch);
+    return head_grad(g, a->transposed, reinterpret_cast<float*>(p + plain), p, reinterpret_cast<hipStream_t>(a->stream), who);
 }
 
 extern "C" int must3r_hip_op_linear_dgrad_f32(const float* dZ, int ldz, const float* W, float* out, int M, int O, int K, void* stream) {

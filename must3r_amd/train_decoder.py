@@ -21,7 +21,9 @@ Everything runs in fp32 -- or, inside ``with train_block.linear_precision("bf16"
 (bf16 operands, fp32 accumulation; the norms, the attention cores, the feedback add, the head and all storage stay fp32; ``backward()`` may be called after
 the block has ended: each Function runs its backward in the mode of its forward); ``train_block.attention_precision("bf16")`` moves the products of the
 attention cores there as well, and ``train_block.amp("bf16")`` is both.  Only the gradients ``needs_input_grad`` asks for are computed (frozen parts cost no launches); first order only; CPU tensors
-raise.  List inputs (``forward_list``) and mixed aspect ratios are not built; memory dropout is ``train_dropout.CausalMUSt3R``, which hands the key masks of a
+raise.  ``landscape_only=True`` (the recipe's constructor value; False by default, and never taken from the native decoder) takes a batch stored landscape whose
+portrait views carry true_shape rows of (W, H): ``dec(x, pos, true_shape, mem, img_shape=(H, W))`` (``train_head.PredictionHead``).  List inputs
+(``forward_list``) and aspect ratios beyond that pair are not built; memory dropout is ``train_dropout.CausalMUSt3R``, which hands the key masks of a
 call to this forward.  The memory is concatenated per call, not appended in place.
 """
 import ctypes as C
@@ -245,8 +247,8 @@ class MUSt3R(PredictionHead):
     _causal = False
 
     def __init__(self, enc_embed_dim=1024, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0, feedback_type=None, memory_mode="norm_y",
-                 rope=(100.0, 1.0), eps=1e-6, npos=ROPE_NPOS, head_dtype=_lib.F16):
-        super().__init__(embed_dim, eps, head_dtype)
+                 rope=(100.0, 1.0), eps=1e-6, npos=ROPE_NPOS, head_dtype=_lib.F16, landscape_only=False):
+        super().__init__(embed_dim, eps, head_dtype, landscape_only)
         if memory_mode not in MEMORY_MODES:
             raise ValueError(f"MUSt3R: memory_mode {memory_mode!r}, expected one of {MEMORY_MODES}")
         feedback_type = feedback_type or None
@@ -278,7 +280,8 @@ class MUSt3R(PredictionHead):
 
     @classmethod
     def from_decoder(cls, decoder, memory_mode=None, head_dtype=_lib.F16, **kw):
-        """fp32 copies of a loaded ``must3r_amd.model.MUSt3R`` (or anything with its state-dict keys and attributes); the source is left alone."""
+        """fp32 copies of a loaded ``must3r_amd.model.MUSt3R`` (or anything with its state-dict keys and attributes); the source is left alone.
+        ``landscape_only`` is not among the attributes read: it is the constructor's keyword (``from_decoder(dec, landscape_only=True)``), False by default."""
         sd = decoder.state_dict()
         w = sd["feat_embed_enc_to_dec.weight"]
         D, Denc = int(w.shape[0]), int(w.shape[1])
@@ -336,14 +339,17 @@ class MUSt3R(PredictionHead):
             out.append(torch.cat([TB.linear(y, c.projk.weight, c.projk.bias), TB.linear(y, c.projv.weight, c.projv.bias)], dim=-1))
         return out
 
-    def forward(self, x, pos, true_shape, current_mem=None, render=False, return_tokens=False, key_mask=None, view_mask=None):
+    def forward(self, x, pos, true_shape, current_mem=None, render=False, return_tokens=False, key_mask=None, view_mask=None, img_shape=None):
         """x ``[B, nimgs, N, Denc]``, pos int64 ``[B, nimgs, N, 2]`` (or flattened ``[B nimgs N, 2]``: ``train_block.check_positions`` then recognises
         the tensor from call to call and does not read it on the host again), true_shape ``[B, nimgs, 2]`` (all views of a call share (H, W)) ->
         ``(mem, pointmaps [B, nimgs, H, W, 7])``; ``mem`` is the reference's 5-tuple ``([L tensors [B, Nm, W]], labels int64 [B, Nm], mem_nimgs,
         protected_imgs, protected_tokens)`` whose tensors stay in the autograd graph (a detached memory, or one made under ``torch.no_grad()``, is fine).
         ``render``: the memory is read, not updated, and comes back as it was given.  ``return_tokens``: also the last layer's tokens ``[B, nimgs, N, D]``
         (before ``norm_dec``).  ``key_mask`` / ``view_mask``: packed key masks over the key rows of the call's cross attention and each view's row of them
-        (``train_attention.pack_key_mask``; ``train_dropout``), the same for every layer."""
+        (``train_attention.pack_key_mask``; ``train_dropout``), the same for every layer.  A decoder built with ``landscape_only=True`` takes a batch
+        stored landscape whose portrait views have true_shape rows of (W, H), with the tokens and positions of their own grid (``ManyAR_PatchEmbed``); the
+        blocks see the orientation through ``pos`` alone, the head turns those views back into the stored layout.  ``img_shape``: the stored (H, W), with
+        which the head reads nothing back to the host (``PredictionHead.forward``)."""
         if isinstance(x, (list, tuple)) or isinstance(pos, (list, tuple)):
             raise TypeError("train_decoder.MUSt3R.forward takes tensors [B, nimgs, N, Denc]: list inputs (forward_list, mixed aspect ratios) are not built")
         _dev(x, "x")
@@ -404,7 +410,7 @@ class MUSt3R(PredictionHead):
             n_imgs = int(n_imgs) + V
             out = (mem, labels, n_imgs, *self._memory_tail(n_imgs, int(labels.shape[1]), prot_imgs, prot_tokens, V, N))
         tokens = xr.view(B, V, N, D)
-        pts = PredictionHead.forward(self, tokens, true_shape)
+        pts = PredictionHead.forward(self, tokens, true_shape, img_shape)
         return (out, pts, tokens) if return_tokens else (out, pts)
 
 

@@ -175,15 +175,15 @@ class CausalMUSt3R(TD.CausalMUSt3R):
         view_mask = [index.get(0 if render else j, -1) for _ in range(B) for j in range(V)]
         return pack_key_mask(torch.stack(rows)), view_mask
 
-    def forward(self, x, pos, true_shape, current_mem=None, render=False, return_tokens=False, selection=None):
+    def forward(self, x, pos, true_shape, current_mem=None, render=False, return_tokens=False, selection=None, img_shape=None):
         """``train_decoder.MUSt3R.forward`` with dropout.  ``selection``: the ``(sel, not_sel)`` lists the reference's selector returned for this call (index
         tensors on any device) instead of a draw of this module's -- a recorded draw can be replayed.  In the permanent mode the memory and the labels of
-        the returned tuple hold the kept rows only."""
+        the returned tuple hold the kept rows only.  ``img_shape``: ``train_decoder.MUSt3R.forward``'s."""
         p = self.mem_dropout.p
         if not p > 0.0:
-            return super().forward(x, pos, true_shape, current_mem, render, return_tokens)
+            return super().forward(x, pos, true_shape, current_mem, render, return_tokens, img_shape=img_shape)
         if render and self.dropout_mode != "temporary":
-            return super().forward(x, pos, true_shape, current_mem, render, return_tokens)
+            return super().forward(x, pos, true_shape, current_mem, render, return_tokens, img_shape=img_shape)
         TD._dev(x, "x")
         if x.ndim != 4:
             raise ValueError(f"MUSt3R: x of shape {tuple(x.shape)}, expected [B, nimgs, N, {self.enc_embed_dim}]")
@@ -203,7 +203,7 @@ class CausalMUSt3R(TD.CausalMUSt3R):
             keeps, compact = self.draw(Nm, V, N, prot_tokens, x.device, render)
         masked = render or Nm > 0 or V > 1          # a lone first view attends its own tokens, unmasked (decoder.py:498)
         key_mask, view_mask = self._cross_mask(keeps, B, V, Nk, render, x.device) if masked else (None, None)
-        out = super().forward(x, pos, true_shape, current_mem, render, return_tokens, key_mask, view_mask)
+        out = super().forward(x, pos, true_shape, current_mem, render, return_tokens, key_mask, view_mask, img_shape)
         if compact is None or render:
             return out
         mem, labels, *tail = out[0]

@@ -18,7 +18,10 @@ autocast disabled even under ``--amp bf16`` (encoder.py:46): ``precision="fp32"`
 ``train_block.amp("bf16")`` around encoder and decoder does what the reference's autocast does; ``"bf16"`` enters ``amp("bf16")``; ``None`` leaves the caller's
 modes alone.  The forward reads nothing back to the host.  First order only; CPU tensors raise.
 
-Not built: the image gradient (``img.requires_grad`` raises); ``forward_list`` and mixed orientations through the decoder and the head; DDP, activation
+A decoder built with ``landscape_only=True`` (``train_decoder``) takes the mixed batch on: ``inference`` hands it the stored image size, so that the whole step from
+the images to the pointmaps reads nothing back.
+
+Not built: the image gradient (``img.requires_grad`` raises); ``forward_list``; DDP, activation
 checkpointing and row chunking (a forward keeps two block inputs per layer: 3.0 GB at 24 layers, 20 views of 768 tokens); ``max_bs`` slicing under autograd.
 """
 import contextlib
@@ -35,6 +38,7 @@ from .inference import _cumulative
 from .model.blocks import parse_pos_embed
 from .train_attention import _table, self_views
 from .train_block import ROPE_NPOS
+from .train_head import PredictionHead
 
 PATCH = 16
 PATCH_EMBEDS = ("PatchEmbedDust3R", "ManyAR_PatchEmbed")
@@ -231,7 +235,8 @@ def _grad_if(keep):
 def inference(encoder, decoder, imgs, true_shape, mem_batches, train_decoder_skip=0, to_render=None, encoder_requires_grad=False, max_bs=None,
               verbose=False):
     """The reference's ``inference`` (engine/inference.py:595-688) under autograd: ``imgs`` ``[B, n, 3, H, W]``, ``true_shape`` ``[B, n, 2]`` (one aspect
-    ratio) -> ``(pointmaps_0 [B, sum(mem_batches) - skipped, H, W, C], pointmaps [B, n_rendered, H, W, C])``.  The encoder runs under ``no_grad`` unless
+    ratio; with a ``ManyAR_PatchEmbed`` encoder and a ``landscape_only=True`` decoder, rows of (W, H) for the portrait views of the batch stored landscape)
+    -> ``(pointmaps_0 [B, sum(mem_batches) - skipped, H, W, C], pointmaps [B, n_rendered, H, W, C])``.  The encoder runs under ``no_grad`` unless
     ``encoder_requires_grad``, and so do the first ``train_decoder_skip`` memory updates, which do not contribute to ``pointmaps_0`` either; everything else
     stays in the graph.  Under ``torch.no_grad()`` this is ``must3r_amd.inference.inference``.  ``max_bs`` slicing is not built under autograd."""
     B, n = int(imgs.shape[0]), int(imgs.shape[1])
@@ -240,11 +245,13 @@ def inference(encoder, decoder, imgs, true_shape, mem_batches, train_decoder_ski
     with _grad_if(encoder_requires_grad):
         x, pos = encoder(imgs.reshape(B * n, *imgs.shape[2:]), true_shape.view(B * n, 2))
         x, pos = x.view(B, n, *x.shape[1:]), pos.view(B, n, *pos.shape[1:])
+    # a landscape_only decoder learns the stored size from the image tensor: its head then reads nothing back from true_shape
+    kw = dict(img_shape=(int(imgs.shape[-2]), int(imgs.shape[-1]))) if isinstance(decoder, PredictionHead) and decoder.landscape_only else {}
     bounds = _cumulative(mem_batches)
     mem, first_pass, out_shape = None, [], None
     for b, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:])):
         with _grad_if(b >= train_decoder_skip):
-            mem, pm = decoder(x[:, lo:hi].contiguous(), pos[:, lo:hi].contiguous(), true_shape[:, lo:hi].contiguous(), mem, render=False)
+            mem, pm = decoder(x[:, lo:hi].contiguous(), pos[:, lo:hi].contiguous(), true_shape[:, lo:hi].contiguous(), mem, render=False, **kw)
         out_shape = out_shape or pm.shape
         if b >= train_decoder_skip:
             first_pass.append(pm)
@@ -260,5 +267,5 @@ def inference(encoder, decoder, imgs, true_shape, mem_batches, train_decoder_ski
         print(f"Nmem={mem[0][-1].shape[1]}")
     if n == 0:
         return pointmaps_0, torch.empty((B, 0, *pointmaps_0.shape[2:]), dtype=x.dtype, device=x.device)
-    _, pointmaps = decoder(x, pos, true_shape, mem, render=True)
+    _, pointmaps = decoder(x, pos, true_shape, mem, render=True, **kw)
     return pointmaps_0, pointmaps
