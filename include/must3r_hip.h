@@ -1116,6 +1116,46 @@ typedef struct must3r_hip_patch_rows_args {
 } must3r_hip_patch_rows_args;
 int must3r_hip_patch_rows(const must3r_hip_patch_rows_args* a);
 
+/* ABI 21, additive.  The ground truth of a training batch from its depth maps, on the device (csrc/train_data.hip): what the reference's datasets compute per
+ * view in numpy (must3r_base_dataset.py:185-198) and its criterion then stacks and uploads, 14 bytes per pixel where the depth map is 4 or 2.  V views stored
+ * landscape [V][Hs][Ws]; all pointers are DEVICE pointers.
+ *   depth        fp32, or (depth_u16 = 1) raw uint16 with a per-view pair depth_scale[v] = (div, mul): z = (float(raw) / div) * mul in fp32 -- ScanNet++ is
+ *                (1000, 1), a Co3d-style file (65535, maximum_depth).  The uint16 form has no sky (no negative depth).
+ *   K            [V][3][3], the intrinsics of the true (untransposed) image: fu = K[0][0], cu = K[0][2], fv = K[1][1], cv = K[1][2]; the rest is not read.
+ *   c2w          [V][4][4], camera to world: R its upper 3 x 3, t its last column.  It may be NaN (a view without a pose); the kernel does not test for that.
+ *   transposed   int32 [V] in the meaning of must3r_hip_patch_rows_args.transposed, or NULL (no view is): a non-zero entry marks a portrait image that was
+ *                stored with its axes swapped (dust3r's transpose_to_landscape).  Its stored pixel (r, c) is true pixel (row = c, col = r): u = r, v = c.
+ *                An unflagged view has u = c, v = r.  No data is moved.
+ * Per stored pixel, every operation rounded once (nothing is contracted into an FMA), so that a CPU expression reproduces the bits:
+ *   x = fp32((double(u) - double(cu)) * double(z) / double(fu))     y = fp32((double(v) - double(cv)) * double(z) / double(fv))
+ *   X[i] = ((R[i][0] * x + R[i][1] * y) + R[i][2] * z) + t[i]       in fp32, i = 0..2
+ *   pts3d = X (written for every pixel, as the reference does)     valid = z > 0 && isfinite(X[0..2])     sky = z < 0     n_valid[v] = #{z > 0}
+ * (n_valid is what the datasets' is_valid_check tests; a NaN pose makes a view all invalid and leaves its n_valid alone.)
+ * Every output is optional: a NULL one costs nothing and is not written; at least one is needed.  n_valid is a fixed-order reduce without atomics (lanes, waves,
+ * then the view's blocks in order, in a second small launch) through `scratch`: at least 4 * V * MUST3R_GT_VIEW_BLOCKS bytes, read and written only with n_valid.
+ * The block count of a view depends on Hs and Ws alone: a view's outputs are the same bits alone and in a batch.  The stream travels in the descriptor: all
+ * work goes to it, nothing waits on the host.
+ * Refused with an error before anything is read or launched: a NULL descriptor, depth, K or c2w; depth_u16 not 0 / 1, or 1 without depth_scale; no output;
+ * V outside 1 .. 65535; Hs or Ws not positive, Ws no multiple of 4, more than 2^31 - 1 pixels a view; depth not 16-byte (uint16: 8-byte) aligned, pts3d not
+ * 16-byte aligned, any other pointer not 4-byte aligned; n_valid without enough scratch. */
+#define MUST3R_GT_VIEW_BLOCKS 32
+typedef struct must3r_hip_gt_args {
+    const void*    depth;         /* [V, Hs, Ws] fp32, or uint16 with depth_u16 */
+    const float*   depth_scale;   /* [V, 2] (div, mul): the uint16 form only */
+    const float*   K;             /* [V, 3, 3] */
+    const float*   c2w;           /* [V, 4, 4] */
+    const int32_t* transposed;    /* [V], optional */
+    float*         pts3d;         /* [V, Hs, Ws, 3], optional */
+    uint8_t*       valid;         /* [V, Hs, Ws], optional */
+    uint8_t*       sky;           /* [V, Hs, Ws], optional */
+    int32_t*       n_valid;       /* [V], optional */
+    void*          scratch;       /* with n_valid */
+    size_t         scratch_bytes;
+    int32_t V, Hs, Ws, depth_u16;
+    void* stream;                 /* hipStream_t */
+} must3r_hip_gt_args;
+int must3r_hip_gt_from_depth(const must3r_hip_gt_args* a);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

@@ -249,6 +249,18 @@ class PatchRowsArgs(C.Structure):
                 ("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32), ("stream", C.c_void_p)]
 
 
+GT_VIEW_BLOCKS = 32   # MUST3R_GT_VIEW_BLOCKS: the scratch behind n_valid holds 4 * V * GT_VIEW_BLOCKS bytes
+
+
+class GtArgs(C.Structure):
+    """must3r_hip_gt_args: depth (fp32, or uint16 with per-view (div, mul)), intrinsics, poses and DEVICE orientation flags of a batch stored landscape, the
+    (optional) ground-truth outputs, the scratch behind ``n_valid`` and the stream (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("depth", C.c_void_p), ("depth_scale", C.c_void_p), ("K", C.c_void_p), ("c2w", C.c_void_p), ("transposed", C.c_void_p),
+                ("pts3d", C.c_void_p), ("valid", C.c_void_p), ("sky", C.c_void_p), ("n_valid", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("V", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("depth_u16", C.c_int32), ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -369,6 +381,7 @@ PROTOTYPES = {
     "must3r_hip_train_linear_mode": (i32, [i32]),
     "must3r_hip_train_attention_mode": (i32, [i32]),
     "must3r_hip_patch_rows": (i32, [P(PatchRowsArgs)]),
+    "must3r_hip_gt_from_depth": (i32, [P(GtArgs)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -361,7 +361,7 @@ def inference_encoder(encoder, imgs, true_shape_view, max_bs=None, requires_grad
     """engine/inference.py:570-592.  ``imgs`` [B, n, 3, H, W], ``true_shape_view`` [B*n, 2] -> ``x`` [B, n, N, C],
     ``pos`` [B, n, N, 2]; in slices of ``max_bs`` images when asked."""
     if requires_grad:
-        raise NotImplementedError("the native encoder is inference-only (engine/train.py is out of scope)")
+        raise NotImplementedError("the native encoder is inference-only (training: must3r_amd.train on must3r_amd.train_encoder)")
     with torch.no_grad():
         B, n = imgs.shape[:2]
         flat = imgs.reshape(B * n, *imgs.shape[2:])
