@@ -1156,6 +1156,84 @@ typedef struct must3r_hip_gt_args {
 } must3r_hip_gt_args;
 int must3r_hip_gt_from_depth(const must3r_hip_gt_args* a);
 
+/* ABI 21, additive.  Training augmentation on the device (csrc/train_augment.hip, must3r_amd/train_augment.py): what the reference's datasets do to a raw frame
+ * on the host -- dust3r's _crop_resize_if_necessary (PIL crop and resize, cv2 nearest resize of the depth map), torchvision's ColorJitter + ImgNorm and
+ * transpose_to_landscape.  The crop, the Pillow resize and the final window of the IMAGE are must3r_hip_resample in its two PIL modes; the two entry points
+ * below are what follows it.  Each is one launch per pass for a batch of V views and reads a per-view table, a HOST array that the call checks, turns into its
+ * device form and uploads through pinned slots of the calling thread (a ring of 4, as the resampler's) into `scratch`.  All device work goes to the descriptor's
+ * `stream`; nothing is read back and nothing waits on the host.  The batch is stored as [V][Hs][Ws]: a view of true size (h, w) is stored as it is, or, flagged
+ * portrait, with its axes swapped (stored (r, c) = true (row c, col r): dust3r's transpose_to_landscape, the convention of must3r_hip_gt_args.transposed).
+ * Every view's stored shape must be (Hs, Ws).  A view's output bits do not depend on the batch around it, and two runs give the same bits.
+ *
+ * Colour.  src holds the resampler's output, fp32 planes [3][h][w] per view at src_offset: ImgNorm values, each one of the 256 entries of its table.  A value v
+ * is the byte u = int(127.5f * v + 127.5f + 0.5f), each operation rounded to fp32 (exact for all 256 entries).  The view's flagged operations then run in the
+ * view's order on (r, g, b) bytes, each producing bytes again, and the result is written as (u / 255 - 0.5) / 0.5 in fp32, the table's own expression: a view
+ * with no flag set is a copy.  The arithmetic is Pillow's, through which torchvision's PIL backend works, operation for operation:
+ *   blend(a, b, f)   Image.blend: t = float(a) + f * float(b - a), one fp32 multiply then one fp32 add (no FMA); 0 if t <= 0, 255 if t >= 255, else trunc(t)
+ *   BRIGHTNESS       blend(0, x, f) per channel                                      ImageEnhance.Brightness
+ *   SATURATION       blend(L, x, f), L = (19595 r + 38470 g + 7471 b + 0x8000) >> 16     ImageEnhance.Color
+ *   CONTRAST         blend(m, x, f), m = int(sum(L) / count + 0.5) in double, over the whole view as it stands when contrast is applied (after the operations
+ *                    in front of it in the view's order): a first pass sums L in integers (lanes, waves, tiles; no atomics), the second applies
+ *   HUE              RGB -> HSV, H = (H + shift) mod 256, HSV -> RGB; shift = trunc(double(f) * 255) mod 256 (non-negative), f in [-0.5, 0.5].
+ *                    RGB -> HSV: V = max; max == min: H = S = 0; else cr = float(max - min), S = int(double(cr / float(max)) * 255), rc, gc, bc =
+ *                    float(max - c) / cr in fp32, h = bc - gc (fp32) if r == max, else float(2.0 + double(rc) - double(bc)) if g == max, else
+ *                    float(4.0 + double(gc) - double(rc)); h = float(fmod(double(h) / 6.0 + 1.0, 1.0)); H = int(double(h) * 255); H, S clipped to [0, 255].
+ *                    HSV -> RGB in double: S == 0: r = g = b = V; else hh = H * 6.0 / 255.0, i = floor(hh), f = hh - i, fs = S / 255.0,
+ *                    p = round(V (1 - fs)), q = round(V (1 - fs f)), t = round(V (1 - fs (1 - f))), round half away from zero, clipped to [0, 255];
+ *                    (r, g, b) by i mod 6: (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q).
+ * Depth.  A view's raw depth map (its own DEVICE pointer, size and row stride; fp32, or uint16 with depth_u16) goes through the image's geometry by nearest
+ * neighbour: with the first crop (crop_x, crop_y, crop_w, crop_h), the size it was rescaled to (resize_w, resize_h) and the window's corner (win_x, win_y) inside
+ * that, pixel (x, y) of the out_w x out_h window reads depth[crop_y + sy][crop_x + sx],
+ *   sx = min(floor((x + win_x) * (double(crop_w) / resize_w)), crop_w - 1)     sy = min(floor((y + win_y) * (double(crop_h) / resize_h)), crop_h - 1)     in double.
+ * Values are moved, never computed with: a negative (sky) value, 0 and NaN pass through untouched, and the element type is kept.
+ * Refused with an error before anything is uploaded or launched: a NULL descriptor, src, views, out, scratch or (depth) a view's src; V outside 1 .. 65535; Hs or
+ * Ws not positive, more than 2^31 - 1 pixels a view; pointers not aligned to their element, scratch not 256-byte aligned or smaller than the query's answer; a
+ * flag (apply, portrait, depth_u16) that is not 0 or 1; an order that is no permutation of 0 .. 3; a factor that is not finite, an applied hue factor outside
+ * [-0.5, 0.5]; a view whose stored shape is not (Hs, Ws); planes outside src_elems; a crop outside its source or a window outside its resize. */
+enum { MUST3R_AUG_BRIGHTNESS = 0, MUST3R_AUG_CONTRAST = 1, MUST3R_AUG_SATURATION = 2, MUST3R_AUG_HUE = 3 };
+#define MUST3R_AUG_TILE 64
+typedef struct must3r_hip_augment_color_view {
+    int64_t src_offset;      /* elements into src: this view's planes [3][h][w] */
+    int32_t h, w;            /* the view's true size */
+    int32_t portrait;        /* 1: written with its axes swapped */
+    int32_t order[4];        /* the four MUST3R_AUG_* operations in the order they are applied */
+    int32_t apply[4];        /* by operation: 0 / 1 */
+    float   factor[4];       /* by operation */
+    int32_t reserved;
+} must3r_hip_augment_color_view;
+typedef struct must3r_hip_augment_color_args {
+    const float* src;        /* DEVICE: the resampler's output */
+    int64_t      src_elems;  /* its length */
+    const must3r_hip_augment_color_view* views;   /* HOST [V] */
+    float*       out;        /* DEVICE [V, 3, Hs, Ws] */
+    void*        scratch;
+    size_t       scratch_bytes;
+    int32_t V, Hs, Ws, reserved;
+    void* stream;            /* hipStream_t */
+} must3r_hip_augment_color_args;
+size_t must3r_hip_augment_color_scratch_bytes(int V, int Hs, int Ws);
+int must3r_hip_augment_color(const must3r_hip_augment_color_args* a);
+
+typedef struct must3r_hip_augment_depth_view {
+    const void* src;         /* DEVICE: pixel (0, 0) of the raw depth map */
+    int64_t row_stride;      /* elements between its rows */
+    int32_t H, W;            /* its size */
+    int32_t crop_x, crop_y, crop_w, crop_h;
+    int32_t resize_w, resize_h;
+    int32_t win_x, win_y, out_w, out_h;
+    int32_t portrait, reserved;
+} must3r_hip_augment_depth_view;
+typedef struct must3r_hip_augment_depth_args {
+    const must3r_hip_augment_depth_view* views;   /* HOST [V] */
+    void*  out;              /* DEVICE [V, Hs, Ws], fp32 or uint16 */
+    void*  scratch;
+    size_t scratch_bytes;
+    int32_t V, Hs, Ws, depth_u16;
+    void* stream;            /* hipStream_t */
+} must3r_hip_augment_depth_args;
+size_t must3r_hip_augment_depth_scratch_bytes(int V);
+int must3r_hip_augment_depth(const must3r_hip_augment_depth_args* a);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

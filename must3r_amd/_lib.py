@@ -261,6 +261,41 @@ class GtArgs(C.Structure):
                 ("V", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("depth_u16", C.c_int32), ("stream", C.c_void_p)]
 
 
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE = range(4)   # MUST3R_AUG_*: the operations of the colour jitter
+AUG_TILE = 64   # MUST3R_AUG_TILE
+
+
+class AugmentColorView(C.Structure):
+    """must3r_hip_augment_color_view: one view of the colour jitter's HOST table -- where its planes lie in the resampler's output, its true size, the
+    portrait flag, the order of the four operations, and a flag and a factor per operation (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("src_offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("portrait", C.c_int32), ("order", C.c_int32 * 4),
+                ("apply", C.c_int32 * 4), ("factor", C.c_float * 4), ("reserved", C.c_int32)]
+
+
+class AugmentColorArgs(C.Structure):
+    """must3r_hip_augment_color_args: the resampler's output, the HOST view table, the ImgNorm batch stored landscape, the scratch and the stream
+    (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("src", C.c_void_p), ("src_elems", C.c_int64), ("views", C.POINTER(AugmentColorView)), ("out", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("V", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("reserved", C.c_int32), ("stream", C.c_void_p)]
+
+
+class AugmentDepthView(C.Structure):
+    """must3r_hip_augment_depth_view: one view of the depth gather's HOST table -- its raw depth map on the DEVICE and the geometry the image went through
+    (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("src", C.c_void_p), ("row_stride", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
+                ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_w", C.c_int32), ("crop_h", C.c_int32),
+                ("resize_w", C.c_int32), ("resize_h", C.c_int32),
+                ("win_x", C.c_int32), ("win_y", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("portrait", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AugmentDepthArgs(C.Structure):
+    """must3r_hip_augment_depth_args: the HOST view table, the depth batch stored landscape (fp32 or uint16), the scratch and the stream
+    (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("views", C.POINTER(AugmentDepthView)), ("out", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("V", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("depth_u16", C.c_int32), ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -382,6 +417,10 @@ PROTOTYPES = {
     "must3r_hip_train_attention_mode": (i32, [i32]),
     "must3r_hip_patch_rows": (i32, [P(PatchRowsArgs)]),
     "must3r_hip_gt_from_depth": (i32, [P(GtArgs)]),
+    "must3r_hip_augment_color_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_augment_color": (i32, [P(AugmentColorArgs)]),
+    "must3r_hip_augment_depth_scratch_bytes": (sz, [i32]),
+    "must3r_hip_augment_depth": (i32, [P(AugmentDepthArgs)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -35,6 +35,7 @@ reference's values for the same seeds (tests/golden/select_batch_cases.json).
 * ``args.pointmaps_activation`` defaults to ``get_pointmaps_activation(decoder)`` where ``train(args)`` has not set it.
 
 Not built: ``train(args)`` itself (building a dataset, ``eval``-ing the model strings, the epoch loop around the checkpoints), DDP and tensorboard.
+(Crop, resize and colour augmentation of raw frames in front of the loop: ``train_augment.augment_views`` / ``AugmentedScenes``.)
 """
 import argparse
 import math

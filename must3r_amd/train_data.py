@@ -16,7 +16,8 @@ those of the true image and the kernel swaps the pixel coordinates instead of th
 
 ``SyntheticDepthScenes`` shows the scenes of ``synthetic.SyntheticScenes`` through depth, intrinsics and pose, for tests and scripts/bench_train_data.py.
 
-Not built: the dataset classes and samplers, crop, resize and colour augmentation.  CPU tensors raise in ``ground_truth``.
+Crop, resize and colour augmentation of raw frames into this depth form are ``train_augment``'s.  Not built: the dataset classes and samplers.  CPU tensors
+raise in ``ground_truth``.
 """
 import ctypes as C
 import math
