@@ -37,12 +37,28 @@ template <class T> __device__ __forceinline__ typename Vec<T>::v4 cvt4(f32x4 v) 
 }
 // saturating form for the GEMM epilogues: an fp16 store of |v| > 65504 would be +-inf and turn into NaN downstream (LayerNorm,
 // softmax); the value is clamped to the largest finite fp16 instead (in-range values: same bits).  bf16 has fp32's range.
+// A NaN stays a NaN: a clamp in fp32 (v_med3_f32 returns the smaller bound for a NaN) stored -65504 for it and hid the fault from everything
+// downstream (tests/test_resid_forms_gpu.py).  So the conversion comes first -- |v| >= 65520 and +-inf become +-inf, 65504 < |v| < 65520 round to
+// 65504 by themselves, NaN stays NaN -- and the two infinities are stepped back one code on the packed halves: x = (h & 0x7fff) ^ 0x7c00 is 0 for
+// them alone, 1 -sat x is 1 there and 0 elsewhere (v_bitop3_b32, v_pk_sub_u16 clamp, v_pk_sub_u16: 3 instructions per two values, one more than the clamp).
+typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
 template <class T> __device__ __forceinline__ typename Vec<T>::v4 cvt4_sat(f32x4 v) {
+    typedef typename Vec<T>::v4 v4;
+    const v4 h = __builtin_convertvector(v, v4);
     if constexpr (sizeof(T) == 2 && !__is_same(T, bf16_t)) {
+        unsigned b[2];
+        __builtin_memcpy(b, &h, 8);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = __builtin_amdgcn_fmed3f(v[r], -65504.0f, 65504.0f);
+        for (int d = 0; d < 2; ++d) {
+            const u16x2 x = __builtin_bit_cast(u16x2, (b[d] & 0x7FFF7FFFu) ^ 0x7C007C00u);
+            const u16x2 y = __builtin_elementwise_sub_sat(u16x2{1, 1}, x);
+            b[d] = __builtin_bit_cast(unsigned, (u16x2)(__builtin_bit_cast(u16x2, b[d]) - y));
+        }
+        v4 o;
+        __builtin_memcpy(&o, b, 8);
+        return o;
     }
-    return __builtin_convertvector(v, typename Vec<T>::v4);
+    return h;
 }
 template <class T> __device__ __forceinline__ typename Vec<T>::v8 cvt8(f32x8 v) {
     return __builtin_convertvector(v, typename Vec<T>::v8);
@@ -186,6 +202,7 @@ __device__ __forceinline__ int swz_v(int row, int chunk) { return chunk ^ (((row
 // |erfc error| <= 5.9e-7, |GELU error| <= 1.3e-6 absolute in fp32 arithmetic (relative 6e-5 where |GELU| > 1e-2) -- an eighth of the 16-bit rounding
 // of the result.  P is positive and z P(z) increasing for every z >= 0 (leading coefficient > 0), so large |x| need no clamp: 2^(-z P) underflows to 0
 // and the result is max(x, 0) exactly; the negative tail is a product, not a cancellation (0.5 x (1 + erf) loses the tail to 1 - 1).
+// Defined on finite x: +-inf gives NaN (fma(-inf, 0, max(x, 0))), NaN gives NaN (tests/test_resid_forms_gpu.py sweeps the domain).
 // ONE transcendental (exp2) + 6 FMAs per value instead of two (rcp, exp2) + 7 FMAs + 6 other of the Abramowitz-Stegun 7.1.26 form used through r03 (1.5e-7): the erf
 // epilogue was ~8 us of a 39 us fc1 tile, VALU-bound with the quarter-rate transcendentals at 44 % of it.
 // Coefficients in a = |x| directly (Q_k = P_k / sqrt(2)^(k+1)), and the factor 1/2 folded into the exponent:
