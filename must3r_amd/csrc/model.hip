@@ -79,6 +79,7 @@ struct must3r_hip_ctx {
     bool fin_enc = false, fin_dec = false;
     // per-layer parameter tables (resolved once: no string building / map lookups per launch); entries of absent parameters are null
     std::vector<std::vector<struct Param*>> enc_tab, dec_tab;
+    DType dt = DT_F16;         // operand type of the running forward's kernels; this and the next three: set_mode()
     int wsplit = 0;            // 2 while a forward runs in MUST3R_F16_W2 / MUST3R_F16_WA mode
     int mlp_plain = 0;         // 1 in MUST3R_F16_WA mode: the Mlp Linears take plain fp16 weights (one MFMA pass)
     int attn8 = 0;             // 1 while a forward runs with MUST3R_ATTN_FP8 (e4m3 attention operands)
@@ -86,7 +87,7 @@ struct must3r_hip_ctx {
     int rope_npos = 0;
     // workspace arena (grow-only)
     char* ws = nullptr;
-    size_t ws_cap = 0, ws_off = 0;
+    size_t ws_cap = 0;
     // pinned staging for per-call view tables
     static constexpr int kSlots = 32;
     static constexpr size_t kSlotBytes = 64 * 1024;
@@ -124,7 +125,7 @@ struct DeviceGuard {
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 static int ws_reserve(must3r_hip_ctx* c, size_t bytes, hipStream_t s) {
-    if (bytes <= c->ws_cap) { c->ws_off = 0; return 0; }
+    if (bytes <= c->ws_cap) return 0;
     if (c->ws) {
         HIP_OK(hipStreamSynchronize(s));
         HIP_OK(hipDeviceSynchronize());
@@ -134,16 +135,27 @@ static int ws_reserve(must3r_hip_ctx* c, size_t bytes, hipStream_t s) {
     const size_t cap = align_up(bytes + bytes / 8, 1 << 20);
     HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->ws), cap));
     c->ws_cap = cap;
-    c->ws_off = 0;
     return 0;
 }
-template <class T> static T* ws_take(must3r_hip_ctx* c, size_t count) {
-    const size_t off = align_up(c->ws_off, 256);
-    c->ws_off = off + count * sizeof(T);
-    if (c->ws_off > c->ws_cap) return nullptr;  // cannot happen if reserve() was sized with ws_need()
-    return reinterpret_cast<T*>(c->ws + off);
-}
-static size_t ws_need(size_t cur, size_t count, size_t elt) { return align_up(cur, 256) + count * elt; }
+// Workspace planner of one forward: every buffer is requested ONCE, typed by its pointer; commit() sums the requests, reserves the arena and only then
+// assigns the pointers (nothing may capture a buffer before it).  Each buffer starts at the next multiple of 256 bytes, in request order; a count of 0
+// leaves the pointer null.
+struct Workspace {
+    struct Req { void* ptr; size_t bytes; };   // ptr: address of the caller's T* variable
+    std::vector<Req> reqs;
+    template <class T> void want(T*& p, size_t count) { p = nullptr; reqs.push_back(Req{&p, count * sizeof(T)}); }
+    int commit(must3r_hip_ctx* c, hipStream_t s) {
+        size_t need = 0, off = 0;
+        for (const Req& r : reqs) need = align_up(need, 256) + r.bytes;
+        M3R_OK(ws_reserve(c, need, s));
+        for (const Req& r : reqs) {
+            char* const at = c->ws + (off = align_up(off, 256));
+            if (r.bytes) memcpy(r.ptr, &at, sizeof(at));
+            off += r.bytes;
+        }
+        return 0;
+    }
+};
 
 // upload a small host table to device memory that stays valid until the stream has consumed it
 static int upload_table(must3r_hip_ctx* c, const void* host, size_t bytes, void** dev, hipStream_t s) {
@@ -239,10 +251,6 @@ static int layernorm_a(must3r_hip_ctx* c, DType dt, const LnArgs& a, hipStream_t
     ProfScope ps(c, s, PC_LN, 0.0);
     if (launch_layernorm(dt, a, s, &err)) return fail("%s", err);
     return 0;
-}
-static int layernorm(must3r_hip_ctx* c, DType dt, const float* x, const float* add, const float* w, const float* b,
-                     void* o16, void* o16lo, float* o32, float* copy, int M, int C, float eps, hipStream_t s) {
-    return layernorm_a(c, dt, lnargs(x, add, w, b, o16, o16lo, o32, copy, M, C, eps), s);
 }
 // The two launches of the prediction head, shared by must3r_hip_decode and the training forward (train_head.hip; c = nullptr there: no profiling):
 // LayerNorm of the residual stream into the [y_hi | y_lo | y_hi] rows of 3 D (+ the fp32 y of return_feats), then ONE plain GEMM over K = 3 D against the
@@ -508,21 +516,24 @@ extern "C" int must3r_hip_create(const must3r_hip_config* cfg, int device, must3
     return 0;
 }
 
+// drop the packed copies of a parameter (they are rebuilt from the fp32 master on next use)
+static void free_packed(must3r_hip_ctx* c, Param& p) {
+    for (int i = 0; i < 2; ++i) {
+        if (p.x2[i]) c->sparse_lo.erase(p.x2[i]);
+        for (void** q : {&p.h16[i], &p.l16[i], &p.x2[i], &p.x3[i]})
+            if (*q) { (void)hipFree(*q); *q = nullptr; }
+    }
+    for (void** q : {&p.sp_vals, &p.sp_idx})
+        if (*q) { (void)hipFree(*q); *q = nullptr; }
+}
+
 extern "C" void must3r_hip_destroy(must3r_hip_ctx* c) {
     if (!c) return;
     DeviceGuard dev_guard(c->device);
     (void)hipDeviceSynchronize();
     for (auto& kv : c->params) {
-        Param& p = kv.second;
-        if (p.d) (void)hipFree(p.d);
-        for (int i = 0; i < 2; ++i) {
-            if (p.h16[i]) (void)hipFree(p.h16[i]);
-            if (p.l16[i]) (void)hipFree(p.l16[i]);
-            if (p.x2[i]) (void)hipFree(p.x2[i]);
-            if (p.x3[i]) (void)hipFree(p.x3[i]);
-        }
-        if (p.sp_vals) (void)hipFree(p.sp_vals);
-        if (p.sp_idx) (void)hipFree(p.sp_idx);
+        free_packed(c, kv.second);
+        if (kv.second.d) (void)hipFree(kv.second.d);
     }
     if (c->rope_tab) (void)hipFree(c->rope_tab);
     if (c->ws) (void)hipFree(c->ws);
@@ -545,14 +556,7 @@ extern "C" int must3r_hip_load_weight(must3r_hip_ctx* c, const char* name, const
     DeviceGuard dev_guard(c->device);
     if (!p->d) HIP_OK(hipMalloc(reinterpret_cast<void**>(&p->d), p->n * sizeof(float)));
     HIP_OK(hipMemcpy(p->d, data, p->n * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; ++i) {  // invalidate packed copies
-        if (p->h16[i]) { (void)hipFree(p->h16[i]); p->h16[i] = nullptr; }
-        if (p->l16[i]) { (void)hipFree(p->l16[i]); p->l16[i] = nullptr; }
-        if (p->x2[i]) { c->sparse_lo.erase(p->x2[i]); (void)hipFree(p->x2[i]); p->x2[i] = nullptr; }
-        if (p->x3[i]) { (void)hipFree(p->x3[i]); p->x3[i] = nullptr; }
-    }
-    if (p->sp_vals) { (void)hipFree(p->sp_vals); p->sp_vals = nullptr; }
-    if (p->sp_idx) { (void)hipFree(p->sp_idx); p->sp_idx = nullptr; }
+    free_packed(c, *p);
     p->loaded = true;
     if (strncmp(name, "encoder.", 8) == 0) c->fin_enc = false; else c->fin_dec = false;
     return 0;
@@ -561,14 +565,7 @@ extern "C" int must3r_hip_load_weight(must3r_hip_ctx* c, const char* name, const
 static int derive(must3r_hip_ctx* c, const std::string& name, std::vector<int64_t> shape, const std::vector<float>& host) {
     Param& p = c->params[name];
     if (p.d) { (void)hipFree(p.d); p.d = nullptr; }
-    for (int i = 0; i < 2; ++i) {
-        if (p.h16[i]) { (void)hipFree(p.h16[i]); p.h16[i] = nullptr; }
-        if (p.l16[i]) { (void)hipFree(p.l16[i]); p.l16[i] = nullptr; }
-        if (p.x2[i]) { c->sparse_lo.erase(p.x2[i]); (void)hipFree(p.x2[i]); p.x2[i] = nullptr; }
-        if (p.x3[i]) { (void)hipFree(p.x3[i]); p.x3[i] = nullptr; }
-    }
-    if (p.sp_vals) { (void)hipFree(p.sp_vals); p.sp_vals = nullptr; }
-    if (p.sp_idx) { (void)hipFree(p.sp_idx); p.sp_idx = nullptr; }
+    free_packed(c, p);
     p.shape = shape;
     p.n = host.size();
     p.derived = true;
@@ -708,22 +705,110 @@ extern "C" int must3r_hip_finalize_weights(must3r_hip_ctx* c, int parts) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// what the two forwards share: the precision mode, the LN-fold state, the two sublayers every block has
+// ------------------------------------------------------------------------------------------------
+// the ABI's dtype word -> c->dt (operand type of the kernels), c->wsplit, c->mlp_plain, c->attn8; false: not one of the four dtypes
+static bool set_mode(must3r_hip_ctx* c, int dtype) {
+    const int d = dtype & ~MUST3R_ATTN_FP8;
+    if (d != MUST3R_BF16 && d != MUST3R_F16 && d != MUST3R_F16_W2 && d != MUST3R_F16_WA) return false;
+    c->attn8 = (dtype & MUST3R_ATTN_FP8) ? 1 : 0;
+    c->wsplit = (d == MUST3R_F16_W2 || d == MUST3R_F16_WA) ? 2 : 0;
+    c->mlp_plain = d == MUST3R_F16_WA ? 1 : 0;
+    c->dt = c->wsplit == 2 ? DT_F16 : (DType)d;
+    return true;
+}
+
+// LN fold (kernels.hpp GemmArgs "LN fold") of one forward: the LayerNorm launches of the blocks are not issued; a residual GEMM leaves the 16-bit rows +
+// per-fragment sums (out), the Linear behind the folded norm reads them with the gamma-scaled weight and normalises after its product (in)
+struct Fold {
+    uint16_t* x16 = nullptr;   // the residual stream rounded to fp16 (fold256: the shifted rows); null: this forward does not fold
+    float* stats = nullptr;    // per row and 16-column fragment (fold256: 64-column wave tile) (sum, sum of squares)
+    float* shift = nullptr;    // per row: the mean the last consumer measured (shift of the next rows)
+    bool f256 = false;         // the chip-filling form (GemmArgs::fold256): shift is zeroed up front, the consumers add to it, its first producer reads zeros
+    bool fresh = true;         // nothing measured yet in this call: the first consumer starts the estimate
+    bool on() const { return x16 != nullptr; }
+    void in(GemmArgs& g, const Param* s, const Param* c) {
+        g.A = x16; g.ln_stats = stats; g.ln_s = s->d; g.bias = c->d; g.ln_eps = 1e-6f;
+        g.ln_shift = shift; g.ln_shift_init = (fresh && !f256) ? 1 : 0; g.fold256 = f256 ? 1 : 0;
+        fresh = false;
+    }
+    void out(GemmArgs& g, float* copy32) const { g.x16_out = x16; g.stats_out = stats; g.copy32_out = copy32; g.ln_shift = shift; g.fold256 = f256 ? 1 : 0; }   // copy32: the memorised input of the next block (decoder.py:304-305)
+};
+
+// rows and scratch of the block sublayers: R rows of width C (hidden width F) in the fp32 residual stream x
+struct BlockRows {
+    int R, C, heads, F;
+    float* x; uint16_t *h16, *qkv, *a16, *g16;
+    uint8_t* q8;               // e4m3 copies of q | k (fp8 attention build only)
+    const int64_t* pos;        // [R, 2]
+};
+// the views of a self attention: device table, count, longest view, FLOPs, and (one view) the view itself to pass inline
+struct SelfViews { const AttnView* dev; int n, max_n; double flops; const AttnView* inline0; };
+
+// x += proj(attention(rope(qkv(norm1(x)))))  (layers.py:51-54 / :91).  fold_n1: norm1 is folded into qkv; otherwise its kernel runs, leaves copy32 (the
+// block's memorised input) and mean_out (the row means: the shift of this block's proj producer) where given
+static int self_attention_sublayer(must3r_hip_ctx* c, DType dt, const std::vector<Param*>& LP, const BlockRows& b, const SelfViews& v, Fold& fold, bool fold_n1,
+                                   float* copy32, float* mean_out, hipStream_t s) {
+    const int R = b.R, C = b.C;
+    const bool a8 = kAttnFp8Built && c->attn8 != 0;   // (compiles out of the default build, kernels.hpp)
+    const void* w;
+    if (!fold_n1) {
+        LnArgs la = lnargs(b.x, nullptr, LP[LF_N1W]->d, LP[LF_N1B]->d, b.h16, nullptr, nullptr, copy32, R, C, 1e-6f);
+        if (mean_out) { la.mean_out = mean_out; fold.fresh = false; }
+        M3R_OK(layernorm_a(c, dt, la, s));
+    }
+    M3R_OK(w16p(c, *LP[fold_n1 ? LF_QKVLN_W : LF_QKVW], dt, &w, s));
+    GemmArgs ga = gargs(b.h16, w, LP[LF_QKVB]->d, b.qkv, R, 3 * C, C, C, 3 * C);
+    if (fold_n1) fold.in(ga, LP[LF_QKVLN_S], LP[LF_QKVLN_C]);
+    ga.pos = b.pos; ga.rope_tab = c->rope_tab; ga.rope_cols = 2 * C; ga.rope_npos = c->rope_npos;
+    ga.out_scale = kQScale; ga.scale_cols = C;   // q *= 1/sqrt(64) * log2(e)
+    M3R_OK(gemm(c, dt, EPI_QKV_ROPE, ga, s));
+    AttnArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.Q = b.qkv; aa.K = b.qkv + C; aa.V = b.qkv + 2 * C; aa.O = b.a16;
+    aa.ldq = aa.ldk = aa.ldv = 3 * C; aa.ldo = C; aa.heads = b.heads;
+    aa.views = v.dev; aa.nviews = v.n; aa.max_nq = v.max_n; aa.scale = 0.125f; aa.q_prescaled = 1;
+    if (v.inline0) { aa.view0_inline = 1; aa.view0 = *v.inline0; }
+    if (a8 && !attention_is_small(v.n, b.heads, v.max_n, 1)) {   // e4m3 copies of q | k (one byte per element); V stays 16-bit
+        M3R_OK(quant8(c, dt, b.qkv, 3 * C, b.q8, 2 * C, nullptr, 0, (size_t)R, 2 * C, 0, s));
+        aa.Q = b.q8; aa.K = b.q8 + C; aa.ldq = aa.ldk = 2 * C; aa.fp8 = 1;
+    }
+    aa.max_nk = v.max_n;
+    M3R_OK(attention(c, dt, aa, v.flops, PC_ATTN_SA, s));
+    M3R_OK(w16p(c, *LP[LF_PROJW], dt, &w, s));
+    GemmArgs gp = gargs(b.a16, w, LP[LF_PROJB]->d, b.x, R, C, C, C, C);
+    if (fold.on()) fold.out(gp, nullptr);
+    return gemm(c, dt, EPI_RESID_F32, gp, s);
+}
+
+// x += fc2(gelu(fc1(norm(x))))  (layers.py:54 / :98); norm_w: the block's last norm (LF_N2W in the encoder, LF_N3W in the decoder), folded into fc1 when the
+// forward folds.  leave_rows: fc2 leaves the rows for the next block's norm1 (+ copy32, that block's memorised input)
+static int mlp_sublayer(must3r_hip_ctx* c, DType dt, const std::vector<Param*>& LP, int norm_w, const BlockRows& b, Fold& fold, bool leave_rows, float* copy32,
+                        hipStream_t s) {
+    const int R = b.R, C = b.C, F = b.F;
+    const bool folded = fold.on();
+    const void* w;
+    int ws;
+    if (!folded) M3R_OK(layernorm_a(c, dt, lnargs(b.x, nullptr, LP[norm_w]->d, LP[norm_w + 1]->d, b.h16, nullptr, nullptr, nullptr, R, C, 1e-6f), s));
+    M3R_OK(wmlp(c, *LP[folded ? LF_FC1LN_W : LF_FC1W], dt, &w, &ws, s));
+    GemmArgs g1 = gargs(b.h16, w, LP[LF_FC1B]->d, b.g16, R, F, C, C, F);
+    if (folded) fold.in(g1, LP[LF_FC1LN_S], LP[LF_FC1LN_C]);
+    M3R_OK(gemm(c, dt, EPI_STORE16_GELU, g1, s, ws));
+    M3R_OK(wmlp(c, *LP[LF_FC2W], dt, &w, &ws, s));
+    GemmArgs g2 = gargs(b.g16, w, LP[LF_FC2B]->d, b.x, R, C, F, F, C);
+    if (leave_rows) fold.out(g2, copy32);
+    return gemm(c, dt, EPI_RESID_F32, g2, s, ws);
+}
+
+// ------------------------------------------------------------------------------------------------
 // encoder  (Dust3rEncoder.forward encoder.py:46-52)
 // ------------------------------------------------------------------------------------------------
 static int encode_chunk(must3r_hip_ctx* c, DType dt, const float* img, int V, int H, int W, float* out_tokens,
                         int64_t* out_pos, hipStream_t s) {
     const must3r_hip_config& g = c->cfg;
-    const int C = g.enc_dim, gh = H / 16, gw = W / 16, N = gh * gw, R = V * N, Hh = g.enc_heads, F = g.mlp_ratio * C;
+    const int C = g.enc_dim, gh = H / 16, gw = W / 16, N = gh * gw, R = V * N, F = g.mlp_ratio * C;
     const char* err = "";
     const bool a8 = kAttnFp8Built && c->attn8 != 0;   // (compiles out of the default build, kernels.hpp)
-    size_t need = 0;
-    need = ws_need(need, (size_t)R * 768, 2);
-    need = ws_need(need, (size_t)R * C, 4);
-    need = ws_need(need, (size_t)R * C, 2);
-    need = ws_need(need, (size_t)R * 3 * C, 2);
-    need = ws_need(need, (size_t)R * C, 2);
-    need = ws_need(need, (size_t)R * F, 2);
-    need = ws_need(need, a8 ? (size_t)R * 2 * C : 0, 1);
     // r06, LN fold on the chip-filling launches (GemmArgs::fold256; MUST3R_F16_WA): norm1 of blocks 1.. and norm2 of every block are not launched -- the residual
     // GEMM in front of them (fc2 of the previous block / proj) leaves the shifted rows in fp16 + per-wave-tile sums, qkv / fc1 normalise after their product.
     // Block 0's norm1 keeps its kernel (its rows come from the patch embedding, an EPI_F32 launch).  Only when every Linear of the block lands on the fold kernels.
@@ -732,26 +817,21 @@ static int encode_chunk(must3r_hip_ctx* c, DType dt, const float* img, int V, in
                       c->enc_tab[0][LF_QKVLN_W] && c->enc_tab[0][LF_FC1LN_W] &&
                       gemm_fold256_shape_ok(R, 3 * C, C, true) && gemm_fold256_shape_ok(R, C, C, true) &&
                       gemm_fold256_shape_ok(R, F, C, false) && gemm_fold256_shape_ok(R, C, F, false);
-    need = ws_need(need, f256 ? (size_t)R * C : 0, 2);                 // x16: the shifted residual rows in fp16
-    need = ws_need(need, f256 ? (size_t)R * (C / 64) * 2 : 0, 4);      // per row and 64-column wave tile (sum, sum of squares)
-    need = ws_need(need, f256 ? (size_t)R : 0, 4);                     // per row: the current mean (GemmArgs::ln_shift)
-    M3R_OK(ws_reserve(c, need, s));
-    uint16_t* P16 = ws_take<uint16_t>(c, (size_t)R * 768);
-    float* x = ws_take<float>(c, (size_t)R * C);
-    uint16_t* h16 = ws_take<uint16_t>(c, (size_t)R * C);
-    uint16_t* qkv = ws_take<uint16_t>(c, (size_t)R * 3 * C);
-    uint16_t* a16 = ws_take<uint16_t>(c, (size_t)R * C);
-    uint16_t* g16 = ws_take<uint16_t>(c, (size_t)R * F);
-    uint8_t* q8 = a8 ? ws_take<uint8_t>(c, (size_t)R * 2 * C) : nullptr;
-    uint16_t* x16 = f256 ? ws_take<uint16_t>(c, (size_t)R * C) : nullptr;
-    float* lnstats = f256 ? ws_take<float>(c, (size_t)R * (C / 64) * 2) : nullptr;
-    float* lnshift = f256 ? ws_take<float>(c, (size_t)R) : nullptr;
-    if (!g16 || (a8 && !q8) || (f256 && !lnshift)) return fail("encode: workspace sizing bug");
-    if (f256) HIP_OK(hipMemsetAsync(lnshift, 0, (size_t)R * sizeof(float), s));
-    auto fold_in = [&](GemmArgs& g_, const Param* sn, const Param* cn) {
-        g_.A = x16; g_.ln_stats = lnstats; g_.ln_s = sn->d; g_.bias = cn->d; g_.ln_eps = 1e-6f; g_.ln_shift = lnshift; g_.fold256 = 1;
-    };
-    auto fold_out = [&](GemmArgs& g_) { g_.x16_out = x16; g_.stats_out = lnstats; g_.ln_shift = lnshift; g_.fold256 = 1; };
+    Workspace ws; uint16_t* P16;
+    BlockRows b{R, C, g.enc_heads, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out_pos};
+    Fold fold; fold.f256 = f256;
+    ws.want(P16, (size_t)R * 768);
+    ws.want(b.x, (size_t)R * C);
+    ws.want(b.h16, (size_t)R * C);
+    ws.want(b.qkv, (size_t)R * 3 * C);
+    ws.want(b.a16, (size_t)R * C);
+    ws.want(b.g16, (size_t)R * F);
+    ws.want(b.q8, a8 ? (size_t)R * 2 * C : 0);
+    ws.want(fold.x16, f256 ? (size_t)R * C : 0);                  // the shifted residual rows in fp16
+    ws.want(fold.stats, f256 ? (size_t)R * (C / 64) * 2 : 0);     // per row and 64-column wave tile (sum, sum of squares)
+    ws.want(fold.shift, f256 ? (size_t)R : 0);                    // per row: the current mean (GemmArgs::ln_shift)
+    M3R_OK(ws.commit(c, s));
+    if (f256) HIP_OK(hipMemsetAsync(fold.shift, 0, (size_t)R * sizeof(float), s));
 
     {
         ProfScope ps(c, s, PC_MISC, 0.0);
@@ -762,60 +842,18 @@ static int encode_chunk(must3r_hip_ctx* c, DType dt, const float* img, int V, in
     for (int v = 0; v < V; ++v) views[v] = AttnView{v * N, N, v * N, N, 0, 0};
     void* views_dev = nullptr;
     M3R_OK(upload_table(c, views.data(), sizeof(AttnView) * V, &views_dev, s));
+    const SelfViews sv{reinterpret_cast<const AttnView*>(views_dev), V, N, 4.0 * V * (double)N * N * C, nullptr};   // (never inline: the encoder reads its table)
 
     const void* w;
     M3R_OK(w16(c, "encoder.patch_embed.proj.weight", dt, &w, s));
-    M3R_OK(gemm(c, dt, EPI_F32, gargs(P16, w, p32(c, "encoder.patch_embed.proj.bias"), x, R, C, 768, 768, C), s));
+    M3R_OK(gemm(c, dt, EPI_F32, gargs(P16, w, p32(c, "encoder.patch_embed.proj.bias"), b.x, R, C, 768, 768, C), s));
     for (int l = 0; l < g.enc_depth; ++l) {
         const std::vector<Param*>& LP = c->enc_tab[l];
-        const bool fq = f256 && l > 0;
-        if (!fq)
-            M3R_OK(layernorm(c, dt, x, nullptr, LP[LF_N1W]->d, LP[LF_N1B]->d, h16, nullptr, nullptr,
-                             nullptr, R, C, 1e-6f, s));
-        M3R_OK(w16p(c, *LP[fq ? LF_QKVLN_W : LF_QKVW], dt, &w, s));
-        GemmArgs ga = gargs(h16, w, LP[LF_QKVB]->d, qkv, R, 3 * C, C, C, 3 * C);
-        if (fq) fold_in(ga, LP[LF_QKVLN_S], LP[LF_QKVLN_C]);
-        ga.pos = out_pos; ga.rope_tab = c->rope_tab; ga.rope_cols = 2 * C; ga.rope_npos = c->rope_npos;
-        ga.out_scale = kQScale; ga.scale_cols = C;   // q *= 1/sqrt(64) * log2(e)
-        M3R_OK(gemm(c, dt, EPI_QKV_ROPE, ga, s));
-        AttnArgs aa;
-        memset(&aa, 0, sizeof(aa));
-        aa.Q = qkv; aa.K = qkv + C; aa.V = qkv + 2 * C; aa.O = a16;
-        aa.ldq = aa.ldk = aa.ldv = 3 * C; aa.ldo = C; aa.heads = Hh;
-        aa.views = reinterpret_cast<const AttnView*>(views_dev); aa.nviews = V; aa.max_nq = N; aa.scale = 0.125f;
-        aa.q_prescaled = 1;
-        if (a8 && !attention_is_small(V, Hh, N, 1)) {   // e4m3 copies of q | k (one byte per element); V stays 16-bit
-            M3R_OK(quant8(c, dt, qkv, 3 * C, q8, 2 * C, nullptr, 0, (size_t)R, 2 * C, 0, s));
-            aa.Q = q8; aa.K = q8 + C; aa.ldq = aa.ldk = 2 * C; aa.fp8 = 1;
-        }
-        aa.max_nk = N;
-        M3R_OK(attention(c, dt, aa, 4.0 * V * (double)N * N * C, PC_ATTN_SA, s));
-        M3R_OK(w16p(c, *LP[LF_PROJW], dt, &w, s));
-        {
-            GemmArgs gp = gargs(a16, w, LP[LF_PROJB]->d, x, R, C, C, C, C);
-            if (f256) fold_out(gp);
-            M3R_OK(gemm(c, dt, EPI_RESID_F32, gp, s));
-        }
-        if (!f256)
-            M3R_OK(layernorm(c, dt, x, nullptr, LP[LF_N2W]->d, LP[LF_N2B]->d, h16, nullptr, nullptr,
-                             nullptr, R, C, 1e-6f, s));
-        int ws;
-        M3R_OK(wmlp(c, *LP[f256 ? LF_FC1LN_W : LF_FC1W], dt, &w, &ws, s));
-        {
-            GemmArgs g1 = gargs(h16, w, LP[LF_FC1B]->d, g16, R, F, C, C, F);
-            if (f256) fold_in(g1, LP[LF_FC1LN_S], LP[LF_FC1LN_C]);
-            M3R_OK(gemm(c, dt, EPI_STORE16_GELU, g1, s, ws));
-        }
-        M3R_OK(wmlp(c, *LP[LF_FC2W], dt, &w, &ws, s));
-        {
-            GemmArgs g2 = gargs(g16, w, LP[LF_FC2B]->d, x, R, C, F, F, C);
-            if (f256 && l + 1 < g.enc_depth) fold_out(g2);   // the next block's norm1
-            M3R_OK(gemm(c, dt, EPI_RESID_F32, g2, s, ws));
-        }
+        M3R_OK(self_attention_sublayer(c, dt, LP, b, sv, fold, f256 && l > 0, nullptr, nullptr, s));
+        M3R_OK(mlp_sublayer(c, dt, LP, LF_N2W, b, fold, f256 && l + 1 < g.enc_depth, nullptr, s));   // (leaves the next block's norm1 its rows)
     }
-    M3R_OK(layernorm(c, dt, x, nullptr, p32(c, "encoder.norm_enc.weight"), p32(c, "encoder.norm_enc.bias"), nullptr, nullptr,
-                     out_tokens, nullptr, R, C, 1e-6f, s));
-    return 0;
+    return layernorm_a(c, dt, lnargs(b.x, nullptr, p32(c, "encoder.norm_enc.weight"), p32(c, "encoder.norm_enc.bias"), nullptr, nullptr,
+                     out_tokens, nullptr, R, C, 1e-6f), s);
 }
 
 extern "C" int must3r_hip_encode(must3r_hip_ctx* c, int dtype, const float* img, int n_views, int H, int W,
@@ -823,12 +861,7 @@ extern "C" int must3r_hip_encode(must3r_hip_ctx* c, int dtype, const float* img,
     if (!c || !img || !out_tokens || !out_pos) return fail("encode: null argument");
     if (!c->fin_enc) return fail("encode: encoder weights not finalized");
     if ((dtype & MUST3R_ATTN_FP8) && !kAttnFp8Built) return fail("encode: MUST3R_ATTN_FP8 is an experiment build (make EXTRA=-DM3R_ATTN_FP8): measured outside the 1e-3 target for +0.4 %%");
-    c->attn8 = (dtype & MUST3R_ATTN_FP8) ? 1 : 0;
-    dtype &= ~MUST3R_ATTN_FP8;
-    if (dtype != MUST3R_BF16 && dtype != MUST3R_F16 && dtype != MUST3R_F16_W2 && dtype != MUST3R_F16_WA) return fail("encode: bad dtype %d", dtype);
-    c->wsplit = (dtype == MUST3R_F16_W2 || dtype == MUST3R_F16_WA) ? 2 : 0;
-    c->mlp_plain = dtype == MUST3R_F16_WA ? 1 : 0;
-    if (dtype == MUST3R_F16_W2 || dtype == MUST3R_F16_WA) dtype = MUST3R_F16;
+    if (!set_mode(c, dtype)) return fail("encode: bad dtype %d", dtype & ~MUST3R_ATTN_FP8);
     if (n_views <= 0) return 0;
     if (H <= 0 || W <= 0 || H % 16 || W % 16) return fail("encode: H=%d W=%d must be positive multiples of 16", H, W);
     if (H / 16 > c->rope_npos || W / 16 > c->rope_npos) return fail("encode: image too large for the RoPE table");
@@ -847,7 +880,7 @@ extern "C" int must3r_hip_encode(must3r_hip_ctx* c, int dtype, const float* img,
     }
     for (int v0 = 0; v0 < n_views; v0 += per) {
         const int nv = (n_views - v0 < per) ? n_views - v0 : per;
-        M3R_OK(encode_chunk(c, (DType)dtype, img + (size_t)v0 * 3 * H * W, nv, H, W, out_tokens + (size_t)v0 * N * c->cfg.enc_dim,
+        M3R_OK(encode_chunk(c, c->dt, img +(size_t)v0 * 3 * H * W, nv, H, W, out_tokens + (size_t)v0 * N * c->cfg.enc_dim,
                             out_pos + (size_t)v0 * N * 2, s));
     }
     return 0;
@@ -856,473 +889,439 @@ extern "C" int must3r_hip_encode(must3r_hip_ctx* c, int dtype, const float* img,
 // ------------------------------------------------------------------------------------------------
 // decoder  (MUSt3R.forward_list decoder.py:158-265; forward :267-350 is the single-group case)
 // ------------------------------------------------------------------------------------------------
-// one native call = one launch sequence; must3r_hip_decode (below) validates the arguments and cuts oversize render calls
-static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void* stream) {
-    const int adt = A->dtype & ~MUST3R_ATTN_FP8;
-    c->attn8 = (A->dtype & MUST3R_ATTN_FP8) ? 1 : 0;
-    if (adt != MUST3R_BF16 && adt != MUST3R_F16 && adt != MUST3R_F16_W2 && adt != MUST3R_F16_WA) return fail("decode: bad dtype %d", A->dtype);
-    c->wsplit = (adt == MUST3R_F16_W2 || adt == MUST3R_F16_WA) ? 2 : 0;
-    c->mlp_plain = adt == MUST3R_F16_WA ? 1 : 0;
-    if (A->mem_mode != MUST3R_MEM_KV && A->mem_mode != MUST3R_MEM_NORM_Y && A->mem_mode != MUST3R_MEM_RAW)
-        return fail("decode: bad mem_mode %d", A->mem_mode);
-    if (A->n_groups <= 0) return fail("decode: no input group");
-    if (A->render && (A->first_call || A->n_mem <= 0)) return fail("decode: render needs a memory (decoder.py:278)");
-    if (A->first_call && A->n_mem != 0) return fail("decode: first_call with a non-empty memory");
-    DeviceGuard dev_guard(c->device);
-    if (c->dec_tab.empty()) build_layer_tables(c, true);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const DType dt = (adt == MUST3R_F16_W2 || adt == MUST3R_F16_WA) ? DT_F16 : (DType)adt;
-    const bool a8 = kAttnFp8Built && c->attn8 != 0;   // (the default build has no e4m3 attention path: every `a8` branch below compiles out)
-    const must3r_hip_config& g = c->cfg;
-    const int C = g.enc_dim, D = g.dec_dim, Hh = g.dec_heads, F = g.mlp_ratio * D, L = g.dec_depth, Nm = A->n_mem;
-    const int OUT = g.patch_size * g.patch_size * 7;
-    const char* err = "";
+// one native call = one launch sequence (decode_impl, at the end of this section); must3r_hip_decode (below) validates the arguments and cuts oversize
+// render calls.  Plan and state of one call; the plan (decode_plan) depends on cfg, the arguments and the options only:
+struct Decode {
+    must3r_hip_ctx* c; const must3r_hip_decode_args* A; void* stream; hipStream_t s; DType dt; bool a8;
+    int C, D, Hh, F, L, Nm, mode;
+    // row layout
+    int S, Rs, R, total_views, max_n; long long mem_stride; std::vector<int> grow0; bool one_block;
+    // the call's flags
+    bool update, use_mask, lone_view, need_pre_kv, lnf, lnf_all, f256;
+    const must3r_hip_cp* cp;
+    int max_nk_ca, ca_split, memD; size_t split_bytes, memRB, kvs_rows1, kvs_rows, kv16_rows;
+    // workspace (decode_workspace)
+    BlockRows b; Fold fold;
+    uint16_t *t16, *hcat, *q16, *yall, *kvs, *ytmp, *kv16; float *newmem, *off32; char* split_ws; uint8_t* kvs8;
+    // per-call tables (decode_tables)
+    std::vector<AttnView> tab; SelfViews sv; const AttnView* ca_views; double ca_flops; void* const* kvout;
+};
 
+static void decode_plan(Decode& d) {
+    must3r_hip_ctx* c = d.c; const must3r_hip_decode_args* A = d.A;
+    const must3r_hip_config& g = c->cfg;
+    d.dt = c->dt;
+    d.a8 = kAttnFp8Built && c->attn8 != 0;   // (the default build has no e4m3 attention path: every `a8` branch below compiles out)
+    d.C = g.enc_dim; d.D = g.dec_dim; d.Hh = g.dec_heads; d.F = g.mlp_ratio * g.dec_dim; d.L = g.dec_depth; d.Nm = A->n_mem; d.mode = A->mem_mode;
+    const int D = d.D, F = d.F, Nm = d.Nm;
     // ---- row layout: scenes (batch elements, decoder.py:170-186: B), then groups, then views, then tokens (x_cat order of a scene,
     //      decoder.py:211-214).  The S scenes of a call never interact (memory, labels and attention are per batch element): they
     //      share every launch -- M = S x rows-per-scene in the GEMMs, S x views in the attention tables -- and nothing else.
-    const int S = A->n_scenes > 1 ? A->n_scenes : 1;
-    const long long mem_stride = S > 1 ? A->mem_scene_stride : 0;      // memory rows between two scenes' buffers
-    int Rs = 0, views_s = 0, max_n = 0;
-    std::vector<int> grow0(A->n_groups);
+    const int S = d.S = A->n_scenes > 1 ? A->n_scenes : 1;
+    d.mem_stride = S > 1 ? A->mem_scene_stride : 0;      // memory rows between two scenes' buffers
+    int Rs = 0, views_s = 0;
+    d.max_n = 0;
+    d.grow0.resize(A->n_groups);
     for (int gi = 0; gi < A->n_groups; ++gi) {
         const must3r_hip_group& G = A->groups[gi];
-        grow0[gi] = Rs;
+        d.grow0[gi] = Rs;
         Rs += G.n_views * G.n_tokens;
         views_s += G.n_views;
-        if (G.n_tokens > max_n) max_n = G.n_tokens;
+        if (G.n_tokens > d.max_n) d.max_n = G.n_tokens;
     }
-    const int R = S * Rs, total_views = S * views_s;
-    const bool one_block = A->n_groups == 1;                           // a group's [S, n_views, n_tokens] rows ARE the call's row order
-    const bool update = !A->render;
+    const int R = S * Rs;
+    d.Rs = Rs; d.R = R; d.total_views = S * views_s;
+    d.one_block = A->n_groups == 1;                           // a group's [S, n_views, n_tokens] rows ARE the call's row order
+    const bool update = d.update = !A->render;
     // r06, context-parallel cross attention (include/must3r_hip.h must3r_hip_cp): Nm = THIS rank's shard of the memory (possibly empty), the call's semantics
     // follow the GLOBAL row count (validated by must3r_hip_decode: one-view update of one scene, 'kv' memory, 16-bit attention)
-    const must3r_hip_cp* cp = A->cp;
-    const int Nm_global = cp ? cp->n_mem_total : Nm;
-    const bool use_mask = update && (Nm_global > 0 || views_s > 1);    // decoder.py:199 / :293
-    const bool lone_view = update && views_s == 1 && Nm_global > 0;    // own tokens excluded -> keys = old memory only
-    const bool need_pre_kv = update && !lone_view;                     // pre-feedback K|V of the new tokens are attended
-
-    // ---- workspace
-    size_t need = 0;
-    need = ws_need(need, (size_t)R * C, 2);           // t16
-    need = ws_need(need, (size_t)R * D, 4);           // x
-    need = ws_need(need, (size_t)R * D, 2);           // h16
-    need = ws_need(need, (size_t)R * 3 * D, 2);       // [y_hi | y_lo | y_hi] operand of the head
-    need = ws_need(need, (size_t)R * 3 * D, 2);       // qkv
-    need = ws_need(need, (size_t)R * D, 2);           // q16
-    need = ws_need(need, (size_t)R * D, 2);           // a16
-    need = ws_need(need, (size_t)R * F, 2);           // g16
-    if (update) {
-        need = ws_need(need, (size_t)L * R * D, 4);   // memorised layer inputs
-        need = ws_need(need, (size_t)R * D, 4);       // feedback offset
-        need = ws_need(need, (size_t)L * R * D, 2);   // norm_y of all layers (grouped K|V projection)
-    }
+    d.cp = A->cp;
+    const int Nm_global = d.cp ? d.cp->n_mem_total : Nm;
+    d.use_mask = update && (Nm_global > 0 || views_s > 1);    // decoder.py:199 / :293
+    d.lone_view = update && views_s == 1 && Nm_global > 0;    // own tokens excluded -> keys = old memory only
+    d.need_pre_kv = update && !d.lone_view;                   // pre-feedback K|V of the new tokens are attended
     // LN fold (one-view update calls, fp16 + split weights): the LayerNorm launches of the blocks are not issued; the residual GEMMs
     // leave 16-bit rows + per-fragment sums, the Linears that follow normalise after their product (kernels.hpp GemmArgs "LN fold").
     // Block 0's norm1 keeps its kernel (35 of the 36 launches go): a consumer multiplies the fp16 copy of x - shift, so its error grows with
     // |mean - shift| / sigma of the row, and the embedded tokens come with no estimate of their mean -- a common offset of 40 sigma in the embed
     // bias took the update pointmaps of a 48 x 64 scene from 4.9e-4 to 1.4e-3 (tests/test_lnfold_model_gpu.py; the bound per launch form:
     // tests/lnfold_forms.py).  The LayerNorm launch pays nothing for an offset and leaves the row means as the shift of block 0's first producer.  M3R_LNFOLD=2 (A/B instrument): block 0's norm1 folded too.
-    const bool lnf_on = opt(OPT_LNFOLD) != 0;
     // (S > 1: the consumers of the fold only exist on the small-M tile shapes; a batched call is past the launch floor the fold removes)
-    const bool lnf = lnf_on && update && !need_pre_kv && c->wsplit == 2 && dt == DT_F16 && !a8 && !A->feats && A->n_groups == 1 &&
-                     S == 1 && D == 768 && F % 96 == 0;
+    d.lnf = opt(OPT_LNFOLD) != 0 && update && !d.need_pre_kv && c->wsplit == 2 && d.dt == DT_F16 && !d.a8 && !A->feats && A->n_groups == 1 &&
+            S == 1 && D == 768 && F % 96 == 0;
     // r06: the same fold on the chip-filling launches of a batched call -- update or render -- (GemmArgs::fold256; MUST3R_F16_WA): block 0's norm1 keeps its kernel
     // (its rows come from an EPI_F32 launch), every other norm1 / norm2 / norm3 is folded.  Only when every Linear of the block lands on the fold kernels.
-    const bool f256 = !lnf && opt(OPT_LNFOLD256) != 0 && c->wsplit == 2 && c->mlp_plain && dt == DT_F16 && !a8 && !A->feats && !A->cp && (D == 768 || D == 1024) &&
-                      gemm_fold256_shape_ok(R, 3 * D, D, true) && gemm_fold256_shape_ok(R, D, D, true) &&
-                      gemm_fold256_shape_ok(R, F, D, false) && gemm_fold256_shape_ok(R, D, F, false);
-    const bool lnf_all = lnf && opt(OPT_LNFOLD) == 2;   // block 0's norm1 folded as well: its consumer reads unshifted rows
-    const bool lnF = lnf || f256;
-    need = ws_need(need, lnF ? (size_t)R * D : 0, 2);                 // x16: the residual stream rounded to fp16
-    need = ws_need(need, lnF ? (size_t)R * (D / 16) * 2 : 0, 4);      // per row and 16-column fragment (f256: 64-column wave tile) (sum, sum of squares)
-    need = ws_need(need, lnF ? (size_t)R : 0, 4);                     // per row: the mean the last consumer measured (shift of the next rows)
+    d.f256 = !d.lnf && opt(OPT_LNFOLD256) != 0 && c->wsplit == 2 && c->mlp_plain && d.dt == DT_F16 && !d.a8 && !A->feats && !A->cp && (D == 768 || D == 1024) &&
+             gemm_fold256_shape_ok(R, 3 * D, D, true) && gemm_fold256_shape_ok(R, D, D, true) &&
+             gemm_fold256_shape_ok(R, F, D, false) && gemm_fold256_shape_ok(R, D, F, false);
+    d.lnf_all = d.lnf && opt(OPT_LNFOLD) == 2;   // block 0's norm1 folded as well: its consumer reads unshifted rows
     // split-KV cross attention when the launch cannot fill the chip (sequential memory update: one view per call)
-    const int max_nk_ca = A->render ? Nm : Nm + (lone_view ? 0 : Rs);
+    d.max_nk_ca = A->render ? Nm : Nm + (d.lone_view ? 0 : Rs);
     // (context parallel: the local attention always leaves split-KV partials -- at least two splits, an empty one costs nothing -- for the partial merge)
-    int ca_split = attention_pick_split(total_views, Hh, max_n, max_nk_ca);
-    if (cp) ca_split = Nm > 0 ? (ca_split > 2 ? ca_split : 2) : 0;
-    const size_t split_bytes = attention_split_scratch_bytes(ca_split, R, Hh);
-    need = ws_need(need, split_bytes, 1);
+    d.ca_split = attention_pick_split(d.total_views, d.Hh, d.max_n, d.max_nk_ca);
+    if (d.cp) d.ca_split = Nm > 0 ? (d.ca_split > 2 ? d.ca_split : 2) : 0;
+    d.split_bytes = attention_split_scratch_bytes(d.ca_split, R, d.Hh);
     // memory_mode 'norm_y' / 'raw': the memory holds (normalised / raw) tokens, K|V of ALL attended rows are projected
     // per layer per call into scratch (the reference re-projects them per query view, layers.py:92-96)
-    const int mode = A->mem_mode;
-    const int memD = mode == MUST3R_MEM_KV ? 2 * D : D;
+    d.memD = d.mode == MUST3R_MEM_KV ? 2 * D : D;
     // bytes of a memory row: 16-bit elements, except the K (e4m3, D bytes) | V (16-bit, 2 D bytes) rows of the fp8-attention mode
-    const size_t memRB = (a8 && mode == MUST3R_MEM_KV) ? (size_t)3 * D : (size_t)memD * 2;
-    const size_t kvs_rows1 = mode == MUST3R_MEM_KV ? 0 : (size_t)max_nk_ca;   // per scene
-    const size_t kvs_rows = kvs_rows1 * S;
-    need = ws_need(need, kvs_rows * 2 * D, 2);
-    need = ws_need(need, mode == MUST3R_MEM_RAW ? kvs_rows * D : 0, 2);
-    // fp8 attention: e4m3 copies of q|k|v (self) / q (cross), 16-bit staging of freshly projected K|V rows before they are
-    // quantised into the memory, e4m3 copy of the per-call K|V projection of the 'norm_y' / 'raw' modes
-    const size_t kv16_rows = (a8 && mode == MUST3R_MEM_KV && update) ? (size_t)L * R : 0;
-    need = ws_need(need, a8 ? (size_t)R * 2 * D : 0, 1);
-    need = ws_need(need, kv16_rows * 2 * D, 2);
-    need = ws_need(need, a8 ? kvs_rows * D : 0, 1);
-    M3R_OK(ws_reserve(c, need, s));
-    uint16_t* t16 = ws_take<uint16_t>(c, (size_t)R * C);
-    float* x = ws_take<float>(c, (size_t)R * D);
-    uint16_t* h16 = ws_take<uint16_t>(c, (size_t)R * D);
-    uint16_t* hcat = ws_take<uint16_t>(c, (size_t)R * 3 * D);
-    uint16_t* qkv = ws_take<uint16_t>(c, (size_t)R * 3 * D);
-    uint16_t* q16 = ws_take<uint16_t>(c, (size_t)R * D);
-    uint16_t* a16 = ws_take<uint16_t>(c, (size_t)R * D);
-    uint16_t* g16 = ws_take<uint16_t>(c, (size_t)R * F);
-    float* newmem = update ? ws_take<float>(c, (size_t)L * R * D) : nullptr;
-    float* off32 = update ? ws_take<float>(c, (size_t)R * D) : nullptr;
-    uint16_t* yall = update ? ws_take<uint16_t>(c, (size_t)L * R * D) : nullptr;
-    uint16_t* x16 = lnF ? ws_take<uint16_t>(c, (size_t)R * D) : nullptr;
-    float* lnstats = lnF ? ws_take<float>(c, (size_t)R * (D / 16) * 2) : nullptr;
-    float* lnshift = lnF ? ws_take<float>(c, (size_t)R) : nullptr;
-    bool lnshift_fresh = true;   // nothing measured yet in this call: the first consumer starts the estimate
-    if (f256) HIP_OK(hipMemsetAsync(lnshift, 0, (size_t)R * sizeof(float), s));   // (the fold256 consumers add to it; its first producer reads zeros)
-    char* split_ws = split_bytes ? ws_take<char>(c, split_bytes) : nullptr;
-    uint16_t* kvs = kvs_rows ? ws_take<uint16_t>(c, kvs_rows * 2 * D) : nullptr;
-    uint16_t* ytmp = (mode == MUST3R_MEM_RAW && kvs_rows) ? ws_take<uint16_t>(c, kvs_rows * D) : nullptr;
-    uint8_t* q8 = a8 ? ws_take<uint8_t>(c, (size_t)R * 2 * D) : nullptr;
-    uint16_t* kv16 = kv16_rows ? ws_take<uint16_t>(c, kv16_rows * 2 * D) : nullptr;
-    uint8_t* kvs8 = (a8 && kvs_rows) ? ws_take<uint8_t>(c, kvs_rows * D) : nullptr;   // e4m3 K of the per-call projection ('norm_y' / 'raw')
-    if (!g16 || (update && !off32) || (split_bytes && !split_ws) || (a8 && !q8) || (kv16_rows && !kv16) || (a8 && kvs_rows && !kvs8))
-        return fail("decode: workspace sizing bug");
+    d.memRB = (d.a8 && d.mode == MUST3R_MEM_KV) ? (size_t)3 * D : (size_t)d.memD * 2;
+    d.kvs_rows1 = d.mode == MUST3R_MEM_KV ? 0 : (size_t)d.max_nk_ca;   // per scene
+    d.kvs_rows = d.kvs_rows1 * S;
+    // fp8 attention: 16-bit staging of freshly projected K|V rows before they are quantised into the memory
+    d.kv16_rows = (d.a8 && d.mode == MUST3R_MEM_KV && update) ? (size_t)d.L * R : 0;
+}
 
-    // ---- per-view tables: self-attention, cross-attention; positions gathered into one [R,2] array
-    std::vector<AttnView> tab(2 * (size_t)total_views);
-    double sa_flops = 0, ca_flops = 0;
-    {
-        // K|V rows a scene's cross attention reads: its own memory buffer ('kv': rows b * mem_stride of the layer's buffer) or its slice
-        // of the per-call projection scratch ('norm_y' / 'raw')
-        const long long kv_stride = mode == MUST3R_MEM_KV ? mem_stride : (long long)kvs_rows1;
-        int vi = 0;
-        for (int b = 0; b < S; ++b)
-            for (int gi = 0; gi < A->n_groups; ++gi) {
-                const must3r_hip_group& G = A->groups[gi];
-                for (int j = 0; j < G.n_views; ++j, ++vi) {
-                    const int rl = grow0[gi] + j * G.n_tokens, n = G.n_tokens;   // row inside the scene
-                    const int r0 = b * Rs + rl;
-                    tab[vi] = AttnView{r0, n, r0, n, 0, 0};
-                    AttnView cv{r0, n, (int)(b * kv_stride), Nm, 0, 0};
-                    if (update) {
-                        if (lone_view) { cv.nk = Nm; }
-                        else if (use_mask && A->causal) {
-                            // CausalMUSt3R.make_attn_mask (decoder.py:389-433): old memory + the new tokens of the views before this one = a PREFIX of the key rows;
-                            // empty memory: view 0 attends view 1's tokens (labels < 2, != 0: decoder.py:399-402) = rows [n, 2n) behind an excluded [0, n)
-                            if (Nm == 0 && j == 0) { cv.nk = 2 * n; cv.skip_lo = 0; cv.skip_hi = n; }
-                            else { cv.nk = Nm + rl; }
-                        }
-                        else if (use_mask) { cv.nk = Nm + Rs; cv.skip_lo = Nm + rl; cv.skip_hi = Nm + rl + n; }
-                        else { cv.nk = Nm + Rs; }  // first view alone: attends its own (pre-feedback) tokens
+static int decode_workspace(Decode& d) {
+    const size_t R = d.R, D = d.D, L = d.L;
+    const bool update = d.update, lnF = d.lnf || d.f256, a8 = d.a8;
+    d.b = BlockRows{d.R, d.D, d.Hh, d.F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d.A->groups[0].pos};   // single group: the caller's array is already [R,2]
+    d.fold.f256 = d.f256;
+    Workspace ws;
+    ws.want(d.t16, R * d.C);
+    ws.want(d.b.x, R * D);
+    ws.want(d.b.h16, R * D);
+    ws.want(d.hcat, R * 3 * D);                              // [y_hi | y_lo | y_hi] operand of the head
+    ws.want(d.b.qkv, R * 3 * D);
+    ws.want(d.q16, R * D);
+    ws.want(d.b.a16, R * D);
+    ws.want(d.b.g16, R * d.F);
+    ws.want(d.newmem, update ? L * R * D : 0);               // memorised layer inputs
+    ws.want(d.off32, update ? R * D : 0);                    // feedback offset
+    ws.want(d.yall, update ? L * R * D : 0);                 // norm_y of all layers (grouped K|V projection)
+    ws.want(d.fold.x16, lnF ? R * D : 0);
+    ws.want(d.fold.stats, lnF ? R * (D / 16) * 2 : 0);
+    ws.want(d.fold.shift, lnF ? R : 0);
+    ws.want(d.split_ws, d.split_bytes);
+    ws.want(d.kvs, d.kvs_rows * 2 * D);
+    ws.want(d.ytmp, d.mode == MUST3R_MEM_RAW ? d.kvs_rows * D : 0);
+    // fp8 attention: e4m3 copies of q|k|v (self) / q (cross), the 16-bit staging rows, e4m3 K of the per-call projection ('norm_y' / 'raw')
+    ws.want(d.b.q8, a8 ? R * 2 * D : 0);
+    ws.want(d.kv16, d.kv16_rows * 2 * D);
+    ws.want(d.kvs8, a8 ? d.kvs_rows * D : 0);
+    M3R_OK(ws.commit(d.c, d.s));
+    if (d.f256) HIP_OK(hipMemsetAsync(d.fold.shift, 0, R * sizeof(float), d.s));   // (the fold256 consumers add to it; its first producer reads zeros)
+    return 0;
+}
+
+// per-view tables: self-attention, cross-attention; the K|V destination table of an update
+static int decode_tables(Decode& d) {
+    const must3r_hip_decode_args* A = d.A;
+    const int S = d.S, Rs = d.Rs, Nm = d.Nm, D = d.D, L = d.L, total_views = d.total_views;
+    d.tab.resize(2 * (size_t)total_views);
+    double sa_flops = 0;
+    d.ca_flops = 0;
+    // K|V rows a scene's cross attention reads: its own memory buffer ('kv': rows b * mem_stride of the layer's buffer) or its slice
+    // of the per-call projection scratch ('norm_y' / 'raw')
+    const long long kv_stride = d.mode == MUST3R_MEM_KV ? d.mem_stride : (long long)d.kvs_rows1;
+    int vi = 0;
+    for (int b = 0; b < S; ++b)
+        for (int gi = 0; gi < A->n_groups; ++gi) {
+            const must3r_hip_group& G = A->groups[gi];
+            for (int j = 0; j < G.n_views; ++j, ++vi) {
+                const int rl = d.grow0[gi] + j * G.n_tokens, n = G.n_tokens;   // row inside the scene
+                const int r0 = b * Rs + rl;
+                d.tab[vi] = AttnView{r0, n, r0, n, 0, 0};
+                AttnView cv{r0, n, (int)(b * kv_stride), Nm, 0, 0};
+                if (d.update) {
+                    if (d.lone_view) { cv.nk = Nm; }
+                    else if (d.use_mask && A->causal) {
+                        // CausalMUSt3R.make_attn_mask (decoder.py:389-433): old memory + the new tokens of the views before this one = a PREFIX of the key rows;
+                        // empty memory: view 0 attends view 1's tokens (labels < 2, != 0: decoder.py:399-402) = rows [n, 2n) behind an excluded [0, n)
+                        if (Nm == 0 && j == 0) { cv.nk = 2 * n; cv.skip_lo = 0; cv.skip_hi = n; }
+                        else { cv.nk = Nm + rl; }
                     }
-                    tab[total_views + vi] = cv;
-                    sa_flops += 4.0 * n * (double)n * D;
-                    ca_flops += 4.0 * n * (double)(cv.nk - (cv.skip_hi - cv.skip_lo)) * D;
+                    else if (d.use_mask) { cv.nk = Nm + Rs; cv.skip_lo = Nm + rl; cv.skip_hi = Nm + rl + n; }
+                    else { cv.nk = Nm + Rs; }  // first view alone: attends its own (pre-feedback) tokens
                 }
+                d.tab[total_views + vi] = cv;
+                sa_flops += 4.0 * n * (double)n * D;
+                d.ca_flops += 4.0 * n * (double)(cv.nk - (cv.skip_hi - cv.skip_lo)) * D;
             }
-    }
+        }
     void* tab_dev = nullptr;
-    M3R_OK(upload_table(c, tab.data(), sizeof(AttnView) * tab.size(), &tab_dev, s));
+    M3R_OK(upload_table(d.c, d.tab.data(), sizeof(AttnView) * d.tab.size(), &tab_dev, d.s));
     const AttnView* sa_views = reinterpret_cast<const AttnView*>(tab_dev);
-    const AttnView* ca_views = sa_views + total_views;
-    const int64_t* pos_all = A->groups[0].pos;  // single group: the caller's array is already [R,2]
+    d.ca_views = sa_views + total_views;
+    d.sv = SelfViews{sa_views, total_views, d.max_n, sa_flops, total_views == 1 ? &d.tab[0] : nullptr};   // (a single view travels inline)
 
     // per-(layer, scene) destinations of freshly projected K|V rows: memory rows [Nm, Nm + Rs) of scene b in layer l's buffer;
     // second half: the 16-bit staging rows the fp8 memory is quantised from
     void* kvout_dev = nullptr;
-    if (update && mode == MUST3R_MEM_KV) {
+    if (d.update && d.mode == MUST3R_MEM_KV) {
         std::vector<void*> outs(2 * (size_t)L * S);
         for (int l = 0; l < L; ++l)
             for (int b = 0; b < S; ++b) {
-                void* memrow = reinterpret_cast<char*>(A->mem[l]) + ((size_t)b * mem_stride + Nm) * memRB;
-                outs[(size_t)l * S + b] = a8 ? static_cast<void*>(kv16 + ((size_t)l * S + b) * Rs * 2 * D) : memrow;
+                void* memrow = reinterpret_cast<char*>(A->mem[l]) + ((size_t)b * d.mem_stride + Nm) * d.memRB;
+                outs[(size_t)l * S + b] = d.a8 ? static_cast<void*>(d.kv16 + ((size_t)l * S + b) * Rs * 2 * D) : memrow;
                 outs[(size_t)L * S + (size_t)l * S + b] = memrow;
             }
-        M3R_OK(upload_table(c, outs.data(), sizeof(void*) * outs.size(), &kvout_dev, s));
+        M3R_OK(upload_table(d.c, outs.data(), sizeof(void*) * outs.size(), &kvout_dev, d.s));
     }
-    void* const* kvout = reinterpret_cast<void* const*>(kvout_dev);
+    d.kvout = reinterpret_cast<void* const*>(kvout_dev);
+    return 0;
+}
 
-    // ---- tokens -> 16 bit, enc->dec projection + image2_embed  (decoder.py:172-181 / :275-287)
-    for (int b = 0; b < (one_block ? 1 : S); ++b)
+// tokens -> 16 bit, enc->dec projection + image2_embed  (decoder.py:172-181 / :275-287); several groups: their positions gathered into one [R,2] array
+static int decode_embed(Decode& d) {
+    must3r_hip_ctx* c = d.c; const must3r_hip_decode_args* A = d.A; hipStream_t s = d.s;
+    const int S = d.S, Rs = d.Rs, C = d.C, D = d.D;
+    const char* err = "";
+    for (int b = 0; b < (d.one_block ? 1 : S); ++b)
         for (int gi = 0; gi < A->n_groups; ++gi) {
             const must3r_hip_group& G = A->groups[gi];
             const size_t rg = (size_t)G.n_views * G.n_tokens;   // rows of this group per scene
             ProfScope ps(c, s, PC_MISC, 0.0);
-            if (launch_cast(dt, G.tokens + (size_t)b * rg * C, t16 + ((size_t)b * Rs + grow0[gi]) * C, nullptr, (one_block ? S : 1) * rg * C, s, &err))
+            if (launch_cast(d.dt, G.tokens + (size_t)b * rg * C, d.t16 + ((size_t)b * Rs + d.grow0[gi]) * C, nullptr, (d.one_block ? S : 1) * rg * C, s, &err))
                 return fail("%s", err);
         }
     const void* w;
-    {
-        M3R_OK(w16(c, "decoder.feat_embed_enc_to_dec.weight", dt, &w, s));
-        GemmArgs ga = gargs(t16, w, p32(c, "decoder.feat_embed_enc_to_dec.bias"), x, R, D, C, C, D);
-        ga.bias2 = p32(c, "decoder.image2_embed");
-        ga.row_start2 = A->first_call ? A->groups[0].n_tokens : 0;  // reference view (group 0, view 0) of every scene gets no embed
-        ga.row_period2 = S > 1 ? Rs : 0;
-        if (lnf_all) { ga.x16_out = x16; ga.stats_out = lnstats; ga.copy32_out = newmem; }   // block 0's norm1 input (+ its memorised copy)
-        M3R_OK(gemm(c, dt, EPI_F32, ga, s));
-    }
+    M3R_OK(w16(c, "decoder.feat_embed_enc_to_dec.weight", d.dt, &w, s));
+    GemmArgs ga = gargs(d.t16, w, p32(c, "decoder.feat_embed_enc_to_dec.bias"), d.b.x, d.R, D, C, C, D);
+    ga.bias2 = p32(c, "decoder.image2_embed");
+    ga.row_start2 = A->first_call ? A->groups[0].n_tokens : 0;  // reference view (group 0, view 0) of every scene gets no embed
+    ga.row_period2 = S > 1 ? Rs : 0;
+    if (d.lnf_all) { ga.x16_out = d.fold.x16; ga.stats_out = d.fold.stats; ga.copy32_out = d.newmem; }   // block 0's norm1 input (+ its memorised copy)
+    M3R_OK(gemm(c, d.dt, EPI_F32, ga, s));
     // several aspect ratios: gather the positions of all rows into one [R,2] array.  t16 is dead after the
     // projection above (stream order) and is large enough (R*C*2 >= R*16 bytes).
-    if (!one_block) {
-        int64_t* pos_ws = reinterpret_cast<int64_t*>(t16);
+    if (!d.one_block) {
+        int64_t* pos_ws = reinterpret_cast<int64_t*>(d.t16);
         for (int b = 0; b < S; ++b)
             for (int gi = 0; gi < A->n_groups; ++gi) {
                 const must3r_hip_group& G = A->groups[gi];
                 const size_t rg = (size_t)G.n_views * G.n_tokens;
-                HIP_OK(hipMemcpyAsync(pos_ws + ((size_t)b * Rs + grow0[gi]) * 2, G.pos + (size_t)b * rg * 2, rg * 16, hipMemcpyDeviceToDevice, s));
+                HIP_OK(hipMemcpyAsync(pos_ws + ((size_t)b * Rs + d.grow0[gi]) * 2, G.pos + (size_t)b * rg * 2, rg * 16, hipMemcpyDeviceToDevice, s));
             }
-        pos_all = pos_ws;
+        d.b.pos = pos_ws;
     }
-
-    // prepare_y (layers.py:81-88) of the R new token rows, written to memory rows [Nm, Nm+R) in the caller's mode:
-    //   'kv'     LN(norm_y) -> [projk | projv]       'norm_y'  LN(norm_y)        'raw'  the tokens themselves
-    auto kv_project = [&](int l, const float* src, const float* add, float* copy, hipStream_t st) -> int {
-        const std::vector<Param*>& LP = c->dec_tab[l];
-        if (mode != MUST3R_MEM_KV) {   // the LayerNorm itself writes the scene's memory rows (one launch per scene)
-            for (int b = 0; b < S; ++b) {
-                uint16_t* dst = reinterpret_cast<uint16_t*>(A->mem[l]) + ((size_t)b * mem_stride + Nm) * memD;
-                const size_t o = (size_t)b * Rs * D;
-                LnArgs la = lnargs(src + o, add ? add + o : nullptr, LP[LF_NYW]->d, LP[LF_NYB]->d, nullptr, nullptr, nullptr, copy ? copy + o : nullptr,
-                                   Rs, D, 1e-6f);
-                if (mode == MUST3R_MEM_NORM_Y) la.out16 = dst; else la.raw16 = dst;
-                M3R_OK(layernorm_a(c, dt, la, st));
-            }
-            return 0;
-        }
-        M3R_OK(layernorm_a(c, dt, lnargs(src, add, LP[LF_NYW]->d, LP[LF_NYB]->d, h16, nullptr, nullptr, copy, R, D, 1e-6f), st));
-        const void* wk;
-        M3R_OK(w16p(c, *LP[LF_PKVW], dt, &wk, st));
-        // one problem per scene (same weights): rows [b Rs, (b+1) Rs) -> memory rows of scene b (fp8 memory: 16-bit staging rows first)
-        GemmArgs gk = gargs(h16, wk, LP[LF_PKVB]->d, nullptr, Rs, 2 * D, D, D, 2 * D);
-        gk.batch = S; gk.strideA = (long long)Rs * D; gk.out_table = kvout + (size_t)l * S;
-        if (S == 1) { gk.batch = 0; gk.out_table = nullptr; gk.out = a8 ? static_cast<void*>(kv16) : reinterpret_cast<char*>(A->mem[l]) + (size_t)Nm * memRB; }
-        M3R_OK(gemm(c, dt, EPI_STORE16, gk, st));
-        if (!a8) return 0;
-        // K -> e4m3, V copied: memory rows [K e4m3 | V 16-bit]
-        return quant8(c, dt, kv16 + (size_t)l * S * Rs * 2 * D * (S > 1 ? 1 : 0), 2 * D, S == 1 ? reinterpret_cast<char*>(A->mem[l]) + (size_t)Nm * memRB : nullptr,
-                      3 * D, S > 1 ? kvout + (size_t)L * S + (size_t)l * S : nullptr, Rs, (size_t)R, D, D, st);
-    };
-    // K|V rows the cross attention of layer l reads: the memory itself ('kv') or a projection of it into scratch
-    auto kv_source = [&](int l, const void** kptr, hipStream_t st) -> int {
-        if (mode == MUST3R_MEM_KV) { *kptr = A->mem[l]; return 0; }
-        const std::vector<Param*>& LP = c->dec_tab[l];
-        const int rows = (int)kvs_rows1;
-        const void* wk;
-        M3R_OK(w16p(c, *LP[LF_PKVW], dt, &wk, st));
-        for (int b = 0; b < S; ++b) {
-            const uint16_t* src = reinterpret_cast<const uint16_t*>(A->mem[l]) + (size_t)b * mem_stride * D;
-            if (mode == MUST3R_MEM_RAW) {  // y_ = norm_y(y) on the stored tokens (layers.py:92)
-                LnArgs la = lnargs(nullptr, nullptr, LP[LF_NYW]->d, LP[LF_NYB]->d, ytmp, nullptr, nullptr, nullptr,
-                                   rows, D, 1e-6f);
-                la.x16 = src;
-                M3R_OK(layernorm_a(c, dt, la, st));
-                src = ytmp;
-            }
-            M3R_OK(gemm(c, dt, EPI_STORE16, gargs(src, wk, LP[LF_PKVB]->d, kvs + (size_t)b * rows * 2 * D, rows, 2 * D, D, D, 2 * D), st));
-        }
-        *kptr = kvs;
-        if (a8) M3R_OK(quant8(c, dt, kvs, 2 * D, kvs8, D, nullptr, 0, (size_t)kvs_rows, D, 0, st));   // K -> e4m3 (V is read from kvs)
-        return 0;
-    };
-
-    for (int l = 0; l < L; ++l) {
-        const std::vector<Param*>& LP = c->dec_tab[l];
-        if (need_pre_kv) M3R_OK(kv_project(l, x, nullptr, nullptr, s));
-        // --- self attention (layers.py:91)
-        // LN fold: a consumer reads the raw 16-bit rows + fragment sums its producer left, with the gamma-scaled weight
-        auto fold_in = [&](GemmArgs& g_, int fs) {
-            g_.A = x16; g_.ln_stats = lnstats; g_.ln_s = LP[fs]->d; g_.bias = LP[fs + 1]->d; g_.ln_eps = 1e-6f;
-            g_.ln_shift = lnshift; g_.ln_shift_init = (lnshift_fresh && !f256) ? 1 : 0;   // (f256: the buffer was zeroed)
-            g_.fold256 = f256 ? 1 : 0;
-            lnshift_fresh = false;
-        };
-        // ... and a residual GEMM leaves them for the next consumer (copy: the memorised input of the next block, decoder.py:304-305)
-        auto fold_out = [&](GemmArgs& g_, float* copy) {
-            g_.x16_out = x16; g_.stats_out = lnstats; g_.copy32_out = copy; g_.ln_shift = lnshift; g_.fold256 = f256 ? 1 : 0;
-        };
-        const bool fq = lnf_all || ((lnf || f256) && l > 0);   // is this block's norm1 folded?
-        if (!fq) {
-            LnArgs la = lnargs(x, nullptr, LP[LF_N1W]->d, LP[LF_N1B]->d, h16, nullptr, nullptr, update ? newmem + (size_t)l * R * D : nullptr, R, D, 1e-6f);
-            if (lnf) { la.mean_out = lnshift; lnshift_fresh = false; }   // the row means: the shift of this block's proj producer
-            M3R_OK(layernorm_a(c, dt, la, s));
-        }
-        M3R_OK(w16p(c, *LP[fq ? LF_QKVLN_W : LF_QKVW], dt, &w, s));
-        GemmArgs ga = gargs(h16, w, LP[LF_QKVB]->d, qkv, R, 3 * D, D, D, 3 * D);
-        if (fq) fold_in(ga, LF_QKVLN_S);
-        ga.pos = pos_all; ga.rope_tab = c->rope_tab; ga.rope_cols = 2 * D; ga.rope_npos = c->rope_npos;
-        ga.out_scale = kQScale; ga.scale_cols = D;
-        M3R_OK(gemm(c, dt, EPI_QKV_ROPE, ga, s));
-        AttnArgs aa;
-        memset(&aa, 0, sizeof(aa));
-        aa.Q = qkv; aa.K = qkv + D; aa.V = qkv + 2 * D; aa.O = a16;
-        aa.ldq = aa.ldk = aa.ldv = 3 * D; aa.ldo = D; aa.heads = Hh;
-        aa.views = sa_views; aa.nviews = total_views; aa.max_nq = max_n; aa.scale = 0.125f; aa.q_prescaled = 1;
-        if (total_views == 1) { aa.view0_inline = 1; aa.view0 = tab[0]; }
-        if (a8 && !attention_is_small(total_views, Hh, max_n, 1)) {
-            M3R_OK(quant8(c, dt, qkv, 3 * D, q8, 2 * D, nullptr, 0, (size_t)R, 2 * D, 0, s));
-            aa.Q = q8; aa.K = q8 + D; aa.ldq = aa.ldk = 2 * D; aa.fp8 = 1;
-        }
-        aa.max_nk = max_n;
-        M3R_OK(attention(c, dt, aa, sa_flops, PC_ATTN_SA, s));
-        M3R_OK(w16p(c, *LP[LF_PROJW], dt, &w, s));
-        {
-            GemmArgs gp = gargs(a16, w, LP[LF_PROJB]->d, x, R, D, D, D, D);
-            if (lnF) fold_out(gp, nullptr);
-            M3R_OK(gemm(c, dt, EPI_RESID_F32, gp, s));
-        }
-        // --- cross attention over the memory (layers.py:92-97; attention.py:139-149)
-        if (!lnF)
-            M3R_OK(layernorm(c, dt, x, nullptr, LP[LF_N2W]->d, LP[LF_N2B]->d, h16, nullptr, nullptr, nullptr,
-                             R, D, 1e-6f, s));
-        M3R_OK(w16p(c, *LP[lnF ? LF_PQLN_W : LF_PQW], dt, &w, s));
-        {
-            GemmArgs gq = gargs(h16, w, LP[LF_PQB]->d, q16, R, D, D, D, D);
-            if (lnF) fold_in(gq, LF_PQLN_S);
-            gq.out_scale = kQScale; gq.scale_cols = D;
-            M3R_OK(gemm(c, dt, EPI_STORE16, gq, s));
-        }
-        const void* mk = nullptr;
-        M3R_OK(kv_source(l, &mk, s));
-        memset(&aa, 0, sizeof(aa));
-        aa.Q = q16; aa.K = mk; aa.V = reinterpret_cast<const uint16_t*>(mk) + D; aa.O = a16;
-        aa.ldq = D; aa.ldk = aa.ldv = 2 * D; aa.ldo = D; aa.heads = Hh;
-        if (a8) {   // e4m3 q and K; 'kv' memory rows are [K e4m3 (D bytes) | V 16-bit]: ldk in bytes, ldv in 16-bit elements
-            M3R_OK(quant8(c, dt, q16, D, q8, D, nullptr, 0, (size_t)R, D, 0, s));
-            aa.Q = q8; aa.fp8 = 1;
-            if (mode == MUST3R_MEM_KV) { aa.ldk = 3 * D; aa.ldv = 3 * D / 2; aa.V = reinterpret_cast<const char*>(mk) + D; }
-            else { aa.K = kvs8; aa.ldk = D; }   // per-call projection: K from its e4m3 copy, V from the 16-bit scratch rows
-        }
-        aa.max_nk = max_nk_ca;
-        aa.views = ca_views; aa.nviews = total_views; aa.max_nq = max_n; aa.scale = 0.125f; aa.q_prescaled = 1;
-        if (total_views == 1) { aa.view0_inline = 1; aa.view0 = tab[total_views]; }
-        if (ca_split > 1) {
-            aa.nsplit = ca_split; aa.total_q_rows = R; aa.dense_rows = 1;
-            aa.part_o = reinterpret_cast<float*>(split_ws);
-            aa.part_ml = aa.part_o + (size_t)ca_split * R * D;
-        }
-        if (cp) {
-            // this rank's keys -> ONE partial in its slot (fp32 un-normalised, or 16-bit normalised with must3r_hip_cp::partial16); all-gather of the slots (the
-            // caller's collective); merge of the world's partials into a16
-            const int p16 = cp->partial16 ? 1 : 0;
-            char* const slot0 = reinterpret_cast<char*>(cp->slots);
-            const size_t o_bytes = (size_t)R * D * (p16 ? 2 : 4);
-            float* const my_o = reinterpret_cast<float*>(slot0 + (size_t)cp->rank * cp->slot_bytes);
-            float* const my_ml = reinterpret_cast<float*>(slot0 + (size_t)cp->rank * cp->slot_bytes + o_bytes);
-            if (Nm > 0) {
-                {
-                    ProfScope ps(c, s, PC_ATTN_CA, ca_flops);
-                    if (launch_attention_phase(dt, aa, 1, s, &err)) return fail("%s", err);
-                    ps.kernel(attention_last_kernel(), "/cross");
-                }
-                ProfScope ps(c, s, PC_ATTN_COMBINE, 0.0);
-                aa.total_q_rows = R;
-                if (launch_attention_partial_merge(dt, aa, my_o, my_ml, p16, s, &err)) return fail("%s", err);
-            } else {
-                ProfScope ps(c, s, PC_ATTN_COMBINE, 0.0);
-                if (launch_attention_partial_empty(my_o, my_ml, R, Hh, p16, s, &err)) return fail("%s", err);
-            }
-            if (cp->exchange(cp->user, l, cp->slots, cp->slot_bytes, cp->world, cp->rank, stream))
-                return fail("decode: the context-parallel exchange of layer %d failed", l);
-            ProfScope ps(c, s, PC_ATTN_COMBINE, 0.0);
-            aa.total_q_rows = R;
-            if (launch_attention_partial_final(dt, aa, reinterpret_cast<const float*>(slot0), reinterpret_cast<const float*>(slot0 + o_bytes),
-                                               (long long)(cp->slot_bytes / (p16 ? 2 : 4)), (long long)(cp->slot_bytes / 4), cp->world, p16, s, &err)) return fail("%s", err);
-        } else
-        M3R_OK(attention(c, dt, aa, ca_flops, PC_ATTN_CA, s));
-        M3R_OK(w16p(c, *LP[LF_CPW], dt, &w, s));
-        {
-            GemmArgs gp = gargs(a16, w, LP[LF_CPB]->d, x, R, D, D, D, D);
-            if (lnF) fold_out(gp, nullptr);
-            M3R_OK(gemm(c, dt, EPI_RESID_F32, gp, s));
-        }
-        // --- MLP (layers.py:98)
-        if (!lnF)
-            M3R_OK(layernorm(c, dt, x, nullptr, LP[LF_N3W]->d, LP[LF_N3B]->d, h16, nullptr, nullptr, nullptr,
-                             R, D, 1e-6f, s));
-        int ws_mlp;
-        M3R_OK(wmlp(c, *LP[lnF ? LF_FC1LN_W : LF_FC1W], dt, &w, &ws_mlp, s));
-        {
-            GemmArgs g1 = gargs(h16, w, LP[LF_FC1B]->d, g16, R, F, D, D, F);
-            if (lnF) fold_in(g1, LF_FC1LN_S);
-            M3R_OK(gemm(c, dt, EPI_STORE16_GELU, g1, s, ws_mlp));
-        }
-        M3R_OK(wmlp(c, *LP[LF_FC2W], dt, &w, &ws_mlp, s));
-        {
-            GemmArgs g2 = gargs(g16, w, LP[LF_FC2B]->d, x, R, D, F, F, D);
-            if (lnF && l + 1 < L) fold_out(g2, update ? newmem + (size_t)(l + 1) * R * D : nullptr);   // the next block's norm1 input (+ its memorised copy)
-            M3R_OK(gemm(c, dt, EPI_RESID_F32, g2, s, ws_mlp));
-        }
-        if (A->feats && l < L - 1)   // return_feats: the residual stream after block l (decoder.py:321)
-            HIP_OK(hipMemcpyAsync(A->feats + (size_t)l * R * D, x, (size_t)R * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-
-    // (Measured and rejected in r02: forking this head onto a second stream so that it overlaps the feedback / memory-write chain that ends
-    // an update call -- the two chains are independent -- costs 2.5 ms per scene instead of saving 0.5: the head's blocks take CUs from
-    // the latency-critical chain.  273 vs 282 views/s, interleaved runs on one box.)
-    hipStream_t hs_ = s;
-    {
-    // --- prediction head in split precision (fp32-equivalent; decoder.py:149-156 runs it in fp32):
-        //     y = LN(x); out = y_hi W_hi + y_lo W_hi + y_hi W_lo + b, pixel-shuffled to [n,H,W,7]
-        M3R_OK(head_layernorm(c, dt, x, p32(c, "decoder.norm_dec.weight"), p32(c, "decoder.norm_dec.bias"), hcat,
-                              A->feats ? A->feats + (size_t)(L - 1) * R * D : nullptr, R, D, 1e-6f, hs_));
-        const void* wcat;
-        M3R_OK(w3(c, "decoder.head_dec.proj_ps.weight", dt, &wcat, hs_));
-        for (int b = 0; b < (one_block ? 1 : S); ++b)
-            for (int gi = 0; gi < A->n_groups; ++gi) {
-                const must3r_hip_group& G = A->groups[gi];
-                const int rg = G.n_views * G.n_tokens;                       // rows of this group per scene
-                const int Rg = one_block ? S * rg : rg;                      // one group: all scenes in one launch ([S, n, H, W, 7] is contiguous)
-                const size_t scene_elems = (size_t)G.n_views * G.H * G.W * 7;
-                const size_t scene_stride = G.pointmaps_scene_stride > 0 ? (size_t)G.pointmaps_scene_stride : scene_elems;
-                const bool skip = one_block && scene_stride != scene_elems;
-                M3R_OK(head_linear(c, dt, hcat + ((size_t)b * Rs + grow0[gi]) * 3 * D, wcat, p32(c, "decoder.head_dec.proj_ps.bias"),
-                                   G.pointmaps + (size_t)b * scene_stride, Rg, D, OUT, G.n_tokens, G.W / 16, G.H, G.W, skip ? G.n_views : 0,
-                                   skip ? (long long)(scene_stride - scene_elems) : 0, hs_));
-            }
-    }
-    if (update) {
-        // --- feedback (feedback_mechanism.py:39-53): offset = layer(LN_1e-5(new_mem[L-1])), added to layers 0..L-2;
-        //     layer = Mlp ('single_mlp'), Linear ('single_linear') or nothing (feedback_type None: no offset)
-        const bool fb_mlp = is_loaded(c, "decoder.feedback_layer.fc1.weight");
-        const bool fb_lin = !fb_mlp && is_loaded(c, "decoder.feedback_layer.weight");
-        if (fb_mlp || fb_lin)
-            M3R_OK(layernorm(c, dt, newmem + (size_t)(L - 1) * R * D, nullptr, p32(c, "decoder.feedback_norm.weight"),
-                             p32(c, "decoder.feedback_norm.bias"), h16, nullptr, nullptr, nullptr, R, D, 1e-5f, s));
-        if (fb_mlp) {
-            int ws_fb;
-            M3R_OK(wmlp(c, c->params.at("decoder.feedback_layer.fc1.weight"), dt, &w, &ws_fb, s));
-            M3R_OK(gemm(c, dt, EPI_STORE16_GELU, gargs(h16, w, p32(c, "decoder.feedback_layer.fc1.bias"), g16, R, 4 * D, D, D, 4 * D), s, ws_fb));
-            M3R_OK(wmlp(c, c->params.at("decoder.feedback_layer.fc2.weight"), dt, &w, &ws_fb, s));
-            M3R_OK(gemm(c, dt, EPI_F32, gargs(g16, w, p32(c, "decoder.feedback_layer.fc2.bias"), off32, R, D, 4 * D, 4 * D, D), s, ws_fb));
-        } else if (fb_lin) {
-            M3R_OK(w16(c, "decoder.feedback_layer.weight", dt, &w, s));
-            M3R_OK(gemm(c, dt, EPI_F32, gargs(h16, w, p32(c, "decoder.feedback_layer.bias"), off32, R, D, D, D, D), s));
-        } else {
-            off32 = nullptr;
-        }
-        // --- stored memory = prepare_y(new_mem + offset) (decoder.py:236-239 / :327-330)
-        if (mode == MUST3R_MEM_KV) {
-            // the L projections are independent: ONE grouped LayerNorm over [L*R, D] (per-layer affine, offset on layers
-            // < L-1) and ONE grouped GEMM writing each layer's K|V rows into its own memory buffer
-            LnArgs la = lnargs(newmem, off32, p32(c, "decoder.norm_y_all.weight"), p32(c, "decoder.norm_y_all.bias"), yall, nullptr,
-                               nullptr, nullptr, L * R, D, 1e-6f);
-            la.rows_per_group = R; la.add_groups = L - 1;
-            M3R_OK(layernorm_a(c, dt, la, s));
-            // fp8 memory: the GEMM writes the 16-bit staging rows [L][S][Rs][2D], one grouped quantisation scatters them into the
-            // layers' memory rows.  Problem g = l * S + b: rows of scene b, weights of layer l = g / S.
-            const void* wk;
-            M3R_OK(w16(c, "decoder.projkv_all.weight", dt, &wk, s));
-            GemmArgs gk = gargs(yall, wk, p32(c, "decoder.projkv_all.bias"), nullptr, Rs, 2 * D, D, D, 2 * D);
-            gk.batch = L * S; gk.wdiv = S; gk.strideA = (long long)Rs * D; gk.strideW = (long long)2 * D * D * (c->wsplit == 2 ? 2 : 1);
-            gk.strideB = 2 * D; gk.out_table = kvout;
-            M3R_OK(gemm(c, dt, EPI_STORE16, gk, s));
-            if (a8) M3R_OK(quant8(c, dt, kv16, 2 * D, nullptr, 3 * D, kvout + (size_t)L * S, Rs, (size_t)L * R, D, D, s));
-        } else {
-            for (int l = 0; l < L; ++l)
-                M3R_OK(kv_project(l, newmem + (size_t)l * R * D, l < L - 1 ? off32 : nullptr, nullptr, s));
-        }
-    }
-
     return 0;
+}
+
+// prepare_y (layers.py:81-88) of the R new token rows, written to memory rows [Nm, Nm+R) in the caller's mode:
+//   'kv'     LN(norm_y) -> [projk | projv]       'norm_y'  LN(norm_y)        'raw'  the tokens themselves
+static int kv_project(Decode& d, int l, const float* src, const float* add, float* copy) {
+    must3r_hip_ctx* c = d.c; const must3r_hip_decode_args* A = d.A; hipStream_t s = d.s;
+    const int S = d.S, Rs = d.Rs, R = d.R, D = d.D, Nm = d.Nm;
+    const std::vector<Param*>& LP = c->dec_tab[l];
+    if (d.mode != MUST3R_MEM_KV) {   // the LayerNorm itself writes the scene's memory rows (one launch per scene)
+        for (int b = 0; b < S; ++b) {
+            uint16_t* dst = reinterpret_cast<uint16_t*>(A->mem[l]) + ((size_t)b * d.mem_stride + Nm) * d.memD;
+            const size_t o = (size_t)b * Rs * D;
+            LnArgs la = lnargs(src + o, add ? add + o : nullptr, LP[LF_NYW]->d, LP[LF_NYB]->d, nullptr, nullptr, nullptr, copy ? copy + o : nullptr, Rs, D, 1e-6f);
+            if (d.mode == MUST3R_MEM_NORM_Y) la.out16 = dst; else la.raw16 = dst;
+            M3R_OK(layernorm_a(c, d.dt, la, s));
+        }
+        return 0;
+    }
+    M3R_OK(layernorm_a(c, d.dt, lnargs(src, add, LP[LF_NYW]->d, LP[LF_NYB]->d, d.b.h16, nullptr, nullptr, copy, R, D, 1e-6f), s));
+    const void* wk;
+    M3R_OK(w16p(c, *LP[LF_PKVW], d.dt, &wk, s));
+    // one problem per scene (same weights): rows [b Rs, (b+1) Rs) -> memory rows of scene b (fp8 memory: 16-bit staging rows first)
+    GemmArgs gk = gargs(d.b.h16, wk, LP[LF_PKVB]->d, nullptr, Rs, 2 * D, D, D, 2 * D);
+    gk.batch = S; gk.strideA = (long long)Rs * D; gk.out_table = d.kvout + (size_t)l * S;
+    if (S == 1) { gk.batch = 0; gk.out_table = nullptr; gk.out = d.a8 ? static_cast<void*>(d.kv16) : reinterpret_cast<char*>(A->mem[l]) + (size_t)Nm * d.memRB; }
+    M3R_OK(gemm(c, d.dt, EPI_STORE16, gk, s));
+    if (!d.a8) return 0;
+    // K -> e4m3, V copied: memory rows [K e4m3 | V 16-bit]
+    return quant8(c, d.dt, d.kv16 + (size_t)l * S * Rs * 2 * D * (S > 1 ? 1 : 0), 2 * D, S == 1 ? reinterpret_cast<char*>(A->mem[l]) + (size_t)Nm * d.memRB : nullptr,
+                  3 * D, S > 1 ? d.kvout + (size_t)d.L * S + (size_t)l * S : nullptr, Rs, (size_t)R, D, D, s);
+}
+// K|V rows the cross attention of layer l reads: the memory itself ('kv') or a projection of it into scratch
+static int kv_source(Decode& d, int l, const void** kptr) {
+    must3r_hip_ctx* c = d.c; hipStream_t s = d.s;
+    const int D = d.D, rows = (int)d.kvs_rows1;
+    if (d.mode == MUST3R_MEM_KV) { *kptr = d.A->mem[l]; return 0; }
+    const std::vector<Param*>& LP = c->dec_tab[l];
+    const void* wk;
+    M3R_OK(w16p(c, *LP[LF_PKVW], d.dt, &wk, s));
+    for (int b = 0; b < d.S; ++b) {
+        const uint16_t* src = reinterpret_cast<const uint16_t*>(d.A->mem[l]) + (size_t)b * d.mem_stride * D;
+        if (d.mode == MUST3R_MEM_RAW) {  // y_ = norm_y(y) on the stored tokens (layers.py:92)
+            LnArgs la = lnargs(nullptr, nullptr, LP[LF_NYW]->d, LP[LF_NYB]->d, d.ytmp, nullptr, nullptr, nullptr, rows, D, 1e-6f);
+            la.x16 = src;
+            M3R_OK(layernorm_a(c, d.dt, la, s));
+            src = d.ytmp;
+        }
+        M3R_OK(gemm(c, d.dt, EPI_STORE16, gargs(src, wk, LP[LF_PKVB]->d, d.kvs + (size_t)b * rows * 2 * D, rows, 2 * D, D, D, 2 * D), s));
+    }
+    *kptr = d.kvs;
+    if (d.a8) M3R_OK(quant8(c, d.dt, d.kvs, 2 * D, d.kvs8, D, nullptr, 0, (size_t)d.kvs_rows, D, 0, s));   // K -> e4m3 (V is read from kvs)
+    return 0;
+}
+
+// context-parallel cross attention of layer l: this rank's keys -> ONE partial in its slot (fp32 un-normalised, or 16-bit normalised with
+// must3r_hip_cp::partial16); all-gather of the slots (the caller's collective); merge of the world's partials into a16
+static int cross_attention_cp(Decode& d, int l, AttnArgs& aa) {
+    must3r_hip_ctx* c = d.c; hipStream_t s = d.s; const must3r_hip_cp* cp = d.cp;
+    const int R = d.R, p16 = cp->partial16 ? 1 : 0;
+    const char* err = "";
+    char* const slot0 = reinterpret_cast<char*>(cp->slots);
+    const size_t o_bytes = (size_t)R * d.D * (p16 ? 2 : 4);
+    float* const my_o = reinterpret_cast<float*>(slot0 + (size_t)cp->rank * cp->slot_bytes);
+    float* const my_ml = reinterpret_cast<float*>(slot0 + (size_t)cp->rank * cp->slot_bytes + o_bytes);
+    if (d.Nm > 0) {
+        {
+            ProfScope ps(c, s, PC_ATTN_CA, d.ca_flops);
+            if (launch_attention_phase(d.dt, aa, 1, s, &err)) return fail("%s", err);
+            ps.kernel(attention_last_kernel(), "/cross");
+        }
+        ProfScope ps(c, s, PC_ATTN_COMBINE, 0.0);
+        aa.total_q_rows = R;
+        if (launch_attention_partial_merge(d.dt, aa, my_o, my_ml, p16, s, &err)) return fail("%s", err);
+    } else {
+        ProfScope ps(c, s, PC_ATTN_COMBINE, 0.0);
+        if (launch_attention_partial_empty(my_o, my_ml, R, d.Hh, p16, s, &err)) return fail("%s", err);
+    }
+    if (cp->exchange(cp->user, l, cp->slots, cp->slot_bytes, cp->world, cp->rank, d.stream))
+        return fail("decode: the context-parallel exchange of layer %d failed", l);
+    ProfScope ps(c, s, PC_ATTN_COMBINE, 0.0);
+    aa.total_q_rows = R;
+    if (launch_attention_partial_final(d.dt, aa, reinterpret_cast<const float*>(slot0), reinterpret_cast<const float*>(slot0 + o_bytes),
+                                       (long long)(cp->slot_bytes / (p16 ? 2 : 4)), (long long)(cp->slot_bytes / 4), cp->world, p16, s, &err)) return fail("%s", err);
+    return 0;
+}
+
+// x += proj(attention(projq(norm2(x)), K|V of the memory))  (layers.py:92-97; attention.py:139-149)
+static int cross_attention_sublayer(Decode& d, int l) {
+    must3r_hip_ctx* c = d.c; hipStream_t s = d.s; const DType dt = d.dt;
+    const BlockRows& b = d.b;
+    const std::vector<Param*>& LP = c->dec_tab[l];
+    const int R = d.R, D = d.D;
+    const bool folded = d.fold.on();
+    const void* w;
+    if (!folded) M3R_OK(layernorm_a(c, dt, lnargs(b.x, nullptr, LP[LF_N2W]->d, LP[LF_N2B]->d, b.h16, nullptr, nullptr, nullptr, R, D, 1e-6f), s));
+    M3R_OK(w16p(c, *LP[folded ? LF_PQLN_W : LF_PQW], dt, &w, s));
+    GemmArgs gq = gargs(b.h16, w, LP[LF_PQB]->d, d.q16, R, D, D, D, D);
+    if (folded) d.fold.in(gq, LP[LF_PQLN_S], LP[LF_PQLN_C]);
+    gq.out_scale = kQScale; gq.scale_cols = D;
+    M3R_OK(gemm(c, dt, EPI_STORE16, gq, s));
+    const void* mk = nullptr;
+    M3R_OK(kv_source(d, l, &mk));
+    AttnArgs aa;
+    memset(&aa, 0, sizeof(aa));
+    aa.Q = d.q16; aa.K = mk; aa.V = reinterpret_cast<const uint16_t*>(mk) + D; aa.O = b.a16;
+    aa.ldq = D; aa.ldk = aa.ldv = 2 * D; aa.ldo = D; aa.heads = d.Hh;
+    if (d.a8) {   // e4m3 q and K; 'kv' memory rows are [K e4m3 (D bytes) | V 16-bit]: ldk in bytes, ldv in 16-bit elements
+        M3R_OK(quant8(c, dt, d.q16, D, b.q8, D, nullptr, 0, (size_t)R, D, 0, s));
+        aa.Q = b.q8; aa.fp8 = 1;
+        if (d.mode == MUST3R_MEM_KV) { aa.ldk = 3 * D; aa.ldv = 3 * D / 2; aa.V = reinterpret_cast<const char*>(mk) + D; }
+        else { aa.K = d.kvs8; aa.ldk = D; }   // per-call projection: K from its e4m3 copy, V from the 16-bit scratch rows
+    }
+    aa.max_nk = d.max_nk_ca;
+    aa.views = d.ca_views; aa.nviews = d.total_views; aa.max_nq = d.max_n; aa.scale = 0.125f; aa.q_prescaled = 1;
+    if (d.total_views == 1) { aa.view0_inline = 1; aa.view0 = d.tab[d.total_views]; }
+    if (d.ca_split > 1) {
+        aa.nsplit = d.ca_split; aa.total_q_rows = R; aa.dense_rows = 1;
+        aa.part_o = reinterpret_cast<float*>(d.split_ws);
+        aa.part_ml = aa.part_o + (size_t)d.ca_split * R * D;
+    }
+    if (d.cp) M3R_OK(cross_attention_cp(d, l, aa));
+    else M3R_OK(attention(c, dt, aa, d.ca_flops, PC_ATTN_CA, s));
+    M3R_OK(w16p(c, *LP[LF_CPW], dt, &w, s));
+    GemmArgs gp = gargs(b.a16, w, LP[LF_CPB]->d, b.x, R, D, D, D, D);
+    if (folded) d.fold.out(gp, nullptr);
+    return gemm(c, dt, EPI_RESID_F32, gp, s);
+}
+
+// prediction head in split precision (fp32-equivalent; decoder.py:149-156 runs it in fp32):
+//     y = LN(x); out = y_hi W_hi + y_lo W_hi + y_hi W_lo + b, pixel-shuffled to [n,H,W,7]
+// (Measured and rejected in r02: forking this head onto a second stream so that it overlaps the feedback / memory-write chain that ends
+// an update call -- the two chains are independent -- costs 2.5 ms per scene instead of saving 0.5: the head's blocks take CUs from
+// the latency-critical chain.  273 vs 282 views/s, interleaved runs on one box.)
+static int decode_head(Decode& d) {
+    must3r_hip_ctx* c = d.c; const must3r_hip_decode_args* A = d.A;
+    const int S = d.S, R = d.R, D = d.D, OUT = c->cfg.patch_size * c->cfg.patch_size * 7;
+    M3R_OK(head_layernorm(c, d.dt, d.b.x, p32(c, "decoder.norm_dec.weight"), p32(c, "decoder.norm_dec.bias"), d.hcat,
+                          A->feats ? A->feats + (size_t)(d.L - 1) * R * D : nullptr, R, D, 1e-6f, d.s));
+    const void* wcat;
+    M3R_OK(w3(c, "decoder.head_dec.proj_ps.weight", d.dt, &wcat, d.s));
+    for (int b = 0; b < (d.one_block ? 1 : S); ++b)
+        for (int gi = 0; gi < A->n_groups; ++gi) {
+            const must3r_hip_group& G = A->groups[gi];
+            const int rg = G.n_views * G.n_tokens;                       // rows of this group per scene
+            const int Rg = d.one_block ? S * rg : rg;                    // one group: all scenes in one launch ([S, n, H, W, 7] is contiguous)
+            const size_t scene_elems = (size_t)G.n_views * G.H * G.W * 7;
+            const size_t scene_stride = G.pointmaps_scene_stride > 0 ? (size_t)G.pointmaps_scene_stride : scene_elems;
+            const bool skip = d.one_block && scene_stride != scene_elems;
+            M3R_OK(head_linear(c, d.dt, d.hcat + ((size_t)b * d.Rs + d.grow0[gi]) * 3 * D, wcat, p32(c, "decoder.head_dec.proj_ps.bias"),
+                               G.pointmaps + (size_t)b * scene_stride, Rg, D, OUT, G.n_tokens, G.W / 16, G.H, G.W, skip ? G.n_views : 0,
+                               skip ? (long long)(scene_stride - scene_elems) : 0, d.s));
+        }
+    return 0;
+}
+
+// the end of an update call: feedback, then the stored memory
+static int decode_feedback_memory(Decode& d) {
+    must3r_hip_ctx* c = d.c; hipStream_t s = d.s; const DType dt = d.dt;
+    const int S = d.S, Rs = d.Rs, R = d.R, D = d.D, L = d.L;
+    uint16_t* const h16 = d.b.h16;
+    const void* w;
+    // --- feedback (feedback_mechanism.py:39-53): offset = layer(LN_1e-5(new_mem[L-1])), added to layers 0..L-2;
+    //     layer = Mlp ('single_mlp'), Linear ('single_linear') or nothing (feedback_type None: no offset)
+    const bool fb_mlp = is_loaded(c, "decoder.feedback_layer.fc1.weight");
+    const bool fb_lin = !fb_mlp && is_loaded(c, "decoder.feedback_layer.weight");
+    float* const off32 = (fb_mlp || fb_lin) ? d.off32 : nullptr;
+    if (fb_mlp || fb_lin)
+        M3R_OK(layernorm_a(c, dt, lnargs(d.newmem + (size_t)(L - 1) * R * D, nullptr, p32(c, "decoder.feedback_norm.weight"),
+                         p32(c, "decoder.feedback_norm.bias"), h16, nullptr, nullptr, nullptr, R, D, 1e-5f), s));
+    if (fb_mlp) {
+        int ws_fb;
+        M3R_OK(wmlp(c, c->params.at("decoder.feedback_layer.fc1.weight"), dt, &w, &ws_fb, s));
+        M3R_OK(gemm(c, dt, EPI_STORE16_GELU, gargs(h16, w, p32(c, "decoder.feedback_layer.fc1.bias"), d.b.g16, R, 4 * D, D, D, 4 * D), s, ws_fb));
+        M3R_OK(wmlp(c, c->params.at("decoder.feedback_layer.fc2.weight"), dt, &w, &ws_fb, s));
+        M3R_OK(gemm(c, dt, EPI_F32, gargs(d.b.g16, w, p32(c, "decoder.feedback_layer.fc2.bias"), off32, R, D, 4 * D, 4 * D, D), s, ws_fb));
+    } else if (fb_lin) {
+        M3R_OK(w16(c, "decoder.feedback_layer.weight", dt, &w, s));
+        M3R_OK(gemm(c, dt, EPI_F32, gargs(h16, w, p32(c, "decoder.feedback_layer.bias"), off32, R, D, D, D, D), s));
+    }
+    // --- stored memory = prepare_y(new_mem + offset) (decoder.py:236-239 / :327-330)
+    if (d.mode != MUST3R_MEM_KV) {
+        for (int l = 0; l < L; ++l)
+            M3R_OK(kv_project(d, l, d.newmem + (size_t)l * R * D, l < L - 1 ? off32 : nullptr, nullptr));
+        return 0;
+    }
+    // the L projections are independent: ONE grouped LayerNorm over [L*R, D] (per-layer affine, offset on layers
+    // < L-1) and ONE grouped GEMM writing each layer's K|V rows into its own memory buffer
+    LnArgs la = lnargs(d.newmem, off32, p32(c, "decoder.norm_y_all.weight"), p32(c, "decoder.norm_y_all.bias"), d.yall, nullptr,
+                       nullptr, nullptr, L * R, D, 1e-6f);
+    la.rows_per_group = R; la.add_groups = L - 1;
+    M3R_OK(layernorm_a(c, dt, la, s));
+    // fp8 memory: the GEMM writes the 16-bit staging rows [L][S][Rs][2D], one grouped quantisation scatters them into the
+    // layers' memory rows.  Problem g = l * S + b: rows of scene b, weights of layer l = g / S.
+    const void* wk;
+    M3R_OK(w16(c, "decoder.projkv_all.weight", dt, &wk, s));
+    GemmArgs gk = gargs(d.yall, wk, p32(c, "decoder.projkv_all.bias"), nullptr, Rs, 2 * D, D, D, 2 * D);
+    gk.batch = L * S; gk.wdiv = S; gk.strideA = (long long)Rs * D; gk.strideW = (long long)2 * D * D * (c->wsplit == 2 ? 2 : 1);
+    gk.strideB = 2 * D; gk.out_table = d.kvout;
+    M3R_OK(gemm(c, dt, EPI_STORE16, gk, s));
+    if (d.a8) M3R_OK(quant8(c, dt, d.kv16, 2 * D, nullptr, 3 * D, d.kvout + (size_t)L * S, Rs, (size_t)L * R, D, D, s));
+    return 0;
+}
+
+static int decode_impl(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void* stream) {
+    DeviceGuard dev_guard(c->device);
+    if (c->dec_tab.empty()) build_layer_tables(c, true);
+    Decode d; d.c = c; d.A = A; d.stream = stream; d.s = reinterpret_cast<hipStream_t>(stream);
+    decode_plan(d);
+    M3R_OK(decode_workspace(d));
+    M3R_OK(decode_tables(d));
+    M3R_OK(decode_embed(d));
+    const size_t RD = (size_t)d.R * d.D;
+    for (int l = 0; l < d.L; ++l) {
+        const std::vector<Param*>& LP = c->dec_tab[l];
+        if (d.need_pre_kv) M3R_OK(kv_project(d, l, d.b.x, nullptr, nullptr));
+        // LN fold: norm1 is folded in every block but block 0 (M3R_LNFOLD=2: there too); its kernel leaves the memorised input of the block and, under the
+        // one-view fold, the row means; fc2 leaves the next block's rows (+ their memorised copy, decoder.py:304-305)
+        const bool fq = d.lnf_all || (d.fold.on() && l > 0);
+        M3R_OK(self_attention_sublayer(c, d.dt, LP, d.b, d.sv, d.fold, fq, d.update ? d.newmem + l * RD : nullptr, d.lnf ? d.fold.shift : nullptr, d.s));
+        M3R_OK(cross_attention_sublayer(d, l));
+        M3R_OK(mlp_sublayer(c, d.dt, LP, LF_N3W, d.b, d.fold, d.fold.on() && l + 1 < d.L, d.update ? d.newmem + (l + 1) * RD : nullptr, d.s));
+        if (A->feats && l < d.L - 1)   // return_feats: the residual stream after block l (decoder.py:321)
+            HIP_OK(hipMemcpyAsync(A->feats + l * RD, d.b.x, RD * sizeof(float), hipMemcpyDeviceToDevice, d.s));
+    }
+    M3R_OK(decode_head(d));
+    return d.update ? decode_feedback_memory(d) : 0;
 }
 
 // MUSt3R.forward / forward_list (decoder.py:158-350).  Validates everything the launches rely on (so that a non-Python caller
@@ -1345,8 +1344,7 @@ extern "C" size_t must3r_hip_cp_slot_bytes16(const must3r_hip_ctx* c, int rows) 
 extern "C" int must3r_hip_decode(must3r_hip_ctx* c, const must3r_hip_decode_args* A, void* stream) {
     if (!c || !A || !A->groups || !A->mem) return fail("decode: null argument");
     if (!c->fin_dec) return fail("decode: decoder weights not finalized");
-    const int adt = A->dtype & ~MUST3R_ATTN_FP8;
-    if (adt != MUST3R_BF16 && adt != MUST3R_F16 && adt != MUST3R_F16_W2 && adt != MUST3R_F16_WA) return fail("decode: bad dtype %d", A->dtype);
+    if (!set_mode(c, A->dtype)) return fail("decode: bad dtype %d", A->dtype);
     if ((A->dtype & MUST3R_ATTN_FP8) && !kAttnFp8Built) return fail("decode: MUST3R_ATTN_FP8 is an experiment build (make EXTRA=-DM3R_ATTN_FP8): measured outside the 1e-3 target for +0.4 %%");
     if (A->mem_mode != MUST3R_MEM_KV && A->mem_mode != MUST3R_MEM_NORM_Y && A->mem_mode != MUST3R_MEM_RAW)
         return fail("decode: bad mem_mode %d", A->mem_mode);

@@ -32,12 +32,12 @@ from ._train_common import attention_precision, current_attention_precision   # 
 
 
 def self_views(n_scenes, views_per_scene, n):
-    """The decoder's self-attention table (model.hip:1004): view j of scene b attends its own ``n`` tokens at rows ``(b V + j) n``."""
+    """The decoder's self-attention table (model.hip, decode_tables): view j of scene b attends its own ``n`` tokens at rows ``(b V + j) n``."""
     return [[(b * views_per_scene + j) * n, n, (b * views_per_scene + j) * n, n, 0, 0] for b in range(n_scenes) for j in range(views_per_scene)]
 
 
 def memory_views(n_scenes, views_per_scene, n, Nm, mask=True, causal=False):
-    """The decoder's cross-attention table of a memory update (model.hip:1005-1015): scene b's keys are ``Nm`` memory rows followed by the ``V n`` new
+    """The decoder's cross-attention table of a memory update (model.hip, decode_tables): scene b's keys are ``Nm`` memory rows followed by the ``V n`` new
     tokens, at rows ``b (Nm + V n)``; the queries are the scene's views at rows ``(b V + j) n``.  ``mask``: view j does not attend its own tokens (skip
     ``[Nm + j n, Nm + (j + 1) n)``); ``causal`` (with ``mask``): view j attends the memory and the views before it, a prefix of ``Nm + j n`` rows -- with
     an empty memory view 0 attends view 1's tokens instead, rows ``[n, 2 n)`` behind an excluded ``[0, n)``.  A lone view attends the memory alone."""
