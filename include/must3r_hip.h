@@ -1234,6 +1234,72 @@ typedef struct must3r_hip_augment_depth_args {
 size_t must3r_hip_augment_depth_scratch_bytes(int V);
 int must3r_hip_augment_depth(const must3r_hip_augment_depth_args* a);
 
+/* ---- baseline JPEG decoding (ABI 21, additive; csrc/jpeg_parse.hpp, csrc/jpeg_entropy.hpp, csrc/jpeg.hip) -------------------------
+ * From the bytes of a file to the MUST3R_IMG_U8_HWC pixels the resampler takes, bit-equal to libjpeg-turbo's default decode (accurate integer IDCT, fancy
+ * upsampling, 16-bit YCbCr -> RGB) as Pillow's open().convert("RGB") runs it.  Accepted: SOF0 / SOF1 with 8-bit samples, Huffman coding, one interleaved
+ * scan, 8-bit quantisation tables, one component or three YCbCr components with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, with or without restart
+ * intervals.  Everything else the parser reports as unsupported with a reason, before anything is launched.
+ *
+ * The parser runs on the host and needs no GPU.  It never trusts a length field: every read is checked against the buffer.  The info record is plain data
+ * (no pointers): geometry, the quantisation table of each component (zig-zag order, as in the file), the four Huffman tables in the form the kernels read
+ * (a 9-bit lookahead and the canonical arrays), the restart interval and the byte range of the entropy-coded data.  `seg_offsets` receives the byte offset
+ * (from the start of the file) of every restart segment's first byte, n_segments entries; segment s ends two bytes (its RSTn marker) before segment s + 1
+ * starts, the last at scan_offset + scan_bytes. */
+#define MUST3R_JPEG_SUBSEQ_BYTES 128   /* bytes of one subsequence of the parallel entropy decode */
+#define MUST3R_JPEG_PATH_FAST 0        /* must3r_hip_jpeg_decode, flags: the subsequence scheme verified */
+#define MUST3R_JPEG_PATH_SEQUENTIAL 1  /* the verification failed: one thread per restart segment decoded the image again */
+typedef struct must3r_hip_jpeg_huff {
+    uint16_t look[512];     /* by the next 9 bits: (code length << 8) | symbol; 0: the code is longer than 9 bits */
+    int32_t  maxcode[18];   /* [l], l = 1 ... 16: the largest code of length l, -1 without one; [17]: a sentinel above every code */
+    int32_t  valoff[18];    /* [l]: index into vals of the first code of length l, minus that code */
+    uint8_t  vals[256];
+} must3r_hip_jpeg_huff;
+typedef struct must3r_hip_jpeg_info {
+    int32_t width, height, components;        /* components: 1 (grey) or 3 (YCbCr) */
+    int32_t hs, vs;                           /* luma sampling factors (1x1 for grey); chroma is 1x1 */
+    int32_t mcus_x, mcus_y, blocks_per_mcu;   /* the scan: mcus_x * mcus_y MCUs of hs * vs luma blocks, then Cb, then Cr */
+    int32_t n_blocks;                         /* mcus_x * mcus_y * blocks_per_mcu */
+    int32_t restart_interval;                 /* MCUs per restart segment; 0: one segment */
+    int32_t n_segments;
+    int32_t reserved;
+    int64_t scan_offset, scan_bytes;          /* the entropy-coded data, from the first byte after SOS up to the marker that ends the scan */
+    int32_t comp_dc[3], comp_ac[3];           /* per component: which of dc[2] / ac[2] */
+    uint16_t quant[3][64];                    /* per component, zig-zag order */
+    uint8_t  natural[64];                     /* zig-zag index -> row-major index */
+    must3r_hip_jpeg_huff dc[2], ac[2];
+} must3r_hip_jpeg_info;
+/* 0: accepted, *info is filled (and seg_offsets, when seg_capacity >= n_segments; with a smaller capacity only info is filled: query n_segments first).
+ * 1: not accepted; `reason` (when not NULL, reason_capacity bytes) holds why as a C string.  No other outcome, no GPU call, no allocation. */
+int must3r_hip_jpeg_parse(const void* data, size_t data_bytes, must3r_hip_jpeg_info* info, uint32_t* seg_offsets, size_t seg_capacity,
+                          char* reason, size_t reason_capacity);
+typedef struct must3r_hip_jpeg_image {
+    const must3r_hip_jpeg_info* info;   /* HOST: as must3r_hip_jpeg_parse filled it */
+    const uint32_t* seg_offsets;        /* HOST [info->n_segments] */
+    const void* data;                   /* DEVICE: the whole file, data_bytes bytes, 16-byte aligned */
+    size_t data_bytes;
+    void*  out;                         /* DEVICE: uint8 [height][width][3], rows of out_row_stride bytes (>= 3 * width), 16-byte aligned */
+    int64_t out_row_stride;
+} must3r_hip_jpeg_image;
+typedef struct must3r_hip_jpeg_batch {
+    const must3r_hip_jpeg_image* images;   /* HOST [n_images] */
+    int32_t n_images, reserved;
+    int32_t* flags;          /* DEVICE [n_images], written: MUST3R_JPEG_PATH_FAST or MUST3R_JPEG_PATH_SEQUENTIAL per image */
+    void*  scratch;          /* DEVICE, 256-byte aligned */
+    size_t scratch_bytes;    /* >= must3r_hip_jpeg_scratch_bytes of the same images */
+    void*  stream;           /* hipStream_t: every copy, memset and launch of the call goes there; nothing is read back */
+} must3r_hip_jpeg_batch;
+/* device bytes of scratch for one decode call of these images (0 on invalid descriptors): the descriptor tables, the subsequence states, the int16
+ * coefficients [n_blocks][64] and the component planes padded to whole MCUs.  Only info and seg_offsets of each image are read. */
+size_t must3r_hip_jpeg_scratch_bytes(const must3r_hip_jpeg_image* images, int n_images);
+/* Decodes the batch.  Entropy decoding does not depend on restart markers: every thread decodes one subsequence of MUST3R_JPEG_SUBSEQ_BYTES bytes of a
+ * restart segment from an assumed state, then again from its predecessor's exit state while the states change (a bounded number of rounds); an exclusive
+ * scan of the completed-block counts places every subsequence's coefficients.  The write pass checks that every subsequence's recorded exit came from its
+ * predecessor's: by induction from the segment's first bit the result then IS the sequential decode.  An image that fails the check (a periodic stream
+ * can defeat the synchronisation for ever) is decoded again by one thread per segment, in a launch predicated on the image's device flag.  Then DC
+ * prediction (a segmented scan), dequantisation + IDCT, and upsampling + colour conversion.  The stream is assumed intact: on a damaged one every access stays
+ * in bounds and the pixels are unspecified. */
+int must3r_hip_jpeg_decode(const must3r_hip_jpeg_batch* batch);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

@@ -296,6 +296,36 @@ class AugmentDepthArgs(C.Structure):
                 ("V", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("depth_u16", C.c_int32), ("stream", C.c_void_p)]
 
 
+JPEG_SUBSEQ_BYTES = 128   # MUST3R_JPEG_SUBSEQ_BYTES
+JPEG_PATH_FAST, JPEG_PATH_SEQUENTIAL = 0, 1   # MUST3R_JPEG_PATH_*
+
+
+class JpegHuff(C.Structure):
+    """must3r_hip_jpeg_huff: one Huffman table as the kernels read it (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("look", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 18), ("vals", C.c_uint8 * 256)]
+
+
+class JpegInfo(C.Structure):
+    """must3r_hip_jpeg_info: what must3r_hip_jpeg_parse takes the marker segments of one file to (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("blocks_per_mcu", C.c_int32), ("n_blocks", C.c_int32),
+                ("restart_interval", C.c_int32), ("n_segments", C.c_int32), ("reserved", C.c_int32),
+                ("scan_offset", C.c_int64), ("scan_bytes", C.c_int64), ("comp_dc", C.c_int32 * 3), ("comp_ac", C.c_int32 * 3),
+                ("quant", (C.c_uint16 * 64) * 3), ("natural", C.c_uint8 * 64), ("dc", JpegHuff * 2), ("ac", JpegHuff * 2)]
+
+
+class JpegImage(C.Structure):
+    """must3r_hip_jpeg_image: one image of a decode call -- HOST info and segment offsets, DEVICE file bytes and output (include/must3r_hip.h, ABI 21)."""
+    _fields_ = [("info", C.POINTER(JpegInfo)), ("seg_offsets", C.POINTER(C.c_uint32)), ("data", C.c_void_p), ("data_bytes", C.c_size_t),
+                ("out", C.c_void_p), ("out_row_stride", C.c_int64)]
+
+
+class JpegBatch(C.Structure):
+    """must3r_hip_jpeg_batch: the HOST image table, the DEVICE path flags, the scratch and the stream of one decode call (include/must3r_hip.h, ABI 21)."""
+    _fields_ = [("images", C.POINTER(JpegImage)), ("n_images", C.c_int32), ("reserved", C.c_int32), ("flags", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -421,6 +451,9 @@ PROTOTYPES = {
     "must3r_hip_augment_color": (i32, [P(AugmentColorArgs)]),
     "must3r_hip_augment_depth_scratch_bytes": (sz, [i32]),
     "must3r_hip_augment_depth": (i32, [P(AugmentDepthArgs)]),
+    "must3r_hip_jpeg_parse": (i32, [vp, sz, P(JpegInfo), P(C.c_uint32), sz, vp, sz]),
+    "must3r_hip_jpeg_scratch_bytes": (sz, [P(JpegImage), i32]),
+    "must3r_hip_jpeg_decode": (i32, [P(JpegBatch)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

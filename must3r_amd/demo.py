@@ -87,7 +87,7 @@ def memory_schedule(nimgs, num_mem_images, init_num_images, batch_num_views, ren
 
 
 def must3r_inference(model, retrieval, device, image_size, amp, filelist, num_mem_images, max_bs, init_num_images, batch_num_views,
-                     render_once, is_sequence, viser_server=None, num_refinements_iterations=0, verbose=True):
+                     render_once, is_sequence, viser_server=None, num_refinements_iterations=0, verbose=True, gpu_decode=False):
     """demo/inference.py:109-242 -> ``SceneState``.  ``retrieval``: None, the retrieval checkpoint's path (as in the reference), or a
     ``MUSt3R_Retriever`` already built (a caller running many scenes loads the codebook once)."""
     dtype = get_dtype(amp)
@@ -102,7 +102,7 @@ def must3r_inference(model, retrieval, device, image_size, amp, filelist, num_me
     if verbose:
         print("loading images")
     time_start = datetime.datetime.now()
-    views = load_images(filelist, size=image_size, patch_size=encoder.patch_size, verbose=verbose, device=device)
+    views = load_images(filelist, size=image_size, patch_size=encoder.patch_size, verbose=verbose, device=device, decode="gpu" if gpu_decode else "pil")
     if verbose:
         print(f"loaded in {datetime.datetime.now() - time_start}")
         print("running inference")
@@ -188,7 +188,7 @@ def slam_update_scene_state(subsample, min_conf_keyframe, res, scene_state):
 def must3r_inference_video(model, device, image_size, amp, filelist, max_bs, init_num_images, batch_num_views, viser_server=None,
                            num_refinements_iterations=0, local_context_size: int = 25,
                            is_keyframe_function=lambda id, res, scene_state: (id % 3 == 0), scene_state=None,
-                           scene_state_update_function=lambda res, scene_state: scene_state, verbose=True):
+                           scene_state_update_function=lambda res, scene_state: scene_state, verbose=True, gpu_decode=False):
     """demo/inference.py:244-331 -> ``SceneState``: the frames in file order, ``init_num_images`` of them first, then
     ``batch_num_views`` at a time, through ``inference_video_multi_ar`` with the keyframe and map callbacks."""
     dtype = get_dtype(amp)
@@ -203,7 +203,7 @@ def must3r_inference_video(model, device, image_size, amp, filelist, max_bs, ini
     if verbose:
         print("loading images")
     time_start = datetime.datetime.now()
-    views = load_images(filelist, size=image_size, patch_size=encoder.patch_size, verbose=verbose, device=device)
+    views = load_images(filelist, size=image_size, patch_size=encoder.patch_size, verbose=verbose, device=device, decode="gpu" if gpu_decode else "pil")
     if verbose:
         print(f"loaded in {datetime.datetime.now() - time_start}")
         print("running inference")
@@ -247,10 +247,11 @@ def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrie
                             execution_mode, num_mem_images, render_once, vidseq_local_context_size, keyframe_interval,
                             slam_local_context_size, subsample, min_conf_keyframe, keyframe_overlap_thr, overlap_percentile,
                             min_conf_thr, as_pointcloud, transparent_cams, local_pointmaps, cam_size, camera_conf_thr=0.0,
-                            loaded_files=""):
+                            loaded_files="", gpu_decode=False):
     """demo/gradio.py:160-217 -> ``(SceneState, None)``: the four execution modes with the reference's arguments.  The output
     parameters are accepted and unused, and ``should_save_glb=True`` is refused: export the returned scene with
-    ``get_3D_model_from_scene`` or ``export_scene_thresholds``, as the reference's get_reconstruction.py does."""
+    ``get_3D_model_from_scene`` or ``export_scene_thresholds``, as the reference's get_reconstruction.py does.  ``gpu_decode=True`` decodes the
+    baseline JPEGs of the file list on the device (``load_images(..., decode="gpu")``, must3r_amd/jpeg.py); the default stays on Pillow."""
     if should_save_glb:
         raise NotImplementedError("get_reconstructed_scene does not write the GLB / PLY file itself: call it with should_save_glb=False "
                                   "and pass the returned SceneState to get_3D_model_from_scene or export_scene_thresholds")
@@ -261,6 +262,7 @@ def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrie
     else:
         return None, None
 
+    decode = dict(gpu_decode=True) if gpu_decode else {}   # without the switch the two drivers are called with the reference's arguments alone
     if execution_mode == "vidseq" or execution_mode == "vidslam":
         if execution_mode == "vidseq":
             local_context_size = vidseq_local_context_size
@@ -282,12 +284,12 @@ def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrie
                                        viser_server=viser_server, num_refinements_iterations=num_refinements_iterations,
                                        local_context_size=local_context_size, is_keyframe_function=is_keyframe_function,
                                        scene_state=scene_state, scene_state_update_function=scene_state_update_function,
-                                       verbose=verbose)
+                                       verbose=verbose, **decode)
     else:
         is_sequence = execution_mode == "linseq"
         scene = must3r_inference(model, retrieval, device, image_size, amp, image_list, num_mem_images, max_bs, init_num_images=2,
                                  batch_num_views=1, render_once=render_once, is_sequence=is_sequence, viser_server=viser_server,
-                                 num_refinements_iterations=num_refinements_iterations, verbose=verbose)
+                                 num_refinements_iterations=num_refinements_iterations, verbose=verbose, **decode)
     return scene, None
 
 

@@ -42,8 +42,16 @@ def get_args_parser():
     return p
 
 
+def get_cli_parser():
+    """``get_args_parser()`` -- the reference's arguments, kept equal to them -- plus this project's own switches"""
+    p = get_args_parser()
+    p.add_argument("--gpu_decode", action="store_true", default=False,
+                   help="decode baseline JPEGs on the GPU (must3r_amd.jpeg); every other file, and the default, go through Pillow")
+    return p
+
+
 def main(argv=None):
-    args = get_args_parser().parse_args(argv)
+    args = get_cli_parser().parse_args(argv)
     images = sorted(os.path.join(args.image_dir, f) for f in os.listdir(args.image_dir) if os.path.isfile(os.path.join(args.image_dir, f)))
     os.makedirs(args.output, exist_ok=True)
     if args.execution_mode == "retrieval" and args.retrieval is None:
@@ -59,7 +67,7 @@ def main(argv=None):
         num_refinements_iterations=args.num_refinements_iterations, execution_mode=args.execution_mode,
         vidseq_local_context_size=args.local_context_size, keyframe_interval=args.keyframe_interval,
         slam_local_context_size=args.local_context_size, subsample=args.subsample, min_conf_keyframe=args.min_conf_keyframe,
-        keyframe_overlap_thr=args.keyframe_overlap_thr, overlap_percentile=args.overlap_percentile)
+        keyframe_overlap_thr=args.keyframe_overlap_thr, overlap_percentile=args.overlap_percentile, gpu_decode=args.gpu_decode)
     # the reference passes cam_size alone to its export calls: camera_conf_thr stays at its default there
     paths = export_scene_thresholds(args.output, scene, thresholds, file_type=args.file_type, as_pointcloud=True, transparent_cams=False,
                                     cam_size=args.cam_size, verbose=True)

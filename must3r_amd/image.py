@@ -10,8 +10,8 @@ Same names and contracts as the reference, CUDA tensors out, no CPU fallback:
   BICUBIC) + crop + ImgNorm, bit-exact with Pillow, for one frame or a [B, H, W, 3] uint8 batch in one call.
 
 ImgNorm (dust3r: ToTensor then Normalize(0.5, 0.5)) maps a byte u to the fp32 value (u / 255 - 0.5) / 0.5; the library applies it
-through a 256-entry table built on the host (include/must3r_hip.h).  JPEG / PNG decoding and palette / RGBA -> RGB conversion stay
-on the host in PIL.
+through a 256-entry table built on the host (include/must3r_hip.h).  PNG decoding and palette / RGBA -> RGB conversion stay on the host
+in PIL, and so does JPEG decoding by default; ``load_images(..., decode="gpu")`` decodes baseline JPEGs on the device (must3r_amd/jpeg.py).
 """
 import ctypes as C
 
@@ -172,14 +172,20 @@ def _upload_u8(arr, device):
     return host.to(device, non_blocking=True)
 
 
-def load_images(folder_content, size, patch_size=16, verbose=True, device="cuda"):
+def load_images(folder_content, size, patch_size=16, verbose=True, device="cuda", decode="pil"):
     """must3r/demo/inference.py:63-76 -> [dict(img=fp32 [3, h, w] CUDA, true_shape=np.int32([h, w]))].  Files are decoded in order and
     resampled in chunks of about LOAD_CHUNK_BYTES of uint8 pixels, one native call per chunk (12 MP photos: 8 per call), so host
-    and device memory stay bounded however long the folder is."""
+    and device memory stay bounded however long the folder is.  ``decode="pil"`` (the default) decodes every file with Pillow on the host;
+    ``decode="gpu"`` decodes the baseline JPEGs among them on the device (must3r_amd.jpeg, bit-equal to Pillow) and hands the pixels to the
+    resampler without a host copy; what that decoder refuses still goes through Pillow."""
     import PIL.Image
+    if decode not in ("pil", "gpu"):
+        raise ValueError(f"must3r_amd.image.load_images: decode={decode!r} (\"pil\" or \"gpu\")")
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("must3r_amd.image.load_images: device must be CUDA; the HIP path has no CPU fallback")
+    if decode == "gpu":
+        return _load_images_gpu(folder_content, size, patch_size, verbose, device)
     imgs, chunk, nbytes = [], [], 0
     for path in folder_content:
         rgb = PIL.Image.open(path).convert("RGB")
@@ -196,10 +202,37 @@ def load_images(folder_content, size, patch_size=16, verbose=True, device="cuda"
     return imgs
 
 
+def _load_images_gpu(folder_content, size, patch_size, verbose, device):
+    """load_images with the JPEG decode on the device: per chunk one decode call and one resample call, the pixels never on the host"""
+    from . import jpeg
+    device = jpeg._cuda_device(device, "image.load_images")
+    imgs, preps, paths, nbytes = [], [], [], 0
+
+    def flush():
+        nonlocal preps, paths, nbytes
+        chunk = []
+        for path, (_, _, H, W), t in zip(paths, preps, jpeg._decode_prepared(preps, device)):
+            target, crop_H, crop_W, _, _ = _geometry(size, patch_size, H, W)
+            chunk.append((path, t, H, W, target, crop_H, crop_W))
+        preps, paths, nbytes = [], [], 0
+        return _load_chunk(chunk, device, verbose)
+
+    for path in folder_content:
+        preps.append(jpeg._prepare(path))
+        paths.append(path)
+        _geometry(size, patch_size, preps[-1][2], preps[-1][3])   # a size the buckets refuse is reported before anything is launched for the chunk
+        nbytes += preps[-1][2] * preps[-1][3] * 3
+        if nbytes >= LOAD_CHUNK_BYTES:
+            imgs += flush()
+    if preps:
+        imgs += flush()
+    return imgs
+
+
 def _load_chunk(items, device, verbose):
     descs, srcs, shapes, off = [], [], [], 0
     for path, arr, H, W, target, crop_H, crop_W in items:
-        src = _upload_u8(arr, device)
+        src = arr if isinstance(arr, torch.Tensor) else _upload_u8(arr, device)   # decode="gpu": the pixels are on the device already
         h, w = (H, W) if target is None else target
         top, left = _center_offsets(H, W, crop_H, crop_W)
         descs.append(_desc(src, _lib.IMG_U8_HWC, 3, H, W, W * 3, 0, (top, left, crop_H, crop_W), (h, w), (0, 0, h, w), off))
