@@ -1805,18 +1805,15 @@ static int persistent_blocks() {
     }
     return n;
 }
-// PERSIST (A/B instrument): 1 the chip-filling kernels walk their tiles in a persistent loop when the launch has more than one round, 0 (default) never.
-// Measured (profiles/r06_gemm_persist_ab.txt, one process, interleaved rounds, identical bits): x0.96 ... x1.04 per shape, x1.003 over the 16 shapes; step 526.1 (0) vs 523.6 (1) views/s.
-static int persist_mode() { return opt(OPT_PERSIST); }
 
+// persistent: GemmRoute::persistent (gemm_route.hpp, PERSIST)
 template <class T, int EPI, int WS, int BN, int NPH, int SYNC = 2>
-static int launch_256p(const GemmArgs& a_in, hipStream_t s) {
+static int launch_256p(const GemmArgs& a_in, hipStream_t s, bool persistent) {
     GemmArgs a = a_in;
     a.gm = opt(OPT_G256_GM);
     const int nbn = a.N / BN, nbm = (a.M + 255) / 256;
     const size_t lds = (size_t)2 * 4 * 128 * 64 * sizeof(T);
-    const long nwork = (long)nbm * nbn * (a.batch > 1 ? a.batch : 1);
-    if (persist_mode() != 0 && !a.fold256 && nwork > persistent_blocks() && nwork < (1l << 30)) {
+    if (persistent) {
         static bool attr_set_p = false;
         if (!attr_set_p) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256p_kernel<T, EPI, WS, BN, NPH, SYNC, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
@@ -2080,13 +2077,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 }
 
 template <class T, int EPI>
-static int launch_256s(const GemmArgs& a_in, hipStream_t s) {
+static int launch_256s(const GemmArgs& a_in, hipStream_t s, bool persistent) {
     GemmArgs a = a_in;
     a.gm = opt(OPT_G256_GM);
     const int nbn = a.N / 256, nbm = (a.M + 255) / 256;
     const size_t lds = (size_t)2 * 5 * 128 * 64 * sizeof(T);   // 163840 B: the CU's whole LDS
-    const long nwork = (long)nbm * nbn * (a.batch > 1 ? a.batch : 1);
-    if (persist_mode() != 0 && !a.fold256 && nwork > persistent_blocks() && nwork < (1l << 30)) {
+    if (persistent) {
         static bool attr_set_p = false;
         if (!attr_set_p) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256s_kernel<T, EPI, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
@@ -2260,7 +2256,6 @@ __global__ void __launch_bounds__(576) gemm48_kernel(const GemmArgs p) {
     }
 }
 
-static thread_local int g_gemm48_bk = 64;   // K-tile depth of this thread's last gemm48 launch: the two depths are two symbols of a kernel trace (pick_name48)
 template <class T, int EPI, int WS, int BK>
 static int launch_48k(const GemmArgs& a, hipStream_t s) {
     constexpr int NST = BK == 128 ? (WS == 2 ? 4 : 6) : 6;   // 4 x 36 KB (split) / 6 x 24 KB (plain) of 128-deep stages; 6 x 18 / 12 KB at 64
@@ -2274,18 +2269,13 @@ static int launch_48k(const GemmArgs& a, hipStream_t s) {
         }
         attr_set = true;
     }
-    g_gemm48_bk = BK;
     hipLaunchKernelGGL((gemm48_kernel<T, EPI, WS, NST, BK>), dim3(nbm * nbn, a.batch > 1 ? a.batch : 1), dim3(576), lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
-// M3R_BK128 (A/B instrument): 0 = 64-deep K-tiles everywhere (the r03 kernels).  Measured (profiles/r04_bk128_m768.txt): same
-// bits; fc2 (K = 3072) 17.4 -> 14.1 us plain, 19.0 -> 17.9 us split; the K = 768 launches +-0.2 us (their 12 tiles are not what they spend their
-// time on); one-scene-at-a-time 331 -> 336 views/s.  The same depth in the 64 x 64 ring kernels (2 x 128-deep stages): qkv 11.1 -> 15.1 us,
-// K|V 10.2 -> 14.4 us, fc1 13.3 -> 12.5 us, scene 326 views/s -- not kept.
-static int bk128_mode() { return opt(OPT_BK128); }
+// bk: GemmRoute::bk, the K-tile depth (gemm_route.hpp bk_48, BK128)
 template <class T, int EPI, int WS>
-static int launch_48(const GemmArgs& a, hipStream_t s) {
-    if (a.K % 128 == 0 && a.K >= 256 && bk128_mode() != 0) return launch_48k<T, EPI, WS, 128>(a, s);
+static int launch_48(const GemmArgs& a, hipStream_t s, int bk) {
+    if (bk == 128) return launch_48k<T, EPI, WS, 128>(a, s);
     return launch_48k<T, EPI, WS, 64>(a, s);
 }
 
@@ -2545,182 +2535,86 @@ static thread_local char g_gemm_pick[32] = "";
 static void pick_name(const char* fam, int epi, int ws, int bn) { snprintf(g_gemm_pick, sizeof(g_gemm_pick), "%s/e%d/w%d/n%d", fam, epi, ws, bn); }
 const char* gemm_last_kernel() { return g_gemm_pick; }
 
-// Tile selection (measured on MI355X, scripts/bench_gemm.py): two resident blocks per CU beat every larger tile that
-// leaves one (128x128 3-stage, 256x128 with 4 or 8 waves: 465-613 TF/s vs 644 TF/s on the scene's big-batch shapes).
-//   plain weights : 128x128x64, 2 stages (64 KB)  for chip-filling grids, 64x64x64 4-stage ring (64 KB) otherwise
-//   split weights : 128x64 (+64 lo) 2 stages (64 KB) / 64x64 (+64 lo) 3-stage ring (72 KB)
-// K-tile depth 32 (the BK template parameter; 3-5 resident blocks per CU) was also measured: 605-626 TF/s plain,
-// 397-419 vs 409 TF/s split -- no gain, so only BK = 64 is instantiated.
-// minimum number of big tiles for the big-tile kernel (tunable for experiments: M3R_GEMM_MIN_BIG / _MIN_BIG_SPLIT)
-static long min_big(bool split) { return split ? 384 : 192; }
-
-// Launches of at most one 64 x 64 tile per CU (M = 768: proj, fc2, projq) run it with 8 waves (4 x 2, wave tile 16 x 32), a
-// 6-8 slot LDS ring (one block per CU: the whole LDS can be prefetch depth) and the fragment reads of tile kt+1 issued
-// before the MFMAs of tile kt (PIPE).  Measured at M = 768 with split weights: proj 8.7 -> 8.1 us, fc2 23.4 -> 20.7 us.
-// What the experiments say about these launches (scripts/bench_gemm_small.py; debug builds that drop one component):
-// per K-tile DMA, LDS reads and MFMAs each cost ~0.1 us ALONE (fc2: 16.3 / 16.8 / 16.6 us with one of them removed, 5.4 us
-// with all three removed, 21 us with all) -- they add up instead of overlapping, whatever the ring depth (3 vs 6 slots:
-// same), the bytes per tile (half the lo tile: -2 %) or the wave count; with two blocks per CU (qkv, fc1) the 4-wave form
-// is as fast or faster; 64 x 32 tiles (twice the blocks, half the work each): same time per K-tile; the staggered
-// two-group structure of gemm256_kernel on the 64 x 64 tile: same (fc2 20.4-21.0 us).  The slope is 0.35 us per
-// 64-deep K-tile whatever the structure (proj 12 tiles 8.0 us, fc2 48 tiles 20.5 us); K off the power-of-two strides
-// (3008 / 3136 instead of 3072) changes nothing, so it is not L2-channel camping either.  Open.
-static bool small8(long tiles64) { return tiles64 <= 256; }
-#ifndef SMALL_WGM
-#define SMALL_WGM 4
-#endif
-#ifndef SMALL8_NST_SPLIT
-#define SMALL8_NST_SPLIT 6   // 6 x 24 KB = 144 KB: one block per CU anyway, so the whole LDS can be prefetch depth
-#endif
-#ifndef SMALL8_NST_PLAIN
-#define SMALL8_NST_PLAIN 8   // 8 x 16 KB = 128 KB
-#endif
-
-static bool use_48(const GemmArgs& a, long nb) {
-    if (a.N % 48 || a.K % 64 || a.rope_tab != nullptr) return false;
-    const long tiles = (long)((a.M + 47) / 48) * (a.N / 48) * nb;
-    return tiles <= 256 && tiles >= 192;
+// The rule that picks the kernel family lives in gemm_route.hpp (host-only, no HIP): here its two inputs are filled, and its answer is launched.
+static GemmOpts gemm_opts() {
+    const int persist = opt(OPT_PERSIST);
+    return {opt(OPT_GEMM256), opt(OPT_G256K), opt(OPT_G256P), opt(OPT_G256P_SPLIT), opt(OPT_SPARSE_256), opt(OPT_SPARSE_LO), opt(OPT_BK128), persist,
+            persist != 0 ? persistent_blocks() : 0};   // the device is asked for its CU count only when something compares with it
 }
-
-// 96 x 96 tiles: split weights, one round of 224..256 tiles (M = 768: fc1 / feedback fc1 = 256 tiles; measured 17.8 -> 13.3 us);
-static bool use_96(const GemmArgs& a, long nb) {
-    if (a.N % 96 || a.K % 64) return false;
-    const long tiles = (long)((a.M + 95) / 96) * (a.N / 96) * nb;
-    return tiles <= 256 && tiles >= 224;   // (qkv at M = 768 is 192 tiles = 75 % of the CUs: measured 12.3 us vs 11.2 us on 64 x 64 tiles)
+static GemmShape gemm_shape(DType dt, Epi epi, const GemmArgs& a) {
+    return {dt == DT_F16, epi, a.M, a.N, a.K, a.wsplit, a.batch, a.rope_tab != nullptr, a.Wlo_sp != nullptr && a.Widx_sp != nullptr, a.ln_stats != nullptr,
+            a.x16_out != nullptr || a.copy32_out != nullptr || a.stats_out != nullptr, a.fold256 != 0};
 }
+bool gemm_fold256_shape_ok(int M, int N, int K, bool split) { return gemm_fold256_shape_ok(M, N, K, split, gemm_opts()); }
 
-// M3R_GEMM256: 0 = never use the 8-wave kernel, 1 = by the fill rule below (default), 2 = whenever the shape allows it
-static int gemm256_mode() { return opt(OPT_GEMM256); }
-// the 8-wave kernel holds one block per CU: use it when its rounds over the 256 CUs are reasonably full
-static int fill256(long tiles) {   // percentage of the CU slots of its rounds that do work
-    const long rounds = (tiles + 255) / 256;
-    return (int)(tiles * 100 / (rounds * 256));
-}
-static int g256k_mode() { return opt(OPT_G256K); }
-// M3R_G256P (r05): the phase-staggered 64-deep kernel (gemm256p_kernel, two phases per K-tile, two barriers per phase) for the chip-filling launches.
-//   plain weights  (M3R_G256P, default 1): 0 never (gemm256k_kernel), 1 every epilogue but the RoPE one (its instantiation spills), measured on the
-//                  nine shapes of scripts/exp_gemm256.py: 2-6 % faster on each (profiles/r05_g256p_plain_ab.txt), 987 -> 1113 TF/s at K = 16384;
-//   split weights  (M3R_G256P_SPLIT, default 1): 0 never, 1 where its 256 x 128 tiles fill their rounds at least as well as the widest tile gemm256_kernel
-//                  would pick (decoder qkv N = 2304: 109 -> 103 us, K|V N = 1536: 72.6 -> 65.2 us; NOT the 256-wide encoder qkv 160 -> 162 us or the
-//                  192-wide decoder proj 44.7 -> 51.8 us, profiles/r05_g256p_split_ab.txt), 2 whenever the shape allows.
-// The other forms measured in r05: four phases per K-tile and one barrier per phase with group 1 lagging are template arguments of gemm256p_kernel the library does
-// not instantiate; gemm256n (one phase per K-tile), gemm256pp (persistent tiles), gemm256q (one barrier per K-tile) and gemm256w (four waves, 128 x 128 wave tiles) live
-// in scripts/probes/lab/*.inc and are compiled only with -DM3R_GEMM_LAB (scripts/probes/kloop_lab.hip).
-static int g256p_mode(bool split) { return opt(split ? OPT_G256P_SPLIT : OPT_G256P); }
-// (r04, measured and removed: two 256 x 128 blocks per CU -- the GELU launches' OCC = 2 form -- for the other split-weight epilogues, so that one
-// block's fp32 read-modify-write epilogue runs under the other's K loop: RESID proj 44.7 -> 52.1 us (dec) / 67.2 -> 68.2 us (enc), fc2 122 -> 152 us,
-// STORE16 K|V 71.9 -> 77.8 us, RoPE qkv +-1 %; nine split shapes 1246 -> 1308 us, step 497.6 -> 487.9 views/s.  profiles/r04_occ2_ab.txt.)
-// (r04, measured and removed: the same two-blocks-per-CU form for the PLAIN-weight GELU launches instead of gemm256k -- enc fc1 146.8 -> 172.8 us, dec fc1 92.6 ->
-// 105.4 us, step 495.9 -> 486.3 views/s: the 64-byte DMA rows and 256 x 128 tiles cost more than the hidden erf epilogue (~8 us of a 39 us tile) gives back.
-// profiles/r04_plain_gelu_occ2.txt.)
-// r06: does the default dispatch below send a chip-filling launch of this shape to gemm256s_kernel (split, sparse low part) / gemm256p_kernel<.., 1, 256> (plain)?
-// Only then is the LN fold offered (kernels.hpp): forcing 256 x 256 tiles on a launch the fill rule gives to another tile would cost more than the fold returns.
-bool gemm_fold256_shape_ok(int M, int N, int K, bool split) {
-    if (M <= 0 || M % 256 != 0 || N % 256 != 0 || K % 64 != 0 || gemm256_mode() != 1) return false;
-    const long rb256 = M / 256, t256 = rb256 * (N / 256), t128 = rb256 * (N / 128);
-    if (t256 < 200 || fill256(t256) < 80) return false;
-    if (!split) return g256p_mode(false) != 0;
-    return g256p_mode(true) != 0 && opt(OPT_SPARSE_256) != 0 && opt(OPT_SPARSE_LO) != 0 && fill256(t256) + 12 >= fill256(t128);
-}
-
+// Every family is instantiated for every epilogue and weight form it is built for; `if constexpr` keeps out the ones it is not (the rule never routes there):
+// split weights (ws >= 2) and the fold are fp16 only; gemm48 has no RoPE or head epilogue, gemm96 no head epilogue, the plain gemm256p and the 192-column gemm256 no RoPE one.
 template <class T, int EPI>
 static int launch_epi(const GemmArgs& a, hipStream_t s, const char** err) {
-    const long nb = a.batch > 1 ? a.batch : 1;
-    if (a.fold256) {   // r06: the LN fold on the chip-filling tiles -- the caller asked gemm_fold256_shape_ok first; launch_gemm validated the operands
-        int rc = 1;
-        if constexpr (sizeof(T) == 2 && std::is_same<T, f16_t>::value) {
-            if (a.wsplit == 2) {
-                if constexpr (EPI == EPI_STORE16 || EPI == EPI_QKV_ROPE || EPI == EPI_RESID_F32) { pick_name("g256sf", EPI, 3, 256); rc = launch_256s<T, EPI>(a, s); }
-            } else {
-                if constexpr (EPI == EPI_STORE16_GELU || EPI == EPI_RESID_F32) { pick_name("g256pf", EPI, 1, 256); rc = launch_256p<T, EPI, 1, 256, 2>(a, s); }
+    constexpr bool F16 = std::is_same<T, f16_t>::value;
+    const GemmRoute r = gemm_route(gemm_shape(F16 ? DT_F16 : DT_BF16, (Epi)EPI, a), gemm_opts());
+    if (r.name != nullptr) pick_name(r.name, EPI, r.ws, r.bn);
+    const bool split = r.ws != 1;
+    int rc = 1;
+    switch (r.family) {   // in the order the rule tries the families
+        case GF_NONE: break;
+        case GF_G256SF:
+            if constexpr (F16 && (EPI == EPI_STORE16 || EPI == EPI_QKV_ROPE || EPI == EPI_RESID_F32)) rc = launch_256s<T, EPI>(a, s, false);
+            break;
+        case GF_G256PF:
+            if constexpr (F16 && (EPI == EPI_STORE16_GELU || EPI == EPI_RESID_F32)) rc = launch_256p<T, EPI, 1, 256, 2>(a, s, false);
+            break;
+        case GF_G256O2:   // the rule gives it to the GELU epilogue alone; the library holds the form for every epilogue, and a plain `if` keeps it so
+            if constexpr (F16) {
+                if (EPI == EPI_STORE16_GELU) rc = launch_256<T, EPI, 2, 128, 2>(a, s);
             }
-        }
-        if (rc) *err = "gemm: fold256 is built for fp16: split STORE16 / QKV_ROPE / RESID_F32 and plain STORE16_GELU / RESID_F32";
-        return rc;
+            break;
+        case GF_G96:
+            if constexpr (F16 && EPI != EPI_HEAD) rc = launch_96<T, EPI>(a, s);
+            break;
+        case GF_G48:
+        case GF_G48K128:
+            if constexpr (EPI != EPI_QKV_ROPE && EPI != EPI_HEAD) {
+                if (split) { if constexpr (F16) rc = launch_48<T, EPI, 2>(a, s, r.bk); }
+                else rc = launch_48<T, EPI, 1>(a, s, r.bk);
+            }
+            break;
+        case GF_G256S:
+            if constexpr (F16) rc = launch_256s<T, EPI>(a, s, r.persistent);
+            break;
+        case GF_G256PS:
+            if constexpr (F16) rc = launch_256p<T, EPI, 3, 128, 2>(a, s, r.persistent);
+            break;
+        case GF_G256P:
+            if (split) { if constexpr (F16) rc = launch_256p<T, EPI, 2, 128, 2>(a, s, r.persistent); }
+            else if constexpr (EPI != EPI_QKV_ROPE) rc = launch_256p<T, EPI, 1, 256, 2>(a, s, r.persistent);
+            break;
+        case GF_G256K:
+            if (split) { if constexpr (F16) rc = launch_256k<T, EPI, 2, 128>(a, s); }
+            else rc = launch_256k<T, EPI, 1, 256>(a, s);
+            break;
+        case GF_G256:
+            if (!split) rc = launch_256<T, EPI, 1, 256>(a, s);
+            else if constexpr (F16) {
+                if (r.bn == 256) rc = launch_256<T, EPI, 2, 256>(a, s);
+                else if (r.bn == 128) rc = launch_256<T, EPI, 2, 128>(a, s);
+                else if constexpr (EPI != EPI_QKV_ROPE) rc = launch_256<T, EPI, 2, 192>(a, s);   // its rotate-half pairs need 32-column aligned wave tiles
+            }
+            break;
+        case GF_G128:
+            if (split) { if constexpr (F16) rc = launch_cfg<T, 128, 64, 2, 2, EPI, 2, 2>(a, s); }
+            else rc = launch_cfg<T, 128, 128, 2, 2, EPI, 2, 1>(a, s);
+            break;
+        case GF_G64P:
+            if (split) { if constexpr (F16) rc = launch_cfg<T, 64, 64, SMALL_WGM, 2, EPI, SMALL8_NST_SPLIT, 2, 64, 1>(a, s); }
+            else rc = launch_cfg<T, 64, 64, SMALL_WGM, 2, EPI, SMALL8_NST_PLAIN, 1, 64, 1>(a, s);
+            break;
+        case GF_G64:
+            if (split) { if constexpr (F16) rc = launch_cfg<T, 64, 64, 2, 2, EPI, 3, 2>(a, s); }
+            else rc = launch_cfg<T, 64, 64, 2, 2, EPI, 4, 1>(a, s);
+            break;
     }
-    // LN-fold producers (x16_out / copy32_out / stats_out) need a kernel whose epilogue carries the LN paths: the 64 x 64 / 96 / 48 tiles
-    const bool lnp = a.x16_out != nullptr || a.copy32_out != nullptr || a.stats_out != nullptr;
-    const int mode = lnp ? 0 : gemm256_mode();
-    const long rb256 = (long)((a.M + 255) / 256) * nb;
-    int rc;
-    if (a.wsplit == 2) {
-        if constexpr (sizeof(T) == 2 && std::is_same<T, f16_t>::value) {
-            const long tiles = (long)((a.M + 127) / 128) * (a.N / 64) * nb;
-            const long t256 = rb256 * (a.N / 256), t192 = rb256 * (a.N / 192), t128 = rb256 * (a.N / 128);
-            const bool ok256 = a.N % 256 == 0 && a.K % 32 == 0, ok128 = a.N % 128 == 0 && a.K % 32 == 0;
-            // 192-column tiles (wave tile 128 x 48): N = 768 at M = 15360 is 240 tiles = ONE round at 94 % fill, where 256 columns
-            // give 180 tiles (70 %) and 128 columns two rounds.  Not for the RoPE epilogue (its rotate-half pairs need 32-column
-            // aligned wave tiles).
-            const bool ok192 = a.N % 192 == 0 && a.K % 32 == 0 && EPI != EPI_QKV_ROPE;
-            int pick = 0;
-            if (mode == 2) pick = !ok256 ? (ok128 ? 128 : 0) : 256;
-            else if (mode == 1) {
-                // cost ~ rounds over the 256 CUs x tile width; eligible when its rounds are reasonably full; ties -> wider tile
-                long best = -1;
-                const int bns[3] = {256, 192, 128};
-                const long ts[3] = {t256, t192, t128};
-                const bool oks[3] = {ok256, ok192, ok128};
-                for (int i = 0; i < 3; ++i) {
-                    if (!oks[i] || ts[i] < 200 || fill256(ts[i]) < 80) continue;
-                    const long cost = ((ts[i] + 255) / 256) * bns[i];
-                    if (best < 0 || cost < best) { best = cost; pick = bns[i]; }
-                }
-            }
-            // fc1 (exact-erf GELU epilogue, ~17 VALU per output) of the chip-filling batches: two 256 x 128 blocks per CU, so that one block's
-            // epilogue runs under the other's K loop.  Measured (r02, M = 15360): N = 3072, K = 768: 157 -> 143 us; N = 4096, K = 1024: 270 -> 265 us;
-            // every other epilogue is faster with one block per CU and the deeper ring (qkv 186 vs 199-209 us, fc2 210 vs 228 us).
-            constexpr bool gelu_occ2 = true;
-            if (a.ln_stats != nullptr) {
-                // LN-fold consumers: the kernels that carry the row-statistics prologue, whatever the tile count
-                if constexpr (EPI == EPI_STORE16_GELU) { pick_name("g96", EPI, 2, 96); rc = a.N % 96 == 0 ? launch_96<T, EPI>(a, s) : 1; }
-                else if constexpr (EPI == EPI_STORE16) { rc = a.N % 48 == 0 ? launch_48<T, EPI, 2>(a, s) : 1; pick_name(g_gemm48_bk == 128 ? "g48k128" : "g48", EPI, 2, 48); }
-                else if constexpr (EPI == EPI_QKV_ROPE) { pick_name("g64", EPI, 2, 64); rc = launch_cfg<T, 64, 64, 2, 2, EPI, 3, 2>(a, s); }
-                else rc = 1;
-            } else if (EPI == EPI_STORE16_GELU && gelu_occ2 && mode != 0 && ok128 && t128 >= 1024) { pick_name("g256o2", EPI, 2, 128); rc = launch_256<T, EPI, 2, 128, 2>(a, s); }
-            else if (EPI != EPI_HEAD && use_96(a, nb)) { pick_name("g96", EPI, 2, 96); rc = launch_96<T, EPI == EPI_HEAD ? EPI_STORE16 : EPI>(a, s); }
-            else if (EPI != EPI_QKV_ROPE && EPI != EPI_HEAD && use_48(a, nb)) { rc = launch_48<T, EPI == EPI_QKV_ROPE || EPI == EPI_HEAD ? EPI_STORE16 : EPI, 2>(a, s); pick_name(g_gemm48_bk == 128 ? "g48k128" : "g48", EPI, 2, 48); }
-            // r05: the 2:4-sparse low part (48 matrix instructions per K-tile instead of 64) wherever the launch fills the chip and the caller has the packed copy
-            else if (a.Wlo_sp != nullptr && a.Widx_sp != nullptr && g256p_mode(true) != 0 && ok128 && a.K % 64 == 0 && t128 >= 200 && a.ln_stats == nullptr && !lnp &&
-                     (fill256(t128) >= 80 || pick != 0)) {
-                // 256 x 256 sparse tiles (48 matrix instructions per phase) where they fill their rounds about as well as the 256 x 128 ones (24 per phase, load-bound)
-                const int s256 = opt(OPT_SPARSE_256);
-                if (s256 && ok256 && a.K % 64 == 0 && t256 >= 200 && fill256(t256) + 12 >= fill256(t128)) { pick_name("g256s", EPI, 3, 256); rc = launch_256s<T, EPI>(a, s); }
-                else { pick_name("g256ps", EPI, 3, 128); rc = launch_256p<T, EPI, 3, 128, 2>(a, s); }
-            }
-            else if (pick != 0 && ok128 && a.K % 64 == 0 && (g256p_mode(true) == 2 || (g256p_mode(true) == 1 && (pick == 128 || (pick == 192 && t128 >= 200 && fill256(t128) >= fill256(t192) && fill256(t128) >= 90))))) {
-                pick_name("g256p", EPI, 2, 128); rc = launch_256p<T, EPI, 2, 128, 2>(a, s);
-            }
-            else if (pick != 0 && g256k_mode() >= 2 && ok128) { pick_name("g256k", EPI, 2, 128); rc = launch_256k<T, EPI, 2, 128>(a, s); }
-            else if (pick == 256) { pick_name("g256", EPI, 2, 256); rc = launch_256<T, EPI, 2, 256>(a, s); }
-            else if (pick == 192) { pick_name("g256", EPI, 2, 192); rc = launch_256<T, EPI == EPI_QKV_ROPE ? EPI_STORE16 : EPI, 2, 192>(a, s); }
-            else if (pick == 128) { pick_name("g256", EPI, 2, 128); rc = launch_256<T, EPI, 2, 128>(a, s); }   // (two blocks per CU measured slower for every epilogue but the GELU one)
-            else if (tiles >= min_big(true) && !lnp) { pick_name("g128", EPI, 2, 64); rc = launch_cfg<T, 128, 64, 2, 2, EPI, 2, 2>(a, s); }
-            else if (small8((long)((a.M + 63) / 64) * (a.N / 64) * nb)) { pick_name("g64p", EPI, 2, 64); rc = launch_cfg<T, 64, 64, SMALL_WGM, 2, EPI, SMALL8_NST_SPLIT, 2, 64, 1>(a, s); }
-            else { pick_name("g64", EPI, 2, 64); rc = launch_cfg<T, 64, 64, 2, 2, EPI, 3, 2>(a, s); }
-        } else {
-            *err = "gemm: split weights are only built for fp16";
-            return 1;
-        }
-    } else {
-        const bool n128 = (a.N % 128) == 0;
-        const long tiles128 = (long)((a.M + 127) / 128) * (a.N / 128) * nb;
-        const long t256 = rb256 * (a.N / 256);
-        const bool ok256 = a.N % 256 == 0 && a.K % 32 == 0;
-        if (a.ln_stats != nullptr) {
-            // LN-fold consumers on plain weights (the Mlp fc1 of a one-view update in MUST3R_F16_WA mode): the 64 x 64 ring kernel
-            if constexpr (EPI == EPI_STORE16_GELU || EPI == EPI_STORE16 || EPI == EPI_QKV_ROPE) { pick_name("g64", EPI, 1, 64); rc = launch_cfg<T, 64, 64, 2, 2, EPI, 4, 1>(a, s); }
-            else rc = 1;
-        } else if (EPI != EPI_QKV_ROPE && EPI != EPI_HEAD && sizeof(T) == 2 && use_48(a, nb)) {
-            rc = launch_48<T, EPI == EPI_QKV_ROPE || EPI == EPI_HEAD ? EPI_STORE16 : EPI, 1>(a, s);
-            pick_name(g_gemm48_bk == 128 ? "g48k128" : "g48", EPI, 1, 48);   // N = 768 one-view launches: 256 tiles of 48 x 48
-        } else if (ok256 && a.K % 64 == 0 && g256p_mode(false) != 0 && EPI != EPI_QKV_ROPE && (mode == 2 || (mode == 1 && t256 >= 200 && fill256(t256) >= 80))) {
-            pick_name("g256p", EPI, 1, 256); rc = launch_256p<T, EPI == EPI_QKV_ROPE ? EPI_STORE16 : EPI, 1, 256, 2>(a, s);
-        } else if (ok256 && (mode == 2 || (mode == 1 && t256 >= 200 && fill256(t256) >= 80))) { pick_name(g256k_mode() >= 1 ? "g256k" : "g256", EPI, 1, 256); rc = g256k_mode() >= 1 ? launch_256k<T, EPI, 1, 256>(a, s) : launch_256<T, EPI, 1, 256>(a, s); }
-        else if (n128 && tiles128 >= min_big(false) && !lnp) { pick_name("g128", EPI, 1, 128); rc = launch_cfg<T, 128, 128, 2, 2, EPI, 2, 1>(a, s); }
-        else if (small8((long)((a.M + 63) / 64) * (a.N / 64) * nb)) { pick_name("g64p", EPI, 1, 64); rc = launch_cfg<T, 64, 64, SMALL_WGM, 2, EPI, SMALL8_NST_PLAIN, 1, 64, 1>(a, s); }
-        else { pick_name("g64", EPI, 1, 64); rc = launch_cfg<T, 64, 64, 2, 2, EPI, 4, 1>(a, s); }
-    }
-    if (rc) *err = "gemm: kernel launch failed";
+    if (rc) *err = r.err;
     return rc;
 }
 

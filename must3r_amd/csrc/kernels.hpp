@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gemm_route.hpp"
 
 struct must3r_hip_ctx;
 
@@ -13,15 +14,7 @@ enum DType { DT_BF16 = 0, DT_F16 = 1 };
 // ---------------------------------------------------------------------------------------------
 // GEMM   out[M,N] = epilogue( A[M,K] (16-bit, row-major, lda) x W[N,K]^T (16-bit, row-major) + bias[N] )
 // ---------------------------------------------------------------------------------------------
-enum Epi {
-    EPI_STORE16 = 0,   // out 16-bit [M,ldc]
-    EPI_STORE16_GELU,  // out 16-bit, exact-erf GELU
-    EPI_QKV_ROPE,      // out 16-bit, 2-D RoPE on columns < rope_cols (q and k of a fused qkv projection)
-    EPI_RESID_F32,     // out fp32 [M,ldc] += acc + bias   (in-place residual stream update)
-    EPI_F32,           // out fp32 = acc + bias (+ bias2 on rows >= row_start2) ; accumulate -> out += acc
-    EPI_HEAD,          // fp32 pixel-shuffled scatter into [view][H][W][7] (weights pre-permuted) ; accumulate alike
-    EPI_COUNT
-};
+// enum Epi, the epilogues, is declared in gemm_route.hpp with the rule that reads it
 
 // r06: the e4m3 attention path of BASELINE.json configs[4] (attn4_kernel<.., F8>, the [K e4m3 | V 16-bit] memory rows, the quantisation kernel) is PARKED: measured
 // +0.4 % on the mixed-resolution scene at 1.2e-3 ... 1.4e-3 from the 16-bit path, i.e. outside the 1e-3 target with nothing to show for it.  It is
@@ -105,12 +98,14 @@ struct GemmArgs {
 #endif
 };
 
-// returns 0 on success, non-zero (and sets *err) on an unsupported shape
+// returns 0 on success, non-zero (and sets *err) on an unsupported shape.  Which kernel family a launch gets is decided by gemm_route() (gemm_route.hpp: a pure
+// function of the shape and the option values, which a host program evaluates without a GPU: tests/c/gemm_route_check.cpp)
 int launch_gemm(DType dt, Epi epi, const GemmArgs& a, hipStream_t s, const char** err);
 // the kernel the calling thread's last launch_gemm picked: "<family>/e<EPI>/w<WS>/n<BN>" (one symbol of a kernel trace)
 const char* gemm_last_kernel();
 // r06: would launch_gemm route a launch of this shape to the 256 x 256 kernels that carry the LN fold (GemmArgs::fold256)?  split = [hi | lo] weights with a packed
 // 2:4-sparse low part (gemm256s_kernel), else plain fp16 weights (gemm256p_kernel).  The model folds a call's LayerNorms only when every Linear around them says yes.
+// (gemm_route.hpp's predicate of the same name, at the current option values)
 bool gemm_fold256_shape_ok(int M, int N, int K, bool split);
 
 // ---------------------------------------------------------------------------------------------

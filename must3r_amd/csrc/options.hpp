@@ -2,7 +2,8 @@
 // must3r_hip_set_option (include/must3r_hip.h, ABI 8) or, at first use, from the environment variable M3R_<NAME>; a value outside the range is
 // refused (set_option: status 1 + error string; environment: one line on stderr, the default is used).  The switches are measuring instruments:
 // every one keeps the results inside the precision mode's tolerance, and all but SPARSE_LO / LNFOLD / LNFOLD256 / ATTN_LZ keep them bit-identical (ATTN_LZ = 0:
-// P = 2^(s - m) is rounded against other references m).
+// P = 2^(s - m) is rounded against other references m).  GEMM256 = 0 and G256P_SPLIT = 0 turn the sparse kernels off with the other 256-row ones: on a split weight
+// with a packed sparse low part the launch then multiplies the dense low part, other bits than the default's, as with SPARSE_LO = 0.
 #pragma once
 
 namespace m3r {

@@ -60,7 +60,8 @@ static void run(const Var* vars, int nv, int M, int N, int K, int ws) {
 int main() {
     const Var vars[] = {
         {"256k", PL((launch_256k<f16_t, EPI_STORE16, 1, 256>)), PL((launch_256<f16_t, EPI_STORE16, 2, 128>))},
-        {"256p nph2 sync2", PL((launch_256p<f16_t, EPI_STORE16, 1, 256, 2, 2>)), PL((launch_256p<f16_t, EPI_STORE16, 2, 128, 2, 2>))},
+        {"256p nph2 sync2", [](const GemmArgs& a, hipStream_t s) { return launch_256p<f16_t, EPI_STORE16, 1, 256, 2, 2>(a, s, false); },
+         [](const GemmArgs& a, hipStream_t s) { return launch_256p<f16_t, EPI_STORE16, 2, 128, 2, 2>(a, s, false); }},
         {"256n one phase per K-tile", PL((launch_256n<f16_t, EPI_STORE16>)), nullptr},
         {"256w pat1", PL((launch_256w<f16_t, EPI_STORE16, 1, 256, 1>)), PL((launch_256w<f16_t, EPI_STORE16, 2, 128, 1>))},
     };

@@ -37,8 +37,9 @@ OUT_SCALE = struct.unpack("f", struct.pack("f", 0.125 * math.log2(math.e)))[0]  
 NPOS = 64
 
 
-# ---- csrc/gemm.hip launch_epi for the table defaults of options.hpp (GEMM256 = G256K = G256P = G256P_SPLIT = SPARSE_256 = SPARSE_LO = BK128 = 1, PERSIST = 0), without
-# the LN fold.  sparse: the caller passes the packed low part.  Returns gemm_last_kernel()'s "<family>/e<EPI>/w<WS>/n<BN>".
+# ---- csrc/gemm_route.hpp gemm_route restated for the table defaults of options.hpp (GEMM256 = G256K = G256P = G256P_SPLIT = SPARSE_256 = SPARSE_LO = BK128 = 1,
+# PERSIST = 0), without the LN fold: an independent restatement, held against the rule itself point for point without a GPU (tests/test_gemm_route_host.py).
+# sparse: the caller passes the packed low part.  Returns gemm_last_kernel()'s "<family>/e<EPI>/w<WS>/n<BN>".
 def _fill(t):
     return t * 100 // (((t + 255) // 256) * 256)
 

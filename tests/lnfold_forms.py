@@ -54,7 +54,7 @@ NK = len(KINDS)
 BIG_CH, TOK_CH, SAT_CH = (3, 90), (5, 77, 200), 7
 
 
-# ---- csrc/gemm.hip launch_epi restated for the fold's launches (default options; bk128: M3R_BK128)
+# ---- csrc/gemm_route.hpp gemm_route restated for the fold's launches (default options; bk128: M3R_BK128); tests/test_gemm_route_host.py holds both against the rule
 def consumer_kernel(epi, weights, bk128=1):
     if weights == "plain":
         return f"g64/e{epi}/w1/n64"
