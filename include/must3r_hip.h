@@ -1300,6 +1300,72 @@ size_t must3r_hip_jpeg_scratch_bytes(const must3r_hip_jpeg_image* images, int n_
  * in bounds and the pixels are unspecified. */
 int must3r_hip_jpeg_decode(const must3r_hip_jpeg_batch* batch);
 
+/* ---- PNG decoding (ABI 21, additive; csrc/png_parse.hpp, csrc/png_inflate.hpp, csrc/png.hip) --------------------------------------
+ * From the bytes of a file to pixels on the device, bit-equal to Pillow: inflate (RFC 1951) of the zlib stream the IDAT chunks hold, the Adler-32 check,
+ * the five scanline filters, and the caller's layout.  Accepted: non-interlaced files of colour type 0 at 8 or 16 bits, colour type 2 at 8 bits and colour
+ * type 6 at 8 bits, with one or more consecutive IDAT chunks and no tRNS or acTL chunk.  Everything else the parser reports with a reason, before anything
+ * is launched.
+ *
+ * The parser runs on the host and needs no GPU.  It never trusts a length field: every read is checked against the buffer.  Chunk CRCs are not verified
+ * (the pixel payload is covered by the Adler-32 check of the decode call).  The info record is plain data; `idat_ranges` receives the byte range of every
+ * IDAT chunk's payload, n_idat entries.  The caller copies these payloads back to back: the device sees one contiguous zlib stream per image. */
+#define MUST3R_PNG_OUT_RGB8   0   /* uint8 [H][W][3] (MUST3R_IMG_U8_HWC): grey replicated, alpha dropped; 8-bit files only */
+#define MUST3R_PNG_OUT_GRAY8  1   /* uint8 [H][W]; colour type 0 at 8 bits only */
+#define MUST3R_PNG_OUT_GRAY16 2   /* uint16 [H][W], little-endian; colour type 0 at 16 bits only */
+/* the status word of one image after a decode call; decoding of the image stops at the first of these */
+#define MUST3R_PNG_STATUS_OK          0
+#define MUST3R_PNG_STATUS_BLOCK_TYPE  1   /* deflate block type 3 */
+#define MUST3R_PNG_STATUS_CODE_SET    2   /* an over-subscribed or otherwise invalid set of code lengths */
+#define MUST3R_PNG_STATUS_CODE        3   /* bits that are no code of the table in use */
+#define MUST3R_PNG_STATUS_SYMBOL      4   /* literal/length symbol 286 or 287, distance symbol 30 or 31 */
+#define MUST3R_PNG_STATUS_DISTANCE    5   /* a distance beyond what has been written */
+#define MUST3R_PNG_STATUS_OVERFLOW    6   /* output beyond the expected size */
+#define MUST3R_PNG_STATUS_ENDS_EARLY  7   /* the stream ends inside a block */
+#define MUST3R_PNG_STATUS_SIZE        8   /* the final size is not the expected one */
+#define MUST3R_PNG_STATUS_STORED_LEN  9   /* a stored block whose LEN and ~LEN do not match */
+#define MUST3R_PNG_STATUS_ADLER      10   /* the Adler-32 of the inflated bytes is not the trailer's */
+#define MUST3R_PNG_STATUS_FILTER     11   /* a scanline with a filter type above 4 */
+typedef struct must3r_hip_png_info {
+    int32_t width, height;
+    int32_t color_type, bit_depth;   /* 0 / 8, 0 / 16, 2 / 8 or 6 / 8 */
+    int32_t channels, bpp;           /* samples per pixel; bytes per pixel, the step of the Sub / Average / Paeth filters */
+    int32_t n_idat, reserved;
+    int64_t rowbytes;                /* width * bpp */
+    int64_t inflated_bytes;          /* height * (1 + rowbytes), at most 2^28 */
+    int64_t idat_bytes;              /* the payloads of all IDAT chunks together: the zlib stream */
+} must3r_hip_png_info;
+typedef struct must3r_hip_png_range { uint64_t offset, length; } must3r_hip_png_range;   /* bytes from the start of the file */
+/* 0: accepted, *info is filled (and idat_ranges, when max_ranges >= n_idat; with a smaller capacity only info is filled: query n_idat first).
+ * 1: not accepted; `reason` (when not NULL, reason_bytes bytes) holds why as a C string.  No other outcome, no GPU call, no allocation. */
+int must3r_hip_png_parse(const void* data, size_t nbytes, must3r_hip_png_info* info, must3r_hip_png_range* idat_ranges, size_t max_ranges,
+                         char* reason, size_t reason_bytes);
+typedef struct must3r_hip_png_image {
+    const must3r_hip_png_info* info;   /* HOST: as must3r_hip_png_parse filled it */
+    const void* zdata;                 /* DEVICE: the IDAT payloads back to back, info->idat_bytes bytes, 16-byte aligned and readable up to the next multiple of 16 */
+    void*  out;                        /* DEVICE: [height][width] pixels of out_format, rows of out_row_stride bytes, 16-byte aligned */
+    int64_t out_row_stride;
+    int32_t out_format, reserved;      /* MUST3R_PNG_OUT_* */
+    void*  inflated;                   /* DEVICE or NULL.  Not NULL: the scanlines are kept here and not in the scratch, info->inflated_bytes rounded up to a
+                                          multiple of 256 plus 256 bytes, 256-byte aligned.  The first inflated_bytes bytes are the inflated stream with every
+                                          scanline's bytes unfiltered in place (the filter-type bytes stay); what follows them is unspecified */
+} must3r_hip_png_image;
+typedef struct must3r_hip_png_batch {
+    const must3r_hip_png_image* images;   /* HOST [n_images] */
+    int32_t n_images, reserved;
+    int32_t* status;         /* DEVICE [n_images], written: MUST3R_PNG_STATUS_* per image.  An image whose status is not OK has unspecified pixels */
+    void*  scratch;          /* DEVICE, 256-byte aligned */
+    size_t scratch_bytes;    /* >= must3r_hip_png_scratch_bytes of the same images */
+    void*  stream;           /* hipStream_t: every copy, memset and launch of the call goes there; nothing is read back */
+} must3r_hip_png_batch;
+/* device bytes of scratch for one decode call of these images (0 on invalid descriptors): the descriptor table and, for every image without an `inflated`
+ * buffer of its own, its inflated scanlines.  Only info and inflated of each image are read. */
+size_t must3r_hip_png_scratch_bytes(const must3r_hip_png_image* images, int n_images);
+/* Decodes the batch: png_inflate_kernel (one workgroup per image: the 32 KiB history, a staged stretch of the stream and the two decode tables in LDS),
+ * png_adler_kernel (a parallel reduction over the inflated bytes against the stream's trailer), png_unfilter_kernel (a wave takes 64 consecutive rows,
+ * skewed by one byte a row) and png_pack_kernel (the caller's layout).  A stream that is damaged sets the image's status word and stops that image's
+ * inflate; every access stays in bounds and the other images are not affected. */
+int must3r_hip_png_decode(const must3r_hip_png_batch* batch);
+
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 

@@ -326,6 +326,36 @@ class JpegBatch(C.Structure):
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+PNG_OUT_RGB8, PNG_OUT_GRAY8, PNG_OUT_GRAY16 = 0, 1, 2   # MUST3R_PNG_OUT_*
+# MUST3R_PNG_STATUS_*: the status word of one image after must3r_hip_png_decode
+PNG_STATUS = {0: "ok", 1: "invalid block type", 2: "invalid set of code lengths", 3: "invalid code", 4: "invalid literal/length or distance symbol",
+              5: "distance beyond the written output", 6: "output beyond the expected size", 7: "the stream ends early", 8: "final size is not the expected one",
+              9: "stored block length check", 10: "Adler-32 mismatch", 11: "filter type above 4"}
+
+
+class PngInfo(C.Structure):
+    """must3r_hip_png_info: what must3r_hip_png_parse takes the chunks of one file to (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color_type", C.c_int32), ("bit_depth", C.c_int32), ("channels", C.c_int32), ("bpp", C.c_int32),
+                ("n_idat", C.c_int32), ("reserved", C.c_int32), ("rowbytes", C.c_int64), ("inflated_bytes", C.c_int64), ("idat_bytes", C.c_int64)]
+
+
+class PngRange(C.Structure):
+    """must3r_hip_png_range: the payload of one IDAT chunk, bytes from the start of the file (include/must3r_hip.h, ABI 21)."""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64)]
+
+
+class PngImage(C.Structure):
+    """must3r_hip_png_image: one image of a decode call -- HOST info, DEVICE zlib stream, output and optional scanline buffer (include/must3r_hip.h, ABI 21)."""
+    _fields_ = [("info", C.POINTER(PngInfo)), ("zdata", C.c_void_p), ("out", C.c_void_p), ("out_row_stride", C.c_int64),
+                ("out_format", C.c_int32), ("reserved", C.c_int32), ("inflated", C.c_void_p)]
+
+
+class PngBatch(C.Structure):
+    """must3r_hip_png_batch: the HOST image table, the DEVICE status words, the scratch and the stream of one decode call (include/must3r_hip.h, ABI 21)."""
+    _fields_ = [("images", C.POINTER(PngImage)), ("n_images", C.c_int32), ("reserved", C.c_int32), ("status", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("flops", C.c_double), ("calls", C.c_int64)]
 
@@ -454,6 +484,9 @@ PROTOTYPES = {
     "must3r_hip_jpeg_parse": (i32, [vp, sz, P(JpegInfo), P(C.c_uint32), sz, vp, sz]),
     "must3r_hip_jpeg_scratch_bytes": (sz, [P(JpegImage), i32]),
     "must3r_hip_jpeg_decode": (i32, [P(JpegBatch)]),
+    "must3r_hip_png_parse": (i32, [vp, sz, P(PngInfo), P(PngRange), sz, vp, sz]),
+    "must3r_hip_png_scratch_bytes": (sz, [P(PngImage), i32]),
+    "must3r_hip_png_decode": (i32, [P(PngBatch)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -10,8 +10,9 @@ Same names and contracts as the reference, CUDA tensors out, no CPU fallback:
   BICUBIC) + crop + ImgNorm, bit-exact with Pillow, for one frame or a [B, H, W, 3] uint8 batch in one call.
 
 ImgNorm (dust3r: ToTensor then Normalize(0.5, 0.5)) maps a byte u to the fp32 value (u / 255 - 0.5) / 0.5; the library applies it
-through a 256-entry table built on the host (include/must3r_hip.h).  PNG decoding and palette / RGBA -> RGB conversion stay on the host
-in PIL, and so does JPEG decoding by default; ``load_images(..., decode="gpu")`` decodes baseline JPEGs on the device (must3r_amd/jpeg.py).
+through a 256-entry table built on the host (include/must3r_hip.h).  Palette -> RGB conversion stays on the host in PIL, and so do
+JPEG and PNG decoding by default; ``load_images(..., decode="gpu")`` decodes baseline JPEGs on the device (must3r_amd/jpeg.py), and
+with ``png="gpu"`` the 8-bit grey, RGB and RGBA PNGs as well (must3r_amd/png.py).
 """
 import ctypes as C
 
@@ -172,20 +173,26 @@ def _upload_u8(arr, device):
     return host.to(device, non_blocking=True)
 
 
-def load_images(folder_content, size, patch_size=16, verbose=True, device="cuda", decode="pil"):
+def load_images(folder_content, size, patch_size=16, verbose=True, device="cuda", decode="pil", png="pil"):
     """must3r/demo/inference.py:63-76 -> [dict(img=fp32 [3, h, w] CUDA, true_shape=np.int32([h, w]))].  Files are decoded in order and
     resampled in chunks of about LOAD_CHUNK_BYTES of uint8 pixels, one native call per chunk (12 MP photos: 8 per call), so host
     and device memory stay bounded however long the folder is.  ``decode="pil"`` (the default) decodes every file with Pillow on the host;
     ``decode="gpu"`` decodes the baseline JPEGs among them on the device (must3r_amd.jpeg, bit-equal to Pillow) and hands the pixels to the
-    resampler without a host copy; what that decoder refuses still goes through Pillow."""
+    resampler without a host copy; what that decoder refuses still goes through Pillow.  ``png="gpu"`` (with ``decode="gpu"`` only) sends the PNG files
+    that must3r_amd.png takes (8-bit grey, RGB and RGBA, not interlaced) to the device as well, in the same chunk as the JPEGs; ``png="pil"`` (the default)
+    leaves every PNG with Pillow."""
     import PIL.Image
     if decode not in ("pil", "gpu"):
         raise ValueError(f"must3r_amd.image.load_images: decode={decode!r} (\"pil\" or \"gpu\")")
+    if png not in ("pil", "gpu"):
+        raise ValueError(f"must3r_amd.image.load_images: png={png!r} (\"pil\" or \"gpu\")")
+    if png == "gpu" and decode != "gpu":
+        raise ValueError("must3r_amd.image.load_images: png=\"gpu\" needs decode=\"gpu\"")
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("must3r_amd.image.load_images: device must be CUDA; the HIP path has no CPU fallback")
     if decode == "gpu":
-        return _load_images_gpu(folder_content, size, patch_size, verbose, device)
+        return _load_images_gpu(folder_content, size, patch_size, verbose, device, png == "gpu")
     imgs, chunk, nbytes = [], [], 0
     for path in folder_content:
         rgb = PIL.Image.open(path).convert("RGB")
@@ -202,26 +209,45 @@ def load_images(folder_content, size, patch_size=16, verbose=True, device="cuda"
     return imgs
 
 
-def _load_images_gpu(folder_content, size, patch_size, verbose, device):
-    """load_images with the JPEG decode on the device: per chunk one decode call and one resample call, the pixels never on the host"""
-    from . import jpeg
+def _load_images_gpu(folder_content, size, patch_size, verbose, device, png_gpu=False):
+    """load_images with the JPEG decode on the device (and the PNG decode, with ``png_gpu``): per chunk one decode call per format and one resample call, the
+    pixels never on the host"""
+    from . import jpeg, png
     device = jpeg._cuda_device(device, "image.load_images")
     imgs, preps, paths, nbytes = [], [], [], 0
 
+    def prepare(path):
+        """-> (decoder module, its prepared item); a PNG that must3r_amd.png refuses arrives decoded by Pillow and travels with the JPEG decoder's refusals"""
+        if png_gpu:
+            with open(path, "rb") as f:
+                is_png = f.read(8) == b"\x89PNG\r\n\x1a\n"
+            if is_png:
+                p = png._prepare(path, "rgb", len(paths))
+                return (png, p) if p[0] == "gpu" else (jpeg, p[:4])
+        return jpeg, jpeg._prepare(path)
+
     def flush():
         nonlocal preps, paths, nbytes
+        tensors = [None] * len(preps)
+        for mod in (jpeg, png):
+            idx = [k for k, (m, _) in enumerate(preps) if m is mod]
+            if idx:
+                for k, t in zip(idx, mod._decode_prepared([preps[k][1] for k in idx], device)):
+                    tensors[k] = t
         chunk = []
-        for path, (_, _, H, W), t in zip(paths, preps, jpeg._decode_prepared(preps, device)):
+        for path, (_, p), t in zip(paths, preps, tensors):
+            H, W = p[2], p[3]
             target, crop_H, crop_W, _, _ = _geometry(size, patch_size, H, W)
             chunk.append((path, t, H, W, target, crop_H, crop_W))
         preps, paths, nbytes = [], [], 0
         return _load_chunk(chunk, device, verbose)
 
     for path in folder_content:
-        preps.append(jpeg._prepare(path))
+        preps.append(prepare(path))
         paths.append(path)
-        _geometry(size, patch_size, preps[-1][2], preps[-1][3])   # a size the buckets refuse is reported before anything is launched for the chunk
-        nbytes += preps[-1][2] * preps[-1][3] * 3
+        H, W = preps[-1][1][2], preps[-1][1][3]
+        _geometry(size, patch_size, H, W)   # a size the buckets refuse is reported before anything is launched for the chunk
+        nbytes += H * W * 3
         if nbytes >= LOAD_CHUNK_BYTES:
             imgs += flush()
     if preps:
