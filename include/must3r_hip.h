@@ -1369,6 +1369,92 @@ int must3r_hip_png_decode(const must3r_hip_png_batch* batch);
 /* debug: lane -> element mapping of the gfx950 transposing LDS read the attention kernel relies on; writes 256 int16 */
 int must3r_hip_debug_tr_probe(void* out256_i16_dev, void* stream);
 
+/* ABI 21, additive.  The per-frame step of the SLAM agent (must3r/slam/model.py: get_camera_pose :147-172, get_overlap_score :62-91, mean_focal :131-137 and
+ * the keyframe test of postproc_pred :231-235) as device work (csrc/slam.hip, must3r_amd/slam.py): everything between the decoder call and the keyframe
+ * decision is enqueued on the descriptor's `stream` without a host read, then ONE record of MUST3R_SLAM_RECORD_DOUBLES doubles is copied back per frame.
+ * All pointers are DEVICE pointers.
+ *
+ * must3r_hip_slam_pose: B >= 1 views of raw head output pm [B][H][W][7] -> activated pts3d / pts3d_local / conf (the launches and bits of
+ * must3r_hip_postprocess_cam_act: the raw form costs one pass where the activated form would cost two), focal [B] (the Weiszfeld routine of csrc/cam.hip on
+ * the UNrectified local points), c2w [B][4][4] and the rectified z of pts3d_local, written in place as fp32(z * ratio) with
+ * ratio = fp32(fp32(seq_focal) / focal), what the reference's in-place multiply through a view leaves behind.
+ *   focal_state  double [MUST3R_SLAM_FOCAL_STATE_DOUBLES] = (sum f_i c_i, sum c_i, n, sum f c / sum c), the agent's running sums in fp64, zeroed by the
+ *                caller at reset.  seq_focal = sum f c / sum c is read from it on the device when use_seq_focal != 0; n == 0 there, use_seq_focal == 0 or a
+ *                NULL focal_state mean "none" (ratio 1).  With update_focal != 0 (B must be 1) the view's f_i = focal and c_i = mean(conf - 1) (the fp64 sum of
+ *                the registration weights over H W) are added AFTER seq_focal was read, (f_i, c_i) is written to focal_log[n] (when n < focal_log_cap;
+ *                the caller grows the array by doubling) and n is advanced: mean_focal of the reference after its append.
+ *   is_first     R = I, T = 0, no rectification (the focal and the sums are still computed).
+ * Otherwise the registration of diag(1, 1, ratio) p_local -> p_world with weights conf - 1 is solved from the sums of the unrectified points (the
+ * 3-vector and the 3 x 3 moment are rectified before the solve), so z is rewritten by one small pass and the pixels are not read a second time.
+ * The cooperative exchange of csrc/cam.hip is reused unchanged: a launch that cannot be made co-resident fails with an error.
+ * scratch: must3r_hip_slam_pose_scratch_bytes(B, H, W) bytes (the camera pass's exchange slots and partial sums + one ratio per view), 256-byte aligned.
+ * Refused before anything is read or launched: a NULL descriptor, pm, pts3d, pts3d_local, conf, focal, c2w or scratch; B < 1, H or W not positive; an
+ * unknown activation; update_focal with B != 1 or without focal_state; a negative focal_log_cap, or a positive one without focal_log; scratch too small.
+ *
+ * must3r_hip_slam_keyframe: the keyframe test of ONE frame from pts3d, the rectified pts3d_local and conf [H][W], and c2w [4][4] in device memory (the
+ * camera centre is never a host argument).  Launches: slam_select_kernel (block 0: the mask conf > min_conf on the ::subsamp grid, its count n_sel, and the
+ * selected world points and depths compacted in row-major grid order -- ballots and a running offset, no atomics; block 1: mean of conf, fixed-order fp64
+ * sum, and the lower median of the full conf map, torch.median's value, by a 4 x 8-bit radix select), slam_walk_kernel (quadrant id of every selected point
+ * against the device's camera centre and the exact walk of must3r_hip_nn_index_query, one text with it: csrc/nn_walk.hpp; d = double(dist), with
+ * MUST3R_SLAM_MODE_NORM divided by double(fp32(z + 1e-9f)); +inf becomes DBL_MAX), slam_rank_kernel (the two order statistics numpy's linear percentile
+ * interpolates between, virtual index (n_sel - 1) * quantile, by an 8 x 8-bit radix select on the fp64 values: exact) and slam_record_kernel (the score by
+ * numpy's _lerp rule, a + (b - a) g, and b - (b - a)(1 - g) for g >= 0.5, every operation rounded; the record).  Counts in LDS are the only atomics and
+ * decide no order: two runs give the same bits, and a frame's bits do not depend on the frame before it.
+ *   index        a must3r_hip_nn_index_build buffer with the same `divider`, or NULL: an empty map, every distance DBL_MAX.
+ *   subsamp      0 = every pixel (as 1).   quantile = percentile / 100 in fp64, in [0, 1].
+ *   mode         MUST3R_SLAM_MODE_NN (walk, percentile score; n_sel == 0: score 0) with or without _NORM; else _MEANCONF or _MEDIANCONF: score = that statistic.
+ *   sel          out, fp32 [candidates][3]: rows [0, n_sel) are pts3d[::s, ::s][msk].     dist  out, optional, fp32 [candidates]: rows [0, n_sel) the distances.
+ *   focal, focal_state   optional, copied into the record (focal[0], focal_state[3]).
+ *   record       out, double [MUST3R_SLAM_RECORD_DOUBLES]: n_sel, order statistic below, above, score, conf median, conf mean, focal, mean focal,
+ *                camera centre (3), c2w (16), virtual index; the rest 0.
+ * scratch: must3r_hip_slam_keyframe_scratch_bytes(H, W, subsamp) bytes (12 per candidate + 256), 256-byte aligned.
+ * Refused before anything is read or launched: a NULL descriptor, pts3d, pts3d_local, conf, c2w, sel, record or scratch; H or W not positive or more than
+ * 2^24 pixels; subsamp < 0; divider outside [0, 8]; quantile outside [0, 1] or NaN; no mode or an unknown mode bit, MUST3R_SLAM_MODE_NORM without _NN,
+ * _NN together with a conf mode, both conf modes; scratch too small; sel, record or scratch not 8-byte aligned. */
+#define MUST3R_SLAM_RECORD_DOUBLES 32
+#define MUST3R_SLAM_FOCAL_STATE_DOUBLES 4
+#define MUST3R_SLAM_MODE_NN 1
+#define MUST3R_SLAM_MODE_NORM 2
+#define MUST3R_SLAM_MODE_MEANCONF 4
+#define MUST3R_SLAM_MODE_MEDIANCONF 8
+typedef struct must3r_hip_slam_pose_args {
+    const float* pm;            /* [B, H, W, 7] raw head output */
+    float*  pts3d;              /* [B, H, W, 3] out */
+    float*  pts3d_local;        /* [B, H, W, 3] out, z rectified */
+    float*  conf;               /* [B, H, W] out */
+    float*  focal;              /* [B] out */
+    float*  c2w;                /* [B, 4, 4] out */
+    double* focal_state;        /* [MUST3R_SLAM_FOCAL_STATE_DOUBLES], optional */
+    double* focal_log;          /* [focal_log_cap, 2], optional */
+    void*   scratch;
+    size_t  scratch_bytes;
+    int32_t B, H, W, activation;   /* MUST3R_ACT_* */
+    int32_t is_first, use_seq_focal, update_focal, focal_log_cap;
+    void* stream;               /* hipStream_t */
+} must3r_hip_slam_pose_args;
+size_t must3r_hip_slam_pose_scratch_bytes(int B, int H, int W);
+int must3r_hip_slam_pose(const must3r_hip_slam_pose_args* a);
+typedef struct must3r_hip_slam_keyframe_args {
+    const float*  pts3d;        /* [H, W, 3] */
+    const float*  pts3d_local;  /* [H, W, 3], z rectified */
+    const float*  conf;         /* [H, W] */
+    const float*  c2w;          /* [4, 4] */
+    const float*  focal;        /* [1], optional */
+    const double* focal_state;  /* [MUST3R_SLAM_FOCAL_STATE_DOUBLES], optional */
+    const void*   index;        /* must3r_hip_nn_index_build's, optional */
+    float*  sel;                /* [candidates, 3] out */
+    float*  dist;               /* [candidates] out, optional */
+    double* record;             /* [MUST3R_SLAM_RECORD_DOUBLES] out */
+    void*   scratch;
+    size_t  scratch_bytes;
+    double  quantile;
+    float   min_conf;
+    int32_t H, W, subsamp, divider, mode;
+    void* stream;               /* hipStream_t */
+} must3r_hip_slam_keyframe_args;
+size_t must3r_hip_slam_keyframe_scratch_bytes(int H, int W, int subsamp);
+int must3r_hip_slam_keyframe(const must3r_hip_slam_keyframe_args* a);
+
 /* timing hooks used by bench.py: per-stage HIP-event timers recorded on the call's stream */
 int must3r_hip_set_profiling(must3r_hip_ctx* ctx, int enabled);
 /* returns the number of records written (<= max); each record: name (<=31 chars), milliseconds, flops.

@@ -296,6 +296,28 @@ class AugmentDepthArgs(C.Structure):
                 ("V", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("depth_u16", C.c_int32), ("stream", C.c_void_p)]
 
 
+SLAM_RECORD_DOUBLES, SLAM_FOCAL_STATE_DOUBLES = 32, 4   # MUST3R_SLAM_RECORD_DOUBLES, MUST3R_SLAM_FOCAL_STATE_DOUBLES
+SLAM_MODE_NN, SLAM_MODE_NORM, SLAM_MODE_MEANCONF, SLAM_MODE_MEDIANCONF = 1, 2, 4, 8   # MUST3R_SLAM_MODE_*
+
+
+class SlamPoseArgs(C.Structure):
+    """must3r_hip_slam_pose_args: raw head output of B views, the activated outputs, focal and c2w, the agent's running focal sums and (f, c) log on the
+    DEVICE, the scratch and the stream (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("pm", C.c_void_p), ("pts3d", C.c_void_p), ("pts3d_local", C.c_void_p), ("conf", C.c_void_p), ("focal", C.c_void_p), ("c2w", C.c_void_p),
+                ("focal_state", C.c_void_p), ("focal_log", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("activation", C.c_int32),
+                ("is_first", C.c_int32), ("use_seq_focal", C.c_int32), ("update_focal", C.c_int32), ("focal_log_cap", C.c_int32), ("stream", C.c_void_p)]
+
+
+class SlamKeyframeArgs(C.Structure):
+    """must3r_hip_slam_keyframe_args: one frame's activated maps and its c2w on the DEVICE, the map's index (or none), the compacted points, the
+    per-frame record, the scratch and the stream (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("pts3d", C.c_void_p), ("pts3d_local", C.c_void_p), ("conf", C.c_void_p), ("c2w", C.c_void_p), ("focal", C.c_void_p),
+                ("focal_state", C.c_void_p), ("index", C.c_void_p), ("sel", C.c_void_p), ("dist", C.c_void_p), ("record", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("quantile", C.c_double), ("min_conf", C.c_float),
+                ("H", C.c_int32), ("W", C.c_int32), ("subsamp", C.c_int32), ("divider", C.c_int32), ("mode", C.c_int32), ("stream", C.c_void_p)]
+
+
 JPEG_SUBSEQ_BYTES = 128   # MUST3R_JPEG_SUBSEQ_BYTES
 JPEG_PATH_FAST, JPEG_PATH_SEQUENTIAL = 0, 1   # MUST3R_JPEG_PATH_*
 
@@ -487,6 +509,10 @@ PROTOTYPES = {
     "must3r_hip_png_parse": (i32, [vp, sz, P(PngInfo), P(PngRange), sz, vp, sz]),
     "must3r_hip_png_scratch_bytes": (sz, [P(PngImage), i32]),
     "must3r_hip_png_decode": (i32, [P(PngBatch)]),
+    "must3r_hip_slam_pose_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_slam_pose": (i32, [P(SlamPoseArgs)]),
+    "must3r_hip_slam_keyframe_scratch_bytes": (sz, [i32, i32, i32]),
+    "must3r_hip_slam_keyframe": (i32, [P(SlamKeyframeArgs)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -25,6 +25,7 @@
 // with Horn's quaternion form (largest eigenvector of a 4x4 symmetric matrix, cyclic Jacobi in fp64), which equals
 // U diag(1,1,det(UV^T)) V^T of the SVD form without the sign case analysis.
 #include "abi.hpp"
+#include "cam_solve.hpp"
 #include "common.hpp"
 
 namespace m3r {
@@ -127,121 +128,15 @@ __device__ __forceinline__ void exchange_pair(dbl2* slots /* [3][G] of the view 
 __device__ __forceinline__ void put(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // One block (64 threads) per view: lanes 0..15 add up the G per-block partials of the registration sums in block
-// order, lane 0 solves.  S = [sum w, sum w x (3), sum w y (3), sum w y_i x_j (9)]
+// order, lane 0 solves (cam_solve.hpp, shared with slam.hip).
 __global__ void __launch_bounds__(64) cam_solve_kernel(const double* __restrict__ partial, const double* __restrict__ focal_in, int G,
                                                        float* __restrict__ focal_out, float* __restrict__ c2w_out) {
     __shared__ double S4[4][16];
     __shared__ double S[16];
     const int v = blockIdx.x;
-    const double* part = partial + (size_t)v * G * 16;
-    {   // lane (q, j): blocks b = q, q + 4, ... of sum j; the four quarter sums are then added in order
-        const int j = threadIdx.x & 15, q = threadIdx.x >> 4;
-        double acc = 0.0;
-        for (int b = q; b < G; b += 4) acc += part[(size_t)b * 16 + j];
-        S4[q][j] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) S[threadIdx.x] = ((S4[0][threadIdx.x] + S4[1][threadIdx.x]) + S4[2][threadIdx.x]) + S4[3][threadIdx.x];
-    __syncthreads();
+    cam_sum_partials(partial + (size_t)v * G * 16, G, S4, S);
     if (threadIdx.x != 0) return;
-    float* c2w = c2w_out + (size_t)v * 16;
-    const double sw = S[0];
-    double xb[3], yb[3], M[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        xb[i] = S[1 + i] / sw;
-        yb[i] = S[4 + i] / sw;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) M[i][j] = S[7 + i * 3 + j] / sw - yb[i] * xb[j];
-    // Horn: s[a][b] = sum x_a y_b = M^T
-    const double sxx = M[0][0], sxy = M[1][0], sxz = M[2][0];
-    const double syx = M[0][1], syy = M[1][1], syz = M[2][1];
-    const double szx = M[0][2], szy = M[1][2], szz = M[2][2];
-    double A[4][4] = {{sxx + syy + szz, syz - szy, szx - sxz, sxy - syx},
-                      {syz - szy, sxx - syy - szz, sxy + syx, szx + sxz},
-                      {szx - sxz, sxy + syx, -sxx + syy - szz, syz + szy},
-                      {sxy - syx, szx + sxz, syz + szy, -sxx - syy + szz}};
-    double Q[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    double scale = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) scale = fmax(scale, fabs(A[i][j]));
-    const double inv_scale = scale > 0.0 ? 1.0 / scale : 1.0;   // eigenvectors do not care; keeps the fp32 angle in range
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) A[i][j] *= inv_scale;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        double off = 0.0;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) off = fmax(off, fabs(A[p][q]));
-        if (!(off > 1e-14)) break;   // R is returned in fp32
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[p][q];
-                if (fabs(apq) > 1e-30) {
-                    // the angle only has to be roughly right (fp32 tangent); what must hold to fp64 is c^2 + s^2 = 1, so
-                    // c comes from a Newton-refined fp64 rsqrt of 1 + t^2 and s = t c.  fp64 div/sqrt cost ~30
-                    // dependent instructions each and this is a single thread per view.
-                    const float thf = (float)(A[q][q] - A[p][p]) / (2.0f * (float)apq);
-                    const float tf = (thf >= 0.f ? 1.0f : -1.0f) / (fabsf(thf) + sqrtf(thf * thf + 1.0f));
-                    const double t = (double)tf, n2 = t * t + 1.0;
-                    double c = __builtin_amdgcn_rsq(n2);
-                    c = c * (1.5 - 0.5 * n2 * c * c);
-                    c = c * (1.5 - 0.5 * n2 * c * c);
-                    const double s = t * c;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {   // A <- A J
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = c * akp - s * akq;
-                        A[k][q] = s * akp + c * akq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {   // A <- J^T A
-                        const double apk = A[p][k], aqk = A[q][k];
-                        A[p][k] = c * apk - s * aqk;
-                        A[q][k] = s * apk + c * aqk;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {   // Q <- Q J
-                        const double qkp = Q[k][p], qkq = Q[k][q];
-                        Q[k][p] = c * qkp - s * qkq;
-                        Q[k][q] = s * qkp + c * qkq;
-                    }
-                }
-            }
-    }
-    double bestv = A[0][0], qw = Q[0][0], qx = Q[1][0], qy = Q[2][0], qz = Q[3][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (A[i][i] > bestv) {
-            bestv = A[i][i];
-            qw = Q[0][i]; qx = Q[1][i]; qy = Q[2][i]; qz = Q[3][i];
-        }
-    const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-    qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-    const double R[3][3] = {{1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy)},
-                            {2 * (qx * qy + qw * qz), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qw * qx)},
-                            {2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), 1 - 2 * (qx * qx + qy * qy)}};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double t = yb[i];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            c2w[i * 4 + j] = (float)R[i][j];
-            t -= R[i][j] * xb[j];
-        }
-        c2w[i * 4 + 3] = (float)t;
-    }
-    c2w[12] = 0.f; c2w[13] = 0.f; c2w[14] = 0.f; c2w[15] = 1.f;
+    cam_register<false>(S, 1.0, c2w_out + (size_t)v * 16);
     focal_out[v] = (float)focal_in[v];
 }
 
@@ -356,31 +251,30 @@ extern "C" size_t must3r_hip_postprocess_cam_scratch_bytes(int n_views, int H, i
     return (size_t)n_views * gmax * (3 * 16 + 16 * 8) + (size_t)n_views * 8 + 256;
 }
 
-extern "C" int must3r_hip_postprocess_cam_act(const float* pm, int activation, int n_views, int H, int W, float* p3, float* pl, float* cf,
-                                              float* focal, float* c2w, void* scratch, size_t scratch_bytes, void* stream) {
-    if (n_views < 0 || H <= 0 || W <= 0) return fail("postprocess_cam: bad shape");
-    if (activation != MUST3R_ACT_NORM_EXP && activation != MUST3R_ACT_LINEAR) return fail("postprocess_cam: unknown activation %d", activation);
+int m3r::cam_data_pass(const char* who, const float* pm, int activation, int n_views, int H, int W, float* p3, float* pl, float* cf, void* scratch,
+                       size_t scratch_bytes, hipStream_t s, cam_solve_fn solve, void* user) {
+    if (n_views < 0 || H <= 0 || W <= 0) return fail("%s: bad shape", who);
+    if (activation != MUST3R_ACT_NORM_EXP && activation != MUST3R_ACT_LINEAR) return fail("%s: unknown activation %d", who, activation);
     if (n_views == 0) return 0;
-    if (!pm || !p3 || !pl || !cf || !focal || !c2w || !scratch) return fail("postprocess_cam: null argument");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!pm || !p3 || !pl || !cf || !scratch) return fail("%s: null argument", who);
     const int P = H * W;
-    if (P <= 0) return fail("postprocess_cam: empty image");
-    if (scratch_bytes < must3r_hip_postprocess_cam_scratch_bytes(n_views, H, W)) return fail("postprocess_cam: scratch too small");
+    if (P <= 0) return fail("%s: empty image", who);
+    if (scratch_bytes < must3r_hip_postprocess_cam_scratch_bytes(n_views, H, W)) return fail("%s: scratch too small", who);
     int dev = 0, ncu = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cam_kernel, CAM_T, 0) != hipSuccess || per_cu < 1)
-        return fail("postprocess_cam: occupancy query failed");
+        return fail("%s: occupancy query failed", who);
     const int slots = ncu * per_cu;                                   // blocks that can be resident together
     const int gmin = (P + CAM_T * CAM_PPT - 1) / (CAM_T * CAM_PPT);   // fewest blocks per view (register cache bound)
     const int gmax = (P + CAM_T - 1) / CAM_T;
-    if (gmin > slots) return fail("postprocess_cam: image too large for the per-view register cache");
+    if (gmin > slots) return fail("%s: image too large for the per-view register cache", who);
     const int vmax = slots / gmin;                                    // views per launch
     // scratch: [slots | partial | focal]; the slots must read all-ones (the "not yet published" sentinel)
     const size_t slot_bytes = (size_t)n_views * 3 * gmax * 16;
     dbl2* slot_base = reinterpret_cast<dbl2*>(scratch);
     double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + slot_bytes);
     double* sums = partial + (size_t)n_views * gmax * 16;
-    if (hipMemsetAsync(slot_base, 0xFF, slot_bytes, s) != hipSuccess) return fail("postprocess_cam: memset failed");
+    if (hipMemsetAsync(slot_base, 0xFF, slot_bytes, s) != hipSuccess) return fail("%s: memset failed", who);
     for (int v0 = 0; v0 < n_views; v0 += vmax) {
         const int nv = (n_views - v0 < vmax) ? n_views - v0 : vmax;
         int G = slots / nv;
@@ -402,12 +296,33 @@ extern "C" int must3r_hip_postprocess_cam_act(const float* pm, int activation, i
         void* args[] = {&a};
         if (hipLaunchCooperativeKernel(reinterpret_cast<const void*>(cam_kernel), dim3(nv * G), dim3(CAM_T), args, 0, s) != hipSuccess) {
             (void)hipGetLastError();
-            return fail("postprocess_cam: cooperative launch failed");
+            return fail("%s: cooperative launch failed", who);
         }
-        hipLaunchKernelGGL(cam_solve_kernel, dim3(nv), dim3(64), 0, s, a.partial, a.sums, G, focal + v0, c2w + (size_t)v0 * 16);
-        if (hipGetLastError() != hipSuccess) return fail("postprocess_cam: solve launch failed");
+        if (solve(user, v0, nv, G, a.partial, a.sums, s)) return 1;
     }
     return 0;
+}
+
+namespace {
+struct CamOut {
+    float* focal;
+    float* c2w;
+};
+int cam_solve_launch(void* user, int v0, int nv, int G, const double* partial, const double* focal, hipStream_t s) {
+    const CamOut* o = static_cast<const CamOut*>(user);
+    hipLaunchKernelGGL(cam_solve_kernel, dim3(nv), dim3(64), 0, s, partial, focal, G, o->focal + v0, o->c2w + (size_t)v0 * 16);
+    if (hipGetLastError() != hipSuccess) return fail("postprocess_cam: solve launch failed");
+    return 0;
+}
+}  // namespace
+
+extern "C" int must3r_hip_postprocess_cam_act(const float* pm, int activation, int n_views, int H, int W, float* p3, float* pl, float* cf,
+                                              float* focal, float* c2w, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n_views > 0 && H > 0 && W > 0 && (activation == MUST3R_ACT_NORM_EXP || activation == MUST3R_ACT_LINEAR) && (!focal || !c2w))
+        return fail("postprocess_cam: null argument");
+    CamOut o{focal, c2w};
+    return cam_data_pass("postprocess_cam", pm, activation, n_views, H, W, p3, pl, cf, scratch, scratch_bytes, reinterpret_cast<hipStream_t>(stream),
+                         cam_solve_launch, &o);
 }
 
 extern "C" int must3r_hip_postprocess_cam(const float* pm, int n_views, int H, int W, float* p3, float* pl, float* cf, float* focal, float* c2w,

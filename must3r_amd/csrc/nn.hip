@@ -15,6 +15,7 @@
 // VALU-bound (fp32 vector rate 157 TFLOP/s): 8 flops per pair.
 #include "abi.hpp"
 #include "common.hpp"
+#include "nn_walk.hpp"
 
 namespace m3r {
 
@@ -84,22 +85,12 @@ __global__ void nn_finish_kernel(float* __restrict__ d, const long long n) {
     if (i < n) d[i] = sqrtf(d[i]);         // sqrt(+inf) = +inf
 }
 
-// slam/tools.py:9-31 with quadrant_divider = div, eps = 1e-5 (float32 like the numpy code fed with float32 points)
+// slam/tools.py:9-31 (nn_walk.hpp, shared with slam.hip)
 __global__ void quadrant_id_kernel(const float* __restrict__ pts, const long long n, const float cx, const float cy, const float cz,
                                    const int div, int* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float eps = 1e-5f, pi = 3.14159265358979323846f;
-    float x = pts[i * 3 + 0] - cx, y = pts[i * 3 + 1] - cy, z = pts[i * 3 + 2] - cz;
-    const float nrm = fmaxf(sqrtf(x * x + y * y + z * z), eps);
-    x /= nrm; y /= nrm; z /= nrm;
-    float theta = acosf(z) / pi;
-    float phi = atan2f(y, x) / pi;
-    theta = fminf(fmaxf(theta, eps), 1.0f - eps);
-    phi = fminf(fmaxf(phi, -1.0f + eps), 1.0f - eps);
-    const int ti = (int)floorf(theta * (float)div);
-    const int pj = (int)floorf(phi * (float)div) + div;
-    out[i] = ti + pj * div;
+    out[i] = quadrant_of(pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2], cx, cy, cz, div);
 }
 
 }  // namespace m3r

@@ -27,13 +27,13 @@
 // force's minimum over the same points, and sqrtf of it is bit-identical.  Empty quadrant / non-finite query: +inf as nn.hip gives.
 #include "abi.hpp"
 #include "common.hpp"
+#include "nn_walk.hpp"
 #include "options.hpp"
 
 namespace m3r {
 
 namespace {
 
-constexpr int NNI_MAXQ = 128;          // quadrants (divider <= 8: 2 * 8^2)
 constexpr int NNI_MIN_LEAF_LOG2 = 4;   // the node area is sized for leaves of 16 points, the smallest NN_LEAF_LOG2 allows
 constexpr int RS_T = 256;              // radix sort: threads per block
 constexpr int RS_ITEMS = 32;           // elements per thread and block tile
@@ -41,24 +41,13 @@ constexpr int RS_TILE = RS_T * RS_ITEMS;
 constexpr int BB_BLOCKS = 1024;        // partial boxes of the bounding-box reduction
 constexpr long long NNI_MAX_N = 1LL << 30;
 
-struct NnIndexHeader {
-    int divider, n_quads, leaf_log2, key_shift;
-    int morton_bits, n_points, pad0, pad1;
-    long long pts_off, nodes_off, node_cap, pad2;
-    float lo[4], hi[4];
-    int seg[NNI_MAXQ + 4];            // seg[q] .. seg[q + 1]: quadrant q in key order; seg[Q] = finite points
-    int pow2[NNI_MAXQ];               // P_q: leaves of quadrant q padded to a power of two (0: empty)
-    int depth[NNI_MAXQ];              // log2(P_q)
-    int node_base[NNI_MAXQ];          // first node of quadrant q's heap (node k at node_base + k - 1)
-};
+// NnIndexHeader: nn_walk.hpp
 constexpr size_t NNI_HEADER_BYTES = (sizeof(NnIndexHeader) + 255) / 256 * 256;
 
 int n_quads_of(int divider) { return divider == 0 ? 1 : 2 * divider * divider; }
 long long node_cap_of(long long n, int Q) { return 4 * (((n + (1 << NNI_MIN_LEAF_LOG2) - 1) >> NNI_MIN_LEAF_LOG2) + Q) + 4; }
 long long rs_blocks_of(long long n) { return (n + RS_TILE - 1) / RS_TILE; }
 long long next_pow2(long long v) { long long p = 1; while (p < v) p <<= 1; return p; }
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 // --------------------------------------------------------------------------------------------------------------------------------
 // bounding box of the finite points
@@ -348,74 +337,16 @@ __global__ void __launch_bounds__(256) nn_tree_level_kernel(char* __restrict__ i
 // --------------------------------------------------------------------------------------------------------------------------------
 // query
 // --------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float box_bound(const f32x4* __restrict__ nb, const int k, const float qx, const float qy, const float qz) {
-    const f32x4 lo = nb[2 * (k - 1)], hi = nb[2 * (k - 1) + 1];
-    const float gx = fmaxf(fmaxf(lo[0] - qx, qx - hi[0]), 0.f);
-    const float gy = fmaxf(fmaxf(lo[1] - qy, qy - hi[1]), 0.f);
-    const float gz = fmaxf(fmaxf(lo[2] - qz, qz - hi[2]), 0.f);
-    return fmaf(gz, gz, fmaf(gy, gy, gx * gx));
-}
-
-// G lanes per query: every lane of a group walks the same path (the same boxes, the group's best), the points of a leaf are split
-// over the group and the group's minimum is taken with xor shuffles (min is exact and order-free: the result is the same for every G).
+// G lanes per query walk its quadrant's heap together (nn_walk.hpp, shared with slam.hip).
 template <int G>
 __global__ void __launch_bounds__(256) nn_index_query_kernel(const char* __restrict__ index, const float* __restrict__ q, const int n_q,
                                                              const int divider, float* out) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     const int i = (int)(t / G), sub = (int)(t % G);   // a group never straddles a wave (G divides 64)
     if (i >= n_q) return;
-    const NnIndexHeader* h = reinterpret_cast<const NnIndexHeader*>(index);
     const int quad = divider > 0 ? reinterpret_cast<const int*>(out)[i] : 0;   // must3r_hip_quadrant_ids wrote the id here; read before the write
     const float qx = q[(long long)i * 3 + 0], qy = q[(long long)i * 3 + 1], qz = q[(long long)i * 3 + 2];
-    float best = INFINITY;
-    const int P = (quad >= 0 && quad < h->n_quads) ? h->pow2[quad] : 0;
-    if (divider != h->divider) {
-        best = __builtin_nanf("");   // queried with another divider than the build's: NaN, never a plausible distance
-    } else if (P > 0 && finite3(qx, qy, qz)) {
-        const f32x4* nb = reinterpret_cast<const f32x4*>(index + h->nodes_off) + 2LL * h->node_base[quad];
-        const f32x4* pts = reinterpret_cast<const f32x4*>(index + h->pts_off);
-        const int D = h->depth[quad], L = 1 << h->leaf_log2, lg = h->leaf_log2;
-        const int s_begin = h->seg[quad], s_end = h->seg[quad + 1];
-        int k = 1, l = 0;
-        unsigned trail = 0;   // bit l: the node on the path at level l is the second child visited (its sibling is done)
-        bool go = box_bound(nb, 1, qx, qy, qz) < best;
-        while (go) {
-            bool down = false;
-            if (l == D) {
-                const int s0 = s_begin + ((k - P) << lg);
-                const int s1 = min(s0 + L, s_end);
-                for (int s = s0 + sub; s < s1; s += G) {
-                    const f32x4 p = pts[s];
-                    const float dx = qx - p[0], dy = qy - p[1], dz = qz - p[2];
-                    best = fminf(best, fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
-                }
-#pragma unroll
-                for (int o = G / 2; o > 0; o >>= 1) best = fminf(best, __shfl_xor(best, o, G));
-            } else {
-                const float b0 = box_bound(nb, 2 * k, qx, qy, qz), b1 = box_bound(nb, 2 * k + 1, qx, qy, qz);
-                const bool right = b1 < b0;   // the nearer child first (left on a tie)
-                if ((right ? b1 : b0) < best) {
-                    k = 2 * k + (right ? 1 : 0);
-                    ++l;
-                    down = true;
-                }
-            }
-            if (down) continue;
-            // climb to the first level whose sibling has not been visited and may still hold a smaller d2
-            go = false;
-            while (l > 0) {
-                if ((trail >> l) & 1u) {
-                    trail &= ~(1u << l);
-                    k >>= 1;
-                    --l;
-                    continue;
-                }
-                trail |= 1u << l;
-                k ^= 1;
-                if (box_bound(nb, k, qx, qy, qz) < best) { go = true; break; }
-            }
-        }
-    }
+    const float best = nn_walk<G>(index, divider, quad, qx, qy, qz, sub);
     if (sub == 0) out[i] = sqrtf(best);   // sqrt(+inf) = +inf
 }
 
