@@ -275,6 +275,36 @@ int must3r_hip_asmk_scores(const int32_t* words_q, const uint32_t* bits_q, const
                            const int32_t* words_d, const uint32_t* bits_d, const int32_t* counts_d, const int32_t* offsets_d, int k_d, int n_d,
                            int D, float alpha, float threshold, int normalize, double* out, void* stream);
 
+/* ---- ABI 21, additive: learning the retrieval mode's two artefacts on the device (csrc/asmk_train.hip) -- the k-means update behind the ASMK codebook
+ * (the assignment step is must3r_hip_asmk_quantize with k = 1) and the covariance behind the PCA whitening (retrieval/model.py:18-35
+ * pcawhitenlearn_shrinkage).  The stream is a parameter of both; the scratch and its size come last, as in the other ABI 21 entry points.
+ * Deterministic: no floating-point atomics, every floating-point output has one writer and a fixed order of operations.
+ * must3r_hip_kmeans_update: feat fp32 [M,D], centroids fp32 [K,D] (the ones the ids were assigned against), ids int32, row j at ids[j * ids_stride]
+ *   (ids_stride = 1: a vector; = k: column 0 of a [M,k] tensor), order int64 [M]: the STABLE ascending argsort of the ids (rows grouped by cluster, ascending
+ *   row index inside a cluster).  Outputs: counts int32 [K], exact; new_centroids fp32 [K,D]: for counts[c] > 0, fp32(sum / counts[c]) with the sum of the
+ *   cluster's rows in fp64, SEQUENTIAL in ascending row index -- bit-for-bit repeatable, and independent of every other row and cluster of the call; for
+ *   counts[c] == 0 the old centroids[c], bit for bit (a reseeding rule belongs to the caller).  dist fp64 [M]: sum_d (double(x_jd) - double(c_{ids[j]},d))^2
+ *   against the OLD centroids; objective fp64 [1] (device) = sum_j dist[j], in an order that depends on M alone.
+ *   Refused (non-zero return, must3r_hip_last_error): a NULL pointer, feat / centroids / new_centroids not 16-byte aligned, order / dist / objective / scratch
+ *   not 8-byte aligned, D % 16 != 0, K < 1, M < 1, and an id outside [0, K) or an order entry outside [0, M): the ids are checked on the device before
+ *   anything is read through one, and when one is bad NO output is written.  To report that, the call reads one 16-byte record back: the call synchronises
+ *   `stream` (after everything is queued).  host_record (HOST double [2], may be NULL) receives that record: the objective and the number of empty clusters.
+ *   An order that is not the stable argsort of the ids is not detected: every read stays in bounds and the outputs are unspecified.
+ *   `scratch`: must3r_hip_kmeans_update_scratch_bytes(M, K) device bytes.
+ * must3r_hip_cov_accumulate: x fp32 [M,D] (D % 16 == 0, 16-byte aligned), shift fp64 [D]; with u_r = double(x_r) - shift it accumulates into the caller's
+ *   fp64 state S [D,D] += sum_r u_r u_r^T, s [D] += sum_r u_r, n [1] += M.  The products run on v_mfma_f64_16x16x4_f64 with the rows as the contraction; only
+ *   the 64 x 64 tiles on and below the diagonal are computed, and S[b][a] is written as the copy of S[a][b]: S is exactly symmetric.  The rows are split by a
+ *   rule of (M, D) alone; every split writes fp64 partials that a second launch adds in split order: repeatable bit for bit, no atomics.  Two calls over
+ *   the halves of a chunk and one call over the chunk associate differently and agree to rounding only.  Asynchronous on `stream`.
+ *   `scratch`: must3r_hip_cov_accumulate_scratch_bytes(M, D) device bytes (0 for a refused shape). */
+size_t must3r_hip_kmeans_update_scratch_bytes(int M, int K);
+int must3r_hip_kmeans_update(const float* feat, int M, int D, const float* centroids, int K, const int32_t* ids, int64_t ids_stride, const int64_t* order,
+                             float* new_centroids, int32_t* counts, double* dist, double* objective, double* host_record, void* stream, void* scratch,
+                             size_t scratch_bytes);
+size_t must3r_hip_cov_accumulate_scratch_bytes(int M, int D);
+int must3r_hip_cov_accumulate(const float* x, int M, int D, const double* shift, double* S, double* s, double* n, void* stream, void* scratch,
+                              size_t scratch_bytes);
+
 /* SLAM keyframe test, SURVEY.md section 8f rank 3 (slam/model.py:62-91 get_overlap_score; slam/nns.py:40-92).
  * must3r_hip_nn_query replaces KDTree_scipy.query (nns.py:52-57: scipy KDTree.query(k=1), Euclidean): out_dist[i] =
  * min_j |q_i - db_j| for fp32 xyz points [n,3] on the device, +inf when n_db == 0 (nns.py:53-54).  Exact (brute force).

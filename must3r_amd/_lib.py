@@ -414,6 +414,10 @@ PROTOTYPES = {
     "must3r_hip_asmk_quantize": (i32, [vp, i32, vp, vp, i32, i32, i32, vp, vp, sz, vp]),
     "must3r_hip_asmk_aggregate": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]),
     "must3r_hip_asmk_scores": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, fp, fp, i32, vp, vp]),
+    "must3r_hip_kmeans_update_scratch_bytes": (sz, [i32, i32]),
+    "must3r_hip_kmeans_update": (i32, [vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, P(C.c_double), vp, vp, sz]),
+    "must3r_hip_cov_accumulate_scratch_bytes": (sz, [i32, i32]),
+    "must3r_hip_cov_accumulate": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, sz]),
     "must3r_hip_nn_query": (i32, [vp, i64, vp, i64, vp, vp]),
     "must3r_hip_quadrant_ids": (i32, [vp, i64, P(fp), i32, vp, vp]),
     "must3r_hip_nn_index_bytes": (sz, [i64, i32]),

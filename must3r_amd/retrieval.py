@@ -11,8 +11,12 @@ MFMA, exact products; hidden layers of a multi-layer projector: ``must3r_hip_lay
 
 ``Retriever`` / ``MUSt3R_Retriever`` (processor.py:62-96, demo/inference.py:31-60) add the back-end: the checkpoint's front-end, the
 ASMK codebook next to it and ``must3r_amd.asmk.ASMK`` (quantize, aggregate and score on the GPU, ABI 11), so the encoder tokens
-become the reference's N x N score matrix without leaving the device.  Learning the whitening (``pcawhitenlearn_shrinkage``) and
-training the codebook (k-means) stay out of scope, as in the reference's inference path.
+become the reference's N x N score matrix without leaving the device.
+
+The two learnt artefacts next to the encoder are made here too, so that a model trained with this package can be served in the retrieval mode.  The PCA
+whitening (``pcawhitenlearn_shrinkage``, retrieval/model.py:18-35): ``WhiteningStats`` accumulates the shifted second moments of the features on the device
+(``must3r_hip_cov_accumulate``: fp64 MFMA, exactly symmetric, no atomics), ``finish`` / ``learn_whitening`` / ``Whitener.learn_`` take the one D x D matrix to
+the host for ``numpy.linalg.eigh``.  The ASMK codebook (k-means) is ``must3r_amd.asmk_train``.
 """
 import os
 
@@ -64,6 +68,80 @@ class Whitener(nn.Module):
         if self.l2norm is not None:
             out = l2_normalize(out, self.l2norm)   # the reference normalises the float64 product (:77-78); here its fp32 rounding
         return out.to(x.dtype)
+
+    @torch.no_grad()
+    def learn_(self, x_or_stats, s=1.0):
+        """Write the whitening learnt from features ``x`` [..., dim] (or from a ``WhiteningStats`` fed in chunks) into ``m`` and ``p``, in place."""
+        m, P = x_or_stats.finish(s) if isinstance(x_or_stats, WhiteningStats) else learn_whitening(x_or_stats, s)
+        if tuple(P.shape) != tuple(self.p.shape):
+            raise ValueError(f"the statistics are of dim {P.shape[0]}, the whitener of dim {self.p.shape[0]}")
+        self.m.copy_(torch.from_numpy(m).to(self.m.device))
+        self.p.copy_(torch.from_numpy(P).to(self.p.device))
+        return self
+
+
+class WhiteningStats:
+    """Running fp64 statistics of features for ``pcawhitenlearn_shrinkage`` (retrieval/model.py:18-35), on the device: with the shift fixed at the first
+    chunk (its fp64 column mean) and u = double(x) - shift, ``S = sum u u^T``, ``s = sum u``, ``n`` = rows (``must3r_hip_cov_accumulate``).  Chunks of any size;
+    the state after different chunkings agrees to rounding, not bit for bit (the sums associate differently)."""
+
+    def __init__(self, dim, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("must3r_amd.retrieval.WhiteningStats: device must be CUDA; the HIP path has no CPU fallback")
+        if dim < 1 or dim % 16:
+            raise ValueError(f"WhiteningStats: dim must be a positive multiple of 16, got {dim}")
+        self.dim, self.device = int(dim), device
+        self.S = torch.zeros((dim, dim), dtype=torch.float64, device=device)
+        self.s = torch.zeros((dim,), dtype=torch.float64, device=device)
+        self.n = torch.zeros((1,), dtype=torch.float64, device=device)
+        self.shift = None
+
+    @torch.no_grad()
+    def add(self, x):
+        x = _tokens(x, "x")
+        if x.shape[-1] != self.dim:
+            raise ValueError(f"WhiteningStats of dim {self.dim} fed rows of {x.shape[-1]}")
+        x = x.reshape(-1, self.dim)
+        M = x.shape[0]
+        if M == 0:
+            return self
+        if self.shift is None:
+            self.shift = (x.sum(dim=0, dtype=torch.float64) / M).contiguous()
+        lib = _lib.load()
+        with torch.cuda.device(x.device):
+            nbytes = lib.must3r_hip_cov_accumulate_scratch_bytes(M, self.dim)
+            scratch = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=x.device)
+            _lib.check(lib.must3r_hip_cov_accumulate(x.data_ptr(), M, self.dim, self.shift.data_ptr(), self.S.data_ptr(), self.s.data_ptr(), self.n.data_ptr(),
+                                                     _lib.stream_ptr(x.device), scratch.data_ptr(), nbytes))
+        return self
+
+    def finish(self, s=1.0):
+        """-> (m [1, dim], P [dim, dim]) float64 numpy, the return value of ``pcawhitenlearn_shrinkage(X, s)``"""
+        if self.shift is None:
+            raise ValueError("WhiteningStats.finish: no rows were added")
+        return whitening_from_stats(self.S.cpu().numpy(), self.s.cpu().numpy(), float(self.n.item()), self.shift.cpu().numpy(), s)
+
+
+def whitening_from_stats(S, s_sum, n, shift, s=1.0):
+    """The host part of the whitening: d = s_sum / n, m = shift + d, Xcov = S / n - d d^T, then retrieval/model.py:27-35 with ``numpy.linalg.eigh`` on the
+    symmetric matrix (``eig`` there; on a symmetric matrix the same decomposition up to the sign of each eigenvector, with orthogonality guaranteed)."""
+    d = s_sum / n
+    m = (shift + d)[None, :]
+    Xcov = S / n - np.outer(d, d)
+    eigval, eigvec = np.linalg.eigh(Xcov)
+    order = eigval.argsort()[::-1]
+    eigval = eigval[order]
+    eigvec = eigvec[:, order]
+    eigval = np.clip(eigval, a_min=1e-14, a_max=None)
+    P = np.dot(np.linalg.inv(np.diag(np.power(eigval, 0.5 * s))), eigvec.T)
+    return m, P.T
+
+
+def learn_whitening(x, s=1.0):
+    """``pcawhitenlearn_shrinkage(x, s)`` of CUDA fp32 features ``x`` [..., dim] in one call -> (m, P) float64 numpy."""
+    x = _tokens(x, "x")
+    return WhiteningStats(x.shape[-1], x.device).add(x).finish(s)
 
 
 def l2_normalize(x, dim):
@@ -216,6 +294,20 @@ def codebook_path(modelname):
     return os.path.join(dname, "_".join(bname.split("_")[:-1]) + "_codebook.pkl")
 
 
+def load_frontend(modelname, backbone, device="cuda"):
+    """processor.py:62-82: the retrieval front-end of a checkpoint on ``device`` -> (RetrievalModel, the checkpoint's args); no codebook is needed."""
+    ckpt = torch.load(modelname, "cpu", weights_only=False)
+    a = ckpt["args"]
+    model = RetrievalModel(backbone, freeze_backbone=a.freeze_backbone, prewhiten=a.prewhiten,
+                           hdims=list(map(int, a.hdims.split("_"))) if len(a.hdims) > 0 else "",
+                           residual=getattr(a, "residual", False), postwhiten=a.postwhiten, featweights=a.featweights,
+                           nfeat=a.nfeat).to(device)
+    msg = model.load_state_dict(ckpt["model"], strict=False)
+    if not all(k.startswith("backbone") for k in msg.missing_keys) or len(msg.unexpected_keys) != 0:
+        raise RuntimeError(f"{modelname}: missing {msg.missing_keys}, unexpected {msg.unexpected_keys}")
+    return model, a
+
+
 class Retriever:
     """processor.py:62-96 (construction): the retrieval front-end of a checkpoint and its ASMK codebook, on ``device``."""
 
@@ -227,16 +319,8 @@ class Retriever:
             raise ValueError("Retriever needs the encoder (backbone) the checkpoint was trained on")
         if verbose:
             print(f"Loading retrieval model from {modelname}")
-        ckpt = torch.load(modelname, "cpu", weights_only=False)
-        a = ckpt["args"]
-        self.model = RetrievalModel(backbone, freeze_backbone=a.freeze_backbone, prewhiten=a.prewhiten,
-                                    hdims=list(map(int, a.hdims.split("_"))) if len(a.hdims) > 0 else "",
-                                    residual=getattr(a, "residual", False), postwhiten=a.postwhiten, featweights=a.featweights,
-                                    nfeat=a.nfeat).to(device)
+        self.model, a = load_frontend(modelname, backbone, device)
         self.device = device
-        msg = self.model.load_state_dict(ckpt["model"], strict=False)
-        if not all(k.startswith("backbone") for k in msg.missing_keys) or len(msg.unexpected_keys) != 0:
-            raise RuntimeError(f"{modelname}: missing {msg.missing_keys}, unexpected {msg.unexpected_keys}")
         self.imsize = a.imsize
         cb = codebook_path(modelname)
         if not os.path.isfile(cb):
@@ -244,27 +328,31 @@ class Retriever:
         self.asmk = ASMK(load_codebook(cb, nclusters=getattr(a, "nclusters", None), device=device), alpha=3.0, similarity_threshold=0.0)
 
 
+@torch.no_grad()
+def frontend_local_features(model, enc, device, dim=None):
+    """forward_local of every image's tokens ``enc[i]`` [1, N_i, C] through the front-end ``model``, images with equal token counts in one call ->
+    (feat [M, C] on the device, offsets [n + 1]) with image i on rows [offsets[i], offsets[i+1]).  ``dim``: the width of an empty result."""
+    groups = {}
+    for i, e in enumerate(enc):
+        groups.setdefault(tuple(e.shape[1:]), []).append(i)
+    per_image = [None] * len(enc)
+    for idx in groups.values():
+        x = torch.cat([enc[i].to(device) for i in idx], dim=0)
+        feat, _, _ = model.forward_local(x)
+        for j, i in enumerate(idx):
+            per_image[i] = feat[j]
+    offsets = np.zeros((len(enc) + 1,), dtype=np.int64)
+    offsets[1:] = np.cumsum([f.shape[0] for f in per_image])
+    feat = torch.cat(per_image, dim=0) if per_image else torch.empty((0, model.dim if dim is None else dim), device=device)
+    return feat.contiguous(), offsets
+
+
 class MUSt3R_Retriever(Retriever):
     """demo/inference.py:31-60: encoder tokens of the images -> float64 numpy [n, n] scores (row = query, column = database)."""
 
-    @torch.no_grad()
     def local_features(self, enc, device):
-        """forward_local of every image's tokens ``enc[i]`` [1, N_i, C], images with equal token counts in one call -> (feat [M, C]
-        on the device, offsets [n + 1]) with image i on rows [offsets[i], offsets[i+1])."""
-        groups = {}
-        for i, e in enumerate(enc):
-            groups.setdefault(tuple(e.shape[1:]), []).append(i)
-        per_image = [None] * len(enc)
-        for idx in groups.values():
-            x = torch.cat([enc[i].to(device) for i in idx], dim=0)
-            feat, _, _ = self.model.forward_local(x)
-            for j, i in enumerate(idx):
-                per_image[i] = feat[j]
-        offsets = np.zeros((len(enc) + 1,), dtype=np.int64)
-        offsets[1:] = np.cumsum([f.shape[0] for f in per_image])
-        dim = self.asmk.codebook.shape[1]
-        feat = torch.cat(per_image, dim=0) if per_image else torch.empty((0, dim), device=device)
-        return feat.contiguous(), offsets
+        """``frontend_local_features`` of this retriever's front-end"""
+        return frontend_local_features(self.model, enc, device, dim=self.asmk.codebook.shape[1])
 
     def __call__(self, enc, device):
         feat, offsets = self.local_features(enc, device)
