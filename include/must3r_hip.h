@@ -1485,6 +1485,55 @@ typedef struct must3r_hip_slam_keyframe_args {
 size_t must3r_hip_slam_keyframe_scratch_bytes(int H, int W, int subsamp);
 int must3r_hip_slam_keyframe(const must3r_hip_slam_keyframe_args* a);
 
+/* ABI 21, additive: scene rendering.  A point rasteriser for headless previews (csrc/render.hip, must3r_amd/render.py): what the
+ * reference shows through demo/viser.py and the open3d PipelineView of slam/slam.py -- the confidence-filtered point cloud seen from a pinhole camera -- as
+ * colour, depth and source-index images on the device.  The views are the export's table (ABI 13): conf, pts, rgb, H, W and a 3 x 4 fp64 matrix M per view.
+ *
+ * must3r_hip_render: everything is enqueued on the descriptor's `stream`, nothing is read back, and the host waits only for the staging of the call's own
+ * tables (a ring of 4 pinned slots per calling thread).  Two launches after one memset of the keys:
+ *   splat    The host composes A[c][v] = w2c[c] . M[v] in fp64 with plain scalar loops: per element the three products summed in ascending k, then (in the
+ *            last column) the translation added.  A source pixel with fp32 point (x, y, z) gives per camera, in fp64 with every operation rounded,
+ *                X_a = ((A[a][0] x + A[a][1] y) + A[a][2] z) + A[a][3],   Z = X_2,   u = fx (X_0 (1.0 / Z)) + cx,   v = fy (X_1 (1.0 / Z)) + cy.
+ *            It is dropped, before any conversion to an integer, when conf >= fp32(thr) fails (NaN never passes), when any of x, y, z, u, v is not finite,
+ *            or when Z >= fp64(z_near) and Z <= fp64(z_far) fails.  Otherwise it covers the square of point_size pixels whose first column is
+ *            floor(u - (point_size - 1) / 2) (a true floor: u = -0.3 lands in column -1) and whose first row is floor(v - (point_size - 1) / 2), clipped
+ *            to the image, and every covered target pixel takes a 64-bit unsigned atomicMin of (bits(fp32(Z)) << 32) | global source index (views in
+ *            table order, pixels row-major).  Z is positive there, so the bit pattern orders as the value does; an integer minimum does not depend on
+ *            arrival order, so the images are repeatable bit for bit, and a tie in fp32 depth goes to the lower source index.
+ *   resolve  one thread per target pixel: an empty key gives the background bytes, +inf depth and index 0xFFFFFFFF; otherwise the index, the depth fp32 of
+ *            the key and the colour bytes rint(clip(c, 0, 1) * 255) of the source pixel (the export's rule).
+ * All cameras of one call share (W, H).  Outputs: rgb uint8 [n_cams][H][W][3], depth float32 [n_cams][H][W], index uint32 [n_cams][H][W]; any may be NULL (a
+ * view's rgb plane may be NULL when the rgb output is).
+ * scratch: must3r_hip_render_scratch_bytes(desc) bytes, 256-byte aligned = four sections, each rounded up to 256 bytes: 40 n_views (view table),
+ * 40 n_cams (camera table), 96 n_cams n_views (A) and 8 n_cams H W (keys); 0 with a message on a bad descriptor (its scratch and outputs are not looked at).
+ * Refused before anything is read, uploaded or launched: a NULL descriptor or table; n_views or n_cams < 1; point_size outside
+ * [1, MUST3R_RENDER_MAX_POINT_SIZE]; a view or a camera with a non-positive size; cameras of different sizes; a camera without 0 < z_near <= z_far < inf; a
+ * view of 2^31 or a scene of 2^32 or more pixels; 2^31 or more target pixels; a NULL, small or misaligned scratch; a view with a NULL plane. */
+#define MUST3R_RENDER_MAX_POINT_SIZE 8
+typedef struct must3r_hip_render_camera {
+    double w2c[12];             /* row-major 3x4, world to camera, OpenCV axes: x right, y down, z forward */
+    double fx, fy, cx, cy;
+    float z_near, z_far;
+    int32_t W, H;
+} must3r_hip_render_camera;
+typedef struct must3r_hip_render_desc {
+    const must3r_hip_export_view* views;    /* HOST [n_views] */
+    const must3r_hip_render_camera* cams;   /* HOST [n_cams] */
+    int32_t n_views, n_cams;
+    float thr;
+    int32_t point_size;
+    uint8_t background[3];
+    uint8_t reserved[5];
+    void* scratch;
+    size_t scratch_bytes;
+    uint8_t* rgb;               /* [n_cams, H, W, 3] out, optional */
+    float* depth;               /* [n_cams, H, W] out, optional */
+    uint32_t* index;            /* [n_cams, H, W] out, optional */
+    void* stream;               /* hipStream_t */
+} must3r_hip_render_desc;
+size_t must3r_hip_render_scratch_bytes(const must3r_hip_render_desc* d);
+int must3r_hip_render(const must3r_hip_render_desc* d);
+
 /* timing hooks used by bench.py: per-stage HIP-event timers recorded on the call's stream */
 int must3r_hip_set_profiling(must3r_hip_ctx* ctx, int enabled);
 /* returns the number of records written (<= max); each record: name (<=31 chars), milliseconds, flops.

@@ -18,6 +18,7 @@ EPI_STORE16, EPI_STORE16_GELU, EPI_QKV_ROPE, EPI_RESID_F32, EPI_F32, EPI_HEAD = 
 ABI_VERSION = 21
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
+RENDER_MAX_POINT_SIZE = 8   # MUST3R_RENDER_MAX_POINT_SIZE
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
 LOSS_W_SCALAR, LOSS_W_MEAN, LOSS_W_CONF, LOSS_W_PIXEL = range(4)
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
@@ -111,6 +112,21 @@ class LnFoldOp(C.Structure):
 class ExportView(C.Structure):
     """must3r_hip_export_view: one view of a scene export (include/must3r_hip.h, ABI 13)."""
     _fields_ = [("conf", C.c_void_p), ("pts", C.c_void_p), ("rgb", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_double * 12)]
+
+
+class RenderCamera(C.Structure):
+    """must3r_hip_render_camera: one pinhole camera of a render call (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("w2c", C.c_double * 12), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("z_near", C.c_float), ("z_far", C.c_float), ("W", C.c_int32), ("H", C.c_int32)]
+
+
+class RenderDesc(C.Structure):
+    """must3r_hip_render_desc: the HOST view and camera tables, the threshold, the point size, the background, the scratch, the (optional) DEVICE outputs and
+    the stream of one render call (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("views", C.POINTER(ExportView)), ("cams", C.POINTER(RenderCamera)), ("n_views", C.c_int32), ("n_cams", C.c_int32),
+                ("thr", C.c_float), ("point_size", C.c_int32), ("background", C.c_uint8 * 3), ("reserved", C.c_uint8 * 5),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("rgb", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p),
+                ("stream", C.c_void_p)]
 
 
 class MetricsLossArgs(C.Structure):
@@ -517,6 +533,8 @@ PROTOTYPES = {
     "must3r_hip_slam_pose": (i32, [P(SlamPoseArgs)]),
     "must3r_hip_slam_keyframe_scratch_bytes": (sz, [i32, i32, i32]),
     "must3r_hip_slam_keyframe": (i32, [P(SlamKeyframeArgs)]),
+    "must3r_hip_render_scratch_bytes": (sz, [P(RenderDesc)]),
+    "must3r_hip_render": (i32, [P(RenderDesc)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

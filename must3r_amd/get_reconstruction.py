@@ -47,6 +47,9 @@ def get_cli_parser():
     p = get_args_parser()
     p.add_argument("--gpu_decode", action="store_true", default=False,
                    help="decode baseline JPEGs on the GPU (must3r_amd.jpeg); every other file, and the default, go through Pillow")
+    p.add_argument("--render_dir", type=str, default=None,
+                   help="write headless previews there (must3r_amd.render): one PNG frame per input view from that view's own camera")
+    p.add_argument("--render_views", type=int, default=0, help="with --render_dir: this many orbit frames after the per-view frames")
     return p
 
 
@@ -67,7 +70,8 @@ def main(argv=None):
         num_refinements_iterations=args.num_refinements_iterations, execution_mode=args.execution_mode,
         vidseq_local_context_size=args.local_context_size, keyframe_interval=args.keyframe_interval,
         slam_local_context_size=args.local_context_size, subsample=args.subsample, min_conf_keyframe=args.min_conf_keyframe,
-        keyframe_overlap_thr=args.keyframe_overlap_thr, overlap_percentile=args.overlap_percentile, gpu_decode=args.gpu_decode)
+        keyframe_overlap_thr=args.keyframe_overlap_thr, overlap_percentile=args.overlap_percentile, gpu_decode=args.gpu_decode,
+        render_dir=args.render_dir, render_views=args.render_views)
     # the reference passes cam_size alone to its export calls: camera_conf_thr stays at its default there
     paths = export_scene_thresholds(args.output, scene, thresholds, file_type=args.file_type, as_pointcloud=True, transparent_cams=False,
                                     cam_size=args.cam_size, verbose=True)

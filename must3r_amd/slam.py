@@ -631,13 +631,40 @@ def get_parser():
     parser.add_argument('--viz_conf', default=4., type=float, help="Conf threshold for pts3d vizu")
     parser.add_argument('--gui', action='store_true', default=False, help="Refused: the GUI needs open3d")
     parser.add_argument('--hide_cameras', action='store_true', default=False)
+    parser.add_argument('--render_dir', default=None, type=str,
+                        help="Headless stand-in for the GUI: after the run, write a fly-through there, one PNG frame per pose (must3r_amd.render).")
     return parser
+
+
+def flythrough_points(model, viz_conf):
+    """-> (conf [1, N], pts [1, N, 3], rgb [1, N, 3]), one 1 x N view: the re-rendered pointmaps of all frames when there are any
+    (``all_pts3d``, every point, coloured by its frame), else the keyframe map at ``viz_conf`` (``fetch_memory_map``)."""
+    if model.all_pts3d is not None:
+        pts = model.all_pts3d.reshape(-1, 3)
+        cols = torch.cat([prep_imgs(im['img'], [0.5] * 3, [0.5] * 3).reshape(-1, 3) for im in model.all_images]).to(torch.float32)
+    else:
+        memory_map = model.fetch_memory_map(viz_conf)
+        if memory_map is None:
+            memory_map = get_map(model.keyframe_pointmaps, viz_conf)
+        pts, cols = memory_map
+    n = pts.shape[0]
+    return torch.ones((1, n)), pts.reshape(1, n, 3), cols.reshape(1, n, 3)
+
+
+def render_flythrough(model, outdir, viz_conf=4., W=512, H=384, point_size=2, batch=32):
+    """One ``render.follow_camera`` frame (the reference's ``reset_view``) per pose of ``all_poses`` over ``flythrough_points``, ``batch`` cameras
+    per render call -> the list of paths."""
+    from . import render as _render
+    view = flythrough_points(model, viz_conf)
+    cams = [_render.follow_camera(p.cpu().numpy() if torch.is_tensor(p) else p, W, H) for p in model.all_poses]
+    return _render.render_views(outdir, [view], None, cams, thr=0.5, point_size=point_size, batch=batch)
 
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
     if args.gui:
-        raise SystemExit("must3r_amd.slam: --gui needs open3d, which is not available here; run headless with --output")
+        raise SystemExit("must3r_amd.slam: --gui needs open3d, which is not available here; run headless with --output, and with --render_dir for a "
+                         "rendered fly-through of the map")
     camera = open_input(args.input, args.image_string)
     assert args.output is not None, "You should define an output folder"
     model = SLAM_MUSt3R(chkpt=args.chkpt, res=args.res, kf_x_subsamp=args.subsamp, searcher=args.searcher, overlap_mode=args.overlap_mode,
@@ -681,6 +708,9 @@ def main(argv=None):
         count += 1
     print(f"Dumping memory as {outname}")
     model.save_memory(outname)
+    if args.render_dir is not None:
+        frames = render_flythrough(model, args.render_dir, args.viz_conf)
+        print(f"Wrote {len(frames)} fly-through frames to {args.render_dir}")
 
 
 if __name__ == "__main__":
