@@ -2546,6 +2546,7 @@ static GemmShape gemm_shape(DType dt, Epi epi, const GemmArgs& a) {
             a.x16_out != nullptr || a.copy32_out != nullptr || a.stats_out != nullptr, a.fold256 != 0};
 }
 bool gemm_fold256_shape_ok(int M, int N, int K, bool split) { return gemm_fold256_shape_ok(M, N, K, split, gemm_opts()); }
+GemmOpts gemm_route_opts() { return gemm_opts(); }
 
 // Every family is instantiated for every epilogue and weight form it is built for; `if constexpr` keeps out the ones it is not (the rule never routes there):
 // split weights (ws >= 2) and the fold are fp16 only; gemm48 has no RoPE or head epilogue, gemm96 no head epilogue, the plain gemm256p and the 192-column gemm256 no RoPE one.

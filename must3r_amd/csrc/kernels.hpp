@@ -107,6 +107,8 @@ const char* gemm_last_kernel();
 // 2:4-sparse low part (gemm256s_kernel), else plain fp16 weights (gemm256p_kernel).  The model folds a call's LayerNorms only when every Linear around them says yes.
 // (gemm_route.hpp's predicate of the same name, at the current option values)
 bool gemm_fold256_shape_ok(int M, int N, int K, bool split);
+// the option values launch_gemm hands the rule at this moment, for a caller that asks the rule about launches it is about to make (encode_plan.hpp)
+GemmOpts gemm_route_opts();
 
 // ---------------------------------------------------------------------------------------------
 // fused softmax attention, head dim 64, flash-style (no N x M score matrix in HBM)

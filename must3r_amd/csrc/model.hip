@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "abi.hpp"
+#include "encode_plan.hpp"
 #include "kernels.hpp"
 #include "options.hpp"
 
@@ -870,19 +871,18 @@ extern "C" int must3r_hip_encode(must3r_hip_ctx* c, int dtype, const float* img,
     const int N = (H / 16) * (W / 16);
     // rows per chunk: bounds the workspace (~32k token rows: the 16-bit activations of a chunk stay inside the 256 MB MALL between producer and
     // consumer launches).  M3R_ENC_CHUNK_ROWS: A/B instrument -- larger chunks lose less to the round quantisation of the
-    // one-block-per-CU GEMMs (40 views: 94 % tile fill; 64 / 128 views: 100 %) but stream their activations through HBM.
-    const int chunk_rows = opt(OPT_ENC_CHUNK_ROWS);
-    int per = chunk_rows / N;
-    if (per < 1) per = 1;
-    {   // ... in chunks of equal size (80 views of 768 tokens: 2 x 40 -- 94 % tile fill -- instead of 42 + 38)
-        const int nch = (n_views + per - 1) / per;
-        per = (n_views + nch - 1) / nch;
-    }
-    for (int v0 = 0; v0 < n_views; v0 += per) {
-        const int nv = (n_views - v0 < per) ? n_views - v0 : per;
+    // one-block-per-CU GEMMs (40 views: 93.75 % tile fill; 42 views: 98.4 %; 64 / 128 views: 100 %) but stream their activations through HBM.
+    // Under the cap the chunk sizes come from encode_plan (encode_plan.hpp): the partition whose GEMM rounds are fullest, never more chunks than an equal split
+    // makes (560 views of 768 tokens: 12 x 42 + 35 + 21 instead of 14 x 40; 80 views: 2 x 40 as before, 42 + 38 costs the same rounds and the tie goes to the even
+    // split); shapes that are not on the 256-row kernels keep the equal split.  Every chunk sizes its own workspace, view table and positions (encode_chunk), the largest comes first.
+    const std::vector<int> plan = encode_plan(n_views, N, c->cfg.enc_dim, c->cfg.mlp_ratio * c->cfg.enc_dim, opt(OPT_ENC_CHUNK_ROWS), gemm_route_opts());
+    int v0 = 0;
+    for (const int nv : plan) {
         M3R_OK(encode_chunk(c, c->dt, img +(size_t)v0 * 3 * H * W, nv, H, W, out_tokens + (size_t)v0 * N * c->cfg.enc_dim,
                             out_pos + (size_t)v0 * N * 2, s));
+        v0 += nv;
     }
+    if (v0 != n_views) return fail("encode: the chunk plan covers %d of %d views", v0, n_views);
     return 0;
 }
 
