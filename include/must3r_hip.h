@@ -1534,6 +1534,59 @@ typedef struct must3r_hip_render_desc {
 size_t must3r_hip_render_scratch_bytes(const must3r_hip_render_desc* d);
 int must3r_hip_render(const must3r_hip_render_desc* d);
 
+/* ABI 21, additive: scene rendering, triangles.  A second primitive for the same three images (csrc/render_mesh.hip, csrc/render_tri.hpp; DESIGN.md
+ * section 14.1): the triangles of the exported mesh (must3r_hip_export_scatter_faces), rasterised under the point path's guarantees -- fp64 with every
+ * operation rounded, the same 64-bit key z-buffer, everything on the descriptor's `stream`, nothing read back, one staging slot.  must3r_hip_render, its
+ * descriptor and its bits are unchanged.
+ *   triangles   Per view, each quad anchored at pixel i = r W + c with r < H - 1, c < W - 1 has the corners a = i, b = i + 1, c' = i + W, d = i + W + 1; kind 0
+ *               is (a, b, c'), kind 1 is (b, c', d).  The export writes each in both windings, so the renderer is double-sided and draws each once.
+ *               Triangle id = 2 (global source index of the anchor) + kind; a scene of 2^31 or more pixels is refused.  A view with H < 2 or W < 2 has no
+ *               triangle; that is no error.
+ *   vertices    Each corner is projected exactly as the point path projects a source pixel (A = w2c . M, X_a, Z, u, v above).  A triangle is dropped, before
+ *               any conversion to an integer, when any corner fails the point path's tests: conf >= fp32(thr), finite x, y, z, u, v, and
+ *               z_near <= Z <= z_far.  There is no near-plane clipping: a triangle with a corner outside the depth range is dropped whole.
+ *   candidates  Target pixel (q, r) is sampled at its centre px = q + 0.5, py = r + 0.5 (a point at u lands in column floor(u)).  Columns run from
+ *               ceil(min(u_k) - 0.5) to floor(max(u_k) - 0.5) inclusive, rows likewise, both clipped to the image with fp64 comparisons before any integer
+ *               is formed (u may be 1e300).
+ *   coverage    Number the corners 0, 1, 2 in the order given above, which is ascending source index.  For an edge from corner j to corner k,
+ *                   E_jk(p) = (u_k - u_j) * (py - v_j) - (v_k - v_j) * (px - u_j).
+ *               s0 = E_01, s1 = E_12, s2 = -E_02, den = (s0 + s1) + s2.  The pixel is covered when den is finite and non-zero and s0, s1, s2 are all >= 0
+ *               or all <= 0 (comparisons are false on NaN).  Every edge shared by two triangles is evaluated from its lower-index endpoint in both -- (b, c')
+ *               inside a quad, (b, d) / (a, c') across columns, (c', d) / (a, b) across rows -- so both see the same bits and the inclusive test leaves no
+ *               crack between them; double coverage is harmless under a minimum.
+ *   depth       Perspective-correct: lam0 = s1 / den, lam1 = s2 / den, lam2 = s0 / den; t_k = lam_k * (1.0 / Z_k); iz = (t0 + t1) + t2; Zp = 1.0 / iz.  The
+ *               key is (bits(fp32(Zp)) << 32) | triangle id, taken by the same 64-bit unsigned atomicMin behind the same plain-load early-out.  There is no
+ *               depth-range test after interpolation.  A tie in fp32 depth goes to the lower triangle id.
+ *   resolve     An empty key gives the background, +inf and 0xFFFFFFFF; otherwise the depth is the key's fp32 and `index` is the triangle id.  For colour the
+ *               resolve thread recomputes the triangle's three projections, s, lam, t and Zp at its own pixel from the id; per channel
+ *               c = ((t0 * c0 + t1 * c1) + t2 * c2) * Zp on the corners' fp32 colours widened to fp64, and the byte is the export's
+ *               rint(clip(fp32(c), 0, 1) * 255).  Nothing per pixel is stored beyond the 8-byte key.
+ * A triangle whose candidate box holds at most MUST3R_RENDER_MESH_WAVE_AREA target pixels is rasterised by the lane that owns its anchor; a larger one is
+ * taken by its whole wavefront, whose 64 lanes stride the box.  The result is a minimum over the same (pixel, key) pairs either way.
+ * Outputs, scratch (the same four sections and sizes: must3r_hip_render_mesh_scratch_bytes) and refusals are must3r_hip_render's, without point_size and with
+ * the scene of 2^31 or more pixels. */
+/* Swept on the benchmark scene (200 coherent views of 384 x 512 into 512 x 384; profiles/render_mesh_scratch_builds.jsonl, medians of 7): 8 close cameras take
+ * 24.1 / 16.6 / 15.0 / 15.0 / 15.0 ms at 4 / 16 / 64 / 256 / 1024 and 14.9 ms with the wave path compiled out; 120 orbit cameras 82.5 / 82.9 / 82.2 / 82.5 /
+ * 82.6 ms and 79.0 ms.  A small value hands mid-sized triangles to 64 lanes that mostly idle; from 64 on, one wavefront's worth of samples, the value no longer
+ * shows, because that scene holds almost no larger triangle (241 of 31.7 M at the close cameras).  64 is the smallest value without a measured cost. */
+#define MUST3R_RENDER_MESH_WAVE_AREA 64
+typedef struct must3r_hip_render_mesh_desc {
+    const must3r_hip_export_view* views;    /* HOST [n_views] */
+    const must3r_hip_render_camera* cams;   /* HOST [n_cams] */
+    int32_t n_views, n_cams;
+    float thr;
+    uint8_t background[3];
+    uint8_t reserved[1];
+    void* scratch;
+    size_t scratch_bytes;
+    uint8_t* rgb;               /* [n_cams, H, W, 3] out, optional */
+    float* depth;               /* [n_cams, H, W] out, optional */
+    uint32_t* index;            /* [n_cams, H, W] out, optional: triangle ids */
+    void* stream;               /* hipStream_t */
+} must3r_hip_render_mesh_desc;
+size_t must3r_hip_render_mesh_scratch_bytes(const must3r_hip_render_mesh_desc* d);
+int must3r_hip_render_mesh(const must3r_hip_render_mesh_desc* d);
+
 /* timing hooks used by bench.py: per-stage HIP-event timers recorded on the call's stream */
 int must3r_hip_set_profiling(must3r_hip_ctx* ctx, int enabled);
 /* returns the number of records written (<= max); each record: name (<=31 chars), milliseconds, flops.

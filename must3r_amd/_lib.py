@@ -19,6 +19,7 @@ ABI_VERSION = 21
 ACT_NORM_EXP, ACT_LINEAR = 0, 1
 EXPORT_MAX_THR, EXPORT_GLB, EXPORT_PLY = 8, 0, 1
 RENDER_MAX_POINT_SIZE = 8   # MUST3R_RENDER_MAX_POINT_SIZE
+RENDER_MESH_WAVE_AREA = 64  # MUST3R_RENDER_MESH_WAVE_AREA
 NORM_AVG_DIS, NORM_AVG_LOG1P, NORM_SQRT_DIS, NORM_MEDIAN_DIS = range(4)
 LOSS_W_SCALAR, LOSS_W_MEAN, LOSS_W_CONF, LOSS_W_PIXEL = range(4)
 RESAMPLE_AA_BILINEAR, RESAMPLE_PIL_LANCZOS, RESAMPLE_PIL_BICUBIC, RESAMPLE_NEAREST_EXACT = range(4)
@@ -125,6 +126,14 @@ class RenderDesc(C.Structure):
     the stream of one render call (include/must3r_hip.h, ABI 21, additive)."""
     _fields_ = [("views", C.POINTER(ExportView)), ("cams", C.POINTER(RenderCamera)), ("n_views", C.c_int32), ("n_cams", C.c_int32),
                 ("thr", C.c_float), ("point_size", C.c_int32), ("background", C.c_uint8 * 3), ("reserved", C.c_uint8 * 5),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("rgb", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p),
+                ("stream", C.c_void_p)]
+
+
+class RenderMeshDesc(C.Structure):
+    """must3r_hip_render_mesh_desc: ``RenderDesc`` without the point size, for the triangle rasteriser (include/must3r_hip.h, ABI 21, additive)."""
+    _fields_ = [("views", C.POINTER(ExportView)), ("cams", C.POINTER(RenderCamera)), ("n_views", C.c_int32), ("n_cams", C.c_int32),
+                ("thr", C.c_float), ("background", C.c_uint8 * 3), ("reserved", C.c_uint8 * 1),
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("rgb", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p),
                 ("stream", C.c_void_p)]
 
@@ -535,6 +544,8 @@ PROTOTYPES = {
     "must3r_hip_slam_keyframe": (i32, [P(SlamKeyframeArgs)]),
     "must3r_hip_render_scratch_bytes": (sz, [P(RenderDesc)]),
     "must3r_hip_render": (i32, [P(RenderDesc)]),
+    "must3r_hip_render_mesh_scratch_bytes": (sz, [P(RenderMeshDesc)]),
+    "must3r_hip_render_mesh": (i32, [P(RenderMeshDesc)]),
     "must3r_hip_debug_tr_probe": (i32, [vp, vp]),
     "must3r_hip_set_profiling": (i32, [vp, i32]),
     "must3r_hip_get_profile": (i32, [vp, P(ProfRecord), i32, i32]),

@@ -247,13 +247,13 @@ def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrie
                             execution_mode, num_mem_images, render_once, vidseq_local_context_size, keyframe_interval,
                             slam_local_context_size, subsample, min_conf_keyframe, keyframe_overlap_thr, overlap_percentile,
                             min_conf_thr, as_pointcloud, transparent_cams, local_pointmaps, cam_size, camera_conf_thr=0.0,
-                            loaded_files="", gpu_decode=False, render_dir=None, render_views=0):
+                            loaded_files="", gpu_decode=False, render_mesh=False, render_dir=None, render_views=0):
     """demo/gradio.py:160-217 -> ``(SceneState, None)``: the four execution modes with the reference's arguments.  The output
     parameters are accepted and unused, and ``should_save_glb=True`` is refused: export the returned scene with
     ``get_3D_model_from_scene`` or ``export_scene_thresholds``, as the reference's get_reconstruction.py does.  ``gpu_decode=True`` decodes the
     baseline JPEGs of the file list on the device (``load_images(..., decode="gpu")``, must3r_amd/jpeg.py); the default stays on Pillow.
     ``render_dir`` (default off) writes headless previews there (``render_previews``): one frame per input view from that view's own
-    estimated camera, then ``render_views`` orbit frames."""
+    estimated camera, then ``render_views`` orbit frames; ``render_mesh=True`` draws them from the triangles of the exported mesh, not from points."""
     if should_save_glb:
         raise NotImplementedError("get_reconstructed_scene does not write the GLB / PLY file itself: call it with should_save_glb=False "
                                   "and pass the returned SceneState to get_3D_model_from_scene or export_scene_thresholds")
@@ -293,19 +293,20 @@ def get_reconstructed_scene(outdir, viser_server, should_save_glb, model, retrie
                                  batch_num_views=1, render_once=render_once, is_sequence=is_sequence, viser_server=viser_server,
                                  num_refinements_iterations=num_refinements_iterations, verbose=verbose, **decode)
     if render_dir is not None:
-        render_previews(render_dir, scene, min_conf_thr, render_views, local_pointmaps=local_pointmaps)
+        render_previews(render_dir, scene, min_conf_thr, render_views, local_pointmaps=local_pointmaps, mesh=render_mesh)
     return scene, None
 
 
-def render_previews(render_dir, scene, thr=3.0, n_orbit=0, local_pointmaps=False, point_size=2):
+def render_previews(render_dir, scene, thr=3.0, n_orbit=0, local_pointmaps=False, point_size=2, mesh=False):
     """``frame_%05d.png`` in ``render_dir``: the cloud at confidence >= ``thr`` from every view's own camera (``render.view_camera``: the frame
-    can be laid next to the input photo), then ``n_orbit`` frames from a circle around it, of the size of image 0 -> the list of paths."""
+    can be laid next to the input photo), then ``n_orbit`` frames from a circle around it, of the size of image 0 -> the list of paths.
+    ``mesh=True``: the triangles of the exported mesh instead of squares of ``point_size`` pixels."""
     from . import render as _render
     cams = [_render.view_camera(scene, i) for i in range(len(scene.imgs))]
     if n_orbit > 0:
         H, W = (int(v) for v in scene.imgs[0].shape[:2])
         cams += _render.orbit_cameras(scene, n_orbit, thr, W, H, local_pointmaps=local_pointmaps)
-    return _render.render_scene(render_dir, scene, cams, thr=thr, point_size=point_size, local_pointmaps=local_pointmaps)
+    return _render.render_scene(render_dir, scene, cams, thr=thr, point_size=point_size, local_pointmaps=local_pointmaps, mesh=mesh)
 
 
 @torch.no_grad()

@@ -50,11 +50,15 @@ def get_cli_parser():
     p.add_argument("--render_dir", type=str, default=None,
                    help="write headless previews there (must3r_amd.render): one PNG frame per input view from that view's own camera")
     p.add_argument("--render_views", type=int, default=0, help="with --render_dir: this many orbit frames after the per-view frames")
+    p.add_argument("--render_mesh", action="store_true", default=False,
+                   help="with --render_dir: draw the triangles of the exported mesh instead of points (the reference viewer's default, as_pointcloud=False)")
     return p
 
 
 def main(argv=None):
     args = get_cli_parser().parse_args(argv)
+    if args.render_mesh and args.render_dir is None:
+        raise SystemExit("--render_mesh needs --render_dir")
     images = sorted(os.path.join(args.image_dir, f) for f in os.listdir(args.image_dir) if os.path.isfile(os.path.join(args.image_dir, f)))
     os.makedirs(args.output, exist_ok=True)
     if args.execution_mode == "retrieval" and args.retrieval is None:
@@ -71,7 +75,7 @@ def main(argv=None):
         vidseq_local_context_size=args.local_context_size, keyframe_interval=args.keyframe_interval,
         slam_local_context_size=args.local_context_size, subsample=args.subsample, min_conf_keyframe=args.min_conf_keyframe,
         keyframe_overlap_thr=args.keyframe_overlap_thr, overlap_percentile=args.overlap_percentile, gpu_decode=args.gpu_decode,
-        render_dir=args.render_dir, render_views=args.render_views)
+        render_dir=args.render_dir, render_views=args.render_views, render_mesh=args.render_mesh)
     # the reference passes cam_size alone to its export calls: camera_conf_thr stays at its default there
     paths = export_scene_thresholds(args.output, scene, thresholds, file_type=args.file_type, as_pointcloud=True, transparent_cams=False,
                                     cam_size=args.cam_size, verbose=True)

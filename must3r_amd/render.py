@@ -1,12 +1,13 @@
-"""Headless scene rendering: a point rasteriser for previews of a ``SceneState`` or of a SLAM run's map (what the reference shows through
+"""Headless scene rendering: a point rasteriser and a triangle rasteriser for previews of a ``SceneState`` or of a SLAM run's map (what the reference shows through
 demo/viser.py and the open3d ``PipelineView`` of slam/slam.py), written as PNG frames.
 
 Host planning in fp64 numpy (``view_camera``, ``look_at``, ``follow_camera``, ``orbit_cameras``), the device pass (``SceneRenderer``: one
-splat launch over all cameras and all source pixels, one resolve; csrc/render.hip through the C ABI), ``colorize_grayscale`` for the grey
-panels and ``render_scene`` for the files.  The frames leave the device through one pinned host buffer.
+splat launch over all cameras and all source pixels, one resolve; csrc/render.hip through the C ABI, and with ``mesh=True`` csrc/render_mesh.hip:
+the two triangles per pixel quad that the export writes, into the same three images), ``colorize_grayscale`` for the grey panels and
+``render_scene`` for the files.  The frames leave the device through one pinned host buffer.
 
-The arithmetic order, the key layout and the tie rule are in DESIGN.md section 14.  Not built: triangles and meshes, anti-aliasing, hole
-filling, a live per-frame SLAM view and any interactive server.
+The arithmetic order, the key layout and the tie rule are in DESIGN.md section 14 (triangles: 14.1).  Not built: near-plane clipping and culling
+of stretched triangles, textures, anti-aliasing, hole filling, a mesh of the SLAM map, a live per-frame SLAM view and any interactive server.
 """
 import collections
 import ctypes as C
@@ -158,7 +159,7 @@ class SceneRenderer:
         self.scratch_budget = int(scratch_budget)
         self.scratch = None
 
-    def _call(self, cams, thr, point_size, background, out):
+    def _call(self, cams, thr, point_size, background, out, mesh=False):
         """one native call: cameras of one size -> the slices ``out`` = dict(rgb, depth, index) of device tensors (or None)"""
         table = (_lib.RenderCamera * len(cams))()
         for e, c in zip(table, cams):
@@ -166,12 +167,16 @@ class SceneRenderer:
             for j in range(12):
                 e.w2c[j] = w2c[j]
             e.fx, e.fy, e.cx, e.cy, e.z_near, e.z_far, e.W, e.H = c.fx, c.fy, c.cx, c.cy, c.z_near, c.z_far, c.W, c.H
-        d = _lib.RenderDesc()
+        d = _lib.RenderMeshDesc() if mesh else _lib.RenderDesc()
         d.views, d.cams, d.n_views, d.n_cams = self.table, table, self.n, len(cams)
-        d.thr, d.point_size = float(thr), int(point_size)
+        d.thr = float(thr)
+        if not mesh:
+            d.point_size = int(point_size)
         for a in range(3):
             d.background[a] = int(background[a])
-        nbytes = self.lib.must3r_hip_render_scratch_bytes(C.byref(d))
+        scratch_bytes, run = ((self.lib.must3r_hip_render_mesh_scratch_bytes, self.lib.must3r_hip_render_mesh) if mesh else
+                              (self.lib.must3r_hip_render_scratch_bytes, self.lib.must3r_hip_render))
+        nbytes = scratch_bytes(C.byref(d))
         if nbytes == 0:
             _lib.check(1)
         if self.scratch is None or self.scratch.numel() < nbytes:
@@ -180,17 +185,22 @@ class SceneRenderer:
         d.scratch, d.scratch_bytes = self.scratch.data_ptr(), self.scratch.numel()
         d.rgb, d.depth, d.index = (None if out[k] is None else out[k].data_ptr() for k in ("rgb", "depth", "index"))
         d.stream = _lib.stream_ptr(self.device)
-        _lib.check(self.lib.must3r_hip_render(C.byref(d)))
+        _lib.check(run(C.byref(d)))
 
-    def render(self, cameras, thr, point_size=1, background=(255, 255, 255), want=("rgb", "depth", "index")):
+    def render(self, cameras, thr, point_size=1, background=(255, 255, 255), want=("rgb", "depth", "index"), mesh=False):
         """-> one dict per camera, in the cameras' order, of device tensors: ``rgb`` uint8 [H, W, 3], ``depth`` float32 [H, W] (+inf where
         nothing landed), ``index`` uint32 [H, W] (0xFFFFFFFF there; else views in order, pixels row-major) -- those named in ``want``.
         Cameras are grouped by (W, H), each group is one tensor per output, and a group goes to the library in chunks whose z-buffers stay
-        inside the scratch budget.  Everything is enqueued on the current stream; nothing is read back."""
+        inside the scratch budget.  Everything is enqueued on the current stream; nothing is read back.
+        ``mesh=True`` draws the triangles of the exported mesh instead (two per quad of every view's pixel grid, perspective-correct depth and
+        colour): ``index`` is then the triangle id, 2 x (source index of the quad's first pixel) + (0 upper-left, 1 lower-right triangle), and
+        ``point_size`` must be left at 1."""
         cameras = list(cameras)
         unknown = set(want) - {"rgb", "depth", "index"}
         if unknown or not want:
             raise ValueError(f"render: want {tuple(want)} is not a non-empty subset of ('rgb', 'depth', 'index')")
+        if mesh and int(point_size) != 1:
+            raise ValueError(f"render: point_size {point_size} with mesh=True; triangles have no point size, leave it at 1")
         if not 1 <= int(point_size) <= _lib.RENDER_MAX_POINT_SIZE:
             raise ValueError(f"render: point_size {point_size} is outside [1, {_lib.RENDER_MAX_POINT_SIZE}]")
         result = [None] * len(cameras)
@@ -207,7 +217,7 @@ class SceneRenderer:
                 for c0 in range(0, len(ids), chunk):
                     sel = ids[c0:c0 + chunk]
                     self._call([cameras[i] for i in sel], thr, point_size, background,
-                               {k: None if t is None else t[c0:c0 + len(sel)] for k, t in full.items()})
+                               {k: None if t is None else t[c0:c0 + len(sel)] for k, t in full.items()}, mesh)
                 for j, i in enumerate(ids):
                     result[i] = {k: t[j] for k, t in full.items() if t is not None}
         return result
@@ -247,16 +257,17 @@ def depth_panel(depth):
     return (torch.where(hit[..., None], grey, torch.zeros_like(grey)) * 255).round().to(torch.uint8)
 
 
-def render_views(outdir, views, matrices, cameras, thr=3.0, point_size=2, depth=False, background=(255, 255, 255), start=0, batch=32):
+def render_views(outdir, views, matrices, cameras, thr=3.0, point_size=2, depth=False, background=(255, 255, 255), start=0, batch=32, mesh=False):
     """``render_scene`` for any list of (conf, pts, rgb) views: ``frame_%05d.png`` (and ``depth_%05d.png``) from ``start`` on, ``batch``
-    cameras per render call -> the list of frame paths."""
+    cameras per render call -> the list of frame paths.  ``mesh=True``: triangles, and ``point_size`` is not used."""
     os.makedirs(outdir, exist_ok=True)
     renderer = SceneRenderer(views, matrices)
     writer = _FrameWriter()
     cameras = list(cameras)
     paths = []
     for c0 in range(0, len(cameras), batch):
-        images = renderer.render(cameras[c0:c0 + batch], thr, point_size, background, want=("rgb", "depth") if depth else ("rgb",))
+        images = renderer.render(cameras[c0:c0 + batch], thr, 1 if mesh else point_size, background, want=("rgb", "depth") if depth else ("rgb",),
+                                 mesh=mesh)
         for j, im in enumerate(images):
             k = start + c0 + j
             paths.append(writer.write(os.path.join(outdir, "frame_%05d.png" % k), im["rgb"]))
@@ -265,8 +276,9 @@ def render_views(outdir, views, matrices, cameras, thr=3.0, point_size=2, depth=
     return paths
 
 
-def render_scene(outdir, scene, cameras, thr=3.0, point_size=2, local_pointmaps=False, depth=False, background=(255, 255, 255), start=0):
+def render_scene(outdir, scene, cameras, thr=3.0, point_size=2, local_pointmaps=False, depth=False, background=(255, 255, 255), start=0, mesh=False):
     """One ``frame_%05d.png`` per camera of the points of ``scene`` with confidence >= ``thr``; ``depth=True`` also writes
-    ``depth_%05d.png``, the grey panel of the rendered depth with empty pixels black -> the list of frame paths."""
+    ``depth_%05d.png``, the grey panel of the rendered depth with empty pixels black -> the list of frame paths.  ``mesh=True`` draws the
+    scene's mesh (what ``get_3D_model_from_scene(as_pointcloud=False)`` exports) instead of its points."""
     return render_views(outdir, scene_views(scene, local_pointmaps), _matrices(scene, local_pointmaps), cameras, thr, point_size, depth,
-                        background, start)
+                        background, start, mesh=mesh)
